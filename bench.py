@@ -8,7 +8,9 @@ before the timed region starts.  With N > 1 ranks the block schedule of embeddin
 row % N, N episodes per global batch of N x the single-GPU batch, the syn1neg partitions passed round a ring of point-to-point RCCL
 transfers (`--multi-gpu allreduce` = the walk-shard + delta-averaging scheme, kept for comparison).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 (contract in the task statement) with a `roofline` object.  A plain run does only what that line's
+headline needs: set-up, warm-up, the timed steps and, with `--dump-outputs DIR`, the arrays of the last timed step.  `--full` adds the
+figures that take runs of their own: the CPU baseline (`cpu_baseline`) and the box's copy rate and the model's row rates in `roofline`.
 """
 import argparse
 import json
@@ -73,7 +75,16 @@ def main():
     ap.add_argument("--hs", action="store_true", help="train the hierarchical-softmax term as well (dge_train_config.use_hs; not the headline path)")
     ap.add_argument("--policy", type=int, default=0, help="dge_train_config.update_policy (0 auto = float atomics)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, in runs of their own outside the timed steps: the CPU baseline (unless --no-cpu-baseline), "
+                         "the box's device copy rate and the model's random-row rates (roofline.box_copy_GBps, row_read_GBps, row_rewrite_GBps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: after the timed steps write what the last step computed reproducibly to DIR/<name>.npy, at most 64 MB: a fixed, seeded sample "
+                         "of the step's walks (float64; -1 = past a dead end) with their global walk indices, the trainer's count of pairs and words over the "
+                         "timed steps and, where the schedule that ran fixes the order of the updates (owner-computes or one in-order worker), the same sample "
+                         "of vocabulary rows of syn0, syn1neg (and syn1 with --hs) with their vertex ids.  The Hogwild schedules (the headline's commit locks "
+                         "among them) update shared rows in an order that differs from run to run, so two runs' tables differ beyond rounding: they are not written")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--force-exchange", action="store_true", help="run the delta exchange even with one rank (plumbing check)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -95,6 +106,10 @@ def main():
                     help="ranks only meet (init_process_group, all-reduce, barrier) and rank 0 prints {\"n_gpus\": N, ...}: checks the "
                          "launcher on a box without a GPU; nothing is measured")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus > 1 or args.epoch):
+        ap.error("--dump-outputs writes the tables of one GPU's timed steps: not with --gpus > 1 or --epoch")
 
     # `python bench.py --gpus N` (the driver's command shape) with no torchrun environment: start the N ranks here.  The
     # parent touches neither torch nor HIP, it waits for the children and exits with their status; rank 0 of the children
@@ -257,9 +272,9 @@ def main():
     if exchange:
         delta = torch.empty(model.sync_size(), dtype=torch.float32, device=dev)
         model.snapshot()
-    copy_rate = box_copy_rate(dev) if rank == 0 else None
+    copy_rate = box_copy_rate(dev) if rank == 0 and args.full else None
     row_rates = None
-    if rank == 0 and NV * (-(-D // 64) * 64) * 4 < 0xFFFFFFFF:      # (the probe addresses a table through one descriptor)
+    if rank == 0 and args.full and NV * (-(-D // 64) * 64) * 4 < 0xFFFFFFFF:      # (the probe addresses a table through one descriptor)
         row_rates = model.row_rates()        # this model's own tables: random rows read / read + written back (GB/s), lock exchanges, table look-ups per s
     setup_s = time.time() - t0
 
@@ -321,6 +336,18 @@ def main():
     sync()
     dt = time.perf_counter() - t1
     st = model.stats()
+    if args.dump_outputs:
+        last = args.warmup + args.steps - 1
+        row0, n_last = (0, BG) if blocks else ((last * B) % max(shard - B + 1, 1), B)
+        index0 = (last * BG) % max(epoch_walks - BG + 1, 1) if blocks else shard0 + row0      # global index of the step's first walk
+        ran = model.schedule()
+        # the tables are a reproducible result only where the schedule that trained them fixes the order of the updates: owner-computes (8) or one
+        # in-order worker.  Under the Hogwild schedules (1, 2, 5, 6, 7: the headline's commit locks among them) concurrent workers meet on shared rows
+        # in an order that differs from run to run, and relaxed commit may lose an update: two runs end with tables that differ beyond rounding.
+        tables = ran["update_policy"] in (0, 8) or ran["workers"] == 1
+        names = dump_outputs(args.dump_outputs, model, corpus_rows(E, corpus, row0, n_last), index0, (st["pairs"], st["words"]), args.hs, tables)
+        stage("outputs of step %d written to %s: %s%s" % (last, args.dump_outputs, ", ".join(names), "" if tables else
+              " (not the tables: policy %d with %d workers updates them in an order that differs from run to run)" % (ran["update_policy"], ran["workers"])))
     if blocks and N == 1 and args.sim_episode_times:
         episode_log = []
         step(args.warmup + args.steps)
@@ -390,15 +417,17 @@ def main():
                          "hs_path_rows_per_centre": hs_path,
                          "walk_kernel_ms_per_launch": st["walk_kernel_ms"] / launches,
                          "walk_steps_per_s": (B * L) / (st["walk_kernel_ms"] / launches * 1e-3) if st["walk_kernel_ms"] > 0 else None,
-                         "walk_bytes_per_step": 36, "box_copy_GBps": copy_rate,
-                         "row_read_GBps": row_rates and round(row_rates[0], 1), "row_rewrite_GBps": row_rates and round(row_rates[1], 1),
+                         "walk_bytes_per_step": 36,
                          # what the lock kernel actually runs against (profiles/r03_shape_sweep.txt): requests at the L2's memory side — reads leave as 128 bytes,
                          # writes as 64 — at ~8.5e10/s in every shape measured; from the committed PMC passes like `traffic`, not from counters of this run
                          "fabric_requests_per_s": None if (args.dim or args.negative >= 0 or NB > 1) else measured_requests(args.workload, ("hs_centre" if "hsw" in kernel_name else "hs_pairs") if args.hs else "policy%d" % sched["update_policy"], pairs_per_launch, ms_per_launch, stamp)},
         }
         if "expect_policy" in wl and not (args.policy or args.workers or args.hs or NB > 1) and sched["update_policy"] != wl["expect_policy"]:
             print("warning: workload %s resolved to policy %d, the committed traffic profile is for policy %d" % (args.workload, sched["update_policy"], wl["expect_policy"]), file=sys.stderr)
-        if N == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"].update({"box_copy_GBps": copy_rate, "row_read_GBps": row_rates and round(row_rates[0], 1),
+                                    "row_rewrite_GBps": row_rates and round(row_rates[1], 1)})
+        if args.full and N == 1 and not args.no_cpu_baseline:
             sample = g.sample_walks(min(shard, 400_000), L, seed=WALK_SEED, rng_mode=1, first_index=shard0)   # = first rows of the corpus
             out["cpu_baseline"] = cpu_baseline(sample, NV, D, L, K, args.cpu_seconds)
         print(json.dumps(out), flush=True)
@@ -581,6 +610,61 @@ def cpu_baseline(walks, NV, D, L, K, seconds):
         w8 = run(min(8, cores), 0.4 * seconds)
         out["reference_workers_8"] = {k: w8[k] for k in ("value", "cores", "sample")}     # .workers(8), J/DeepWalk.java:75
     return out
+
+
+DUMP_SEED = 20240601
+DUMP_BYTES = 64 << 20
+
+
+def corpus_rows(E, corpus, row0, n):
+    """Rows [row0, row0 + n) of a device walk corpus as a host int32 array — one copy of those rows only, not of the whole corpus
+    (WalkCorpus.to_host), through the HIP runtime libdge.so is linked against."""
+    import ctypes as C
+
+    import numpy as np
+    n_all, L = corpus.shape
+    assert 0 <= row0 and row0 + n <= n_all
+    d = C.c_void_p(0)
+    E._native.check(E.lib.dge_walks_info(corpus._h, None, None, C.byref(d)))
+    out = np.empty((n, L), np.int32)
+    copy = E.lib.hipMemcpy
+    copy.restype, copy.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    rc = copy(out.ctypes.data, d.value + row0 * L * 4, out.nbytes, 2)           # hipMemcpyDeviceToHost
+    if rc:
+        raise RuntimeError("hipMemcpy of walk rows [%d, %d) failed: error %d" % (row0, row0 + n, rc))
+    return out
+
+
+def dump_outputs(out_dir, model, walks, index0, counts, hs, tables=True):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as float32 / float64 .npy files — a seeded sample of
+    the walks that step sampled (walks[i] has the global walk index index0 + i) with those indices, the trainer's own count of the pairs and
+    words it trained over the timed steps (`counts`: SgnsModel.stats; one count per item, whatever the order of the updates) and, with `tables`, the model's tables
+    (SgnsModel.vectors / syn1neg / syn1: too large to write whole at the bench's sizes, so the same seeded sample of vocabulary rows of each,
+    with the rows' vertex ids).  Samples depend only on the table and batch sizes, so two builds run with the same arguments write the same
+    rows.  -> the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    L = walks.shape[1]
+    rng = np.random.default_rng(DUMP_SEED)
+    n_walks = min(len(walks), 16384, (DUMP_BYTES // 8) // (8 * (L + 1)))
+    picked = np.sort(rng.choice(len(walks), n_walks, replace=False))
+    out = {"walks": walks[picked].astype(np.float64), "walk_index": (index0 + picked).astype(np.float64),
+           "train_counts": np.array(counts, np.float64)}
+    if tables:
+        syn0, vid = model.vectors()
+        tabs = {"syn0": syn0, "syn1neg": model.syn1neg()}
+        if hs:
+            tabs["syn1"] = model.syn1()                # V - 1 inner nodes: sampled among the rows it has
+        V, D = syn0.shape
+        n_rows = min(V, 16384, (DUMP_BYTES - n_walks * (L + 1) * 8 - 16) // (4 * D * len(tabs) + 8))
+        rows = np.sort(rng.choice(V, n_rows, replace=False))
+        out["vocab_ids"] = vid[rows].astype(np.float64)
+        for name, t in tabs.items():
+            out[name] = np.ascontiguousarray(t[rows[rows < len(t)]], dtype=np.float32)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
 
 
 def box_copy_rate(dev):

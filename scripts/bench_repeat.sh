@@ -3,7 +3,7 @@
 # placement luck shows: profiles/r02_box_drift.txt) -> one line per run: edges/s, roofline fraction, ms per launch, the placement search's report
 n=$1; shift
 for i in $(seq 1 $n); do
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" 2> gpurun_out/bench_repeat_$i.err | python3 -c "
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" 2> "${TMPDIR:-/tmp}/bench_repeat_$i.err" | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,6 +8,6 @@ WATCH=$!
 f() { python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', d['roofline']['ms_per_launch'], d['roofline'].get('box_copy_GBps'))"; }
 for r in 1 2 3; do
   echo "run $r starts $(date +%s.%N)" >> gpurun_out/clock_runs.txt
-  python3 bench.py --no-cpu-baseline --steps 6 --warmup 1 2>/dev/null | f run$r
+  python3 bench.py --full --no-cpu-baseline --steps 6 --warmup 1 2>/dev/null | f run$r
 done
 wait $WATCH

@@ -71,3 +71,13 @@ def test_rank_without_a_device_leaves_before_the_rendezvous():
 def test_launcher_refuses_to_start_ranks_under_a_profiler():
     out = _run(["--gpus", "2", "--backend", "gloo", "--rendezvous-check"], env={"LD_PRELOAD_PROBE": "", "ROCP_TOOL_LIBRARIES": "/opt/rocm/lib/librocprofiler-sdk-tool.so"})
     assert out.returncode == 2 and "one rank per rocprofv3 process" in out.stderr and "torch.distributed.run" not in out.stderr
+
+
+def test_steps_and_dump_outputs_are_checked_before_any_rank_starts():
+    # --steps sets the number of timed steps, and zero timed steps is refused; --dump-outputs writes one GPU's outputs, so it is refused with several ranks
+    for args, msg in ((["--steps", "0"], "--steps must be at least 1"),
+                      (["--gpus", "2", "--backend", "gloo", "--dump-outputs", "out"], "--dump-outputs"),
+                      (["--epoch", "--dump-outputs", "out"], "--dump-outputs")):
+        out = _run(args + ["--workload", "tiny"], timeout=120)
+        assert out.returncode == 2 and msg in out.stderr and "torch.distributed.run" not in out.stderr, out.stderr[-1500:]
+        assert not [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
