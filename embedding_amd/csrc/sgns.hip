@@ -636,45 +636,14 @@ extern "C" int dge_model_create(int device, const dge_train_config* cfg, const i
         MH(hipMemcpyAsync(m->h_vocab_ids.data(), m->d_vocab_ids, V * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
     MH(hipStreamSynchronize(st));
-    int64_t tw = 0;
-    for (int64_t i = 0; i < V; i++) tw += m->h_counts[(size_t)i];
-    m->total_words = tw;
+    m->stats = schedule_stats(m->h_counts.data(), V, m->D, m->stride, m->n_cus);
 
     // --- unigram^0.75 cumulative (word2vec.c InitUnigramTable's running d1; a serial double sum by definition)
     dge_tmp<int32_t> d_flat;                                 // word2vec's one-row-per-slot table: a temporary, the trainers read its rank-block form
     MC(d_flat.alloc((size_t)m->T));
     if (V > 0) {
         std::vector<double> cum((size_t)V);
-        double twp = 0.0; const double power = 0.75;
-        for (int64_t i = 0; i < V; i++) twp += pow((double)m->h_counts[(size_t)i], power);
-        {
-            double s2 = 0.0;
-            for (int64_t i = 0; i < V; i++) { double q = pow((double)m->h_counts[(size_t)i], power) / twp; s2 += q * q; }
-            m->neg_collision = s2; m->neg_norm = twp;
-            m->row_share_max = std::max((double)m->h_counts[0] / (double)std::max<int64_t>(tw, 1), pow((double)m->h_counts[0], power) / twp);
-            // Head of the vocabulary for the mixed policy (7).  A try-lock fails when another worker holds the row: per pair
-            // ~5 syn1neg rows drawn with q_i (unigram^0.75) and one syn0 row that occurs with p_i (unigram), held for the whole
-            // pair.  Expected failures per attempt with W workers ~ W * 5 * (sum q_i^2 + sum p_i^2) over the LOCKED rows; the
-            // head [0, H) is taken out until that is below 0.1.  (cfg3: 0.14 with H = 0 — left alone, see train_rows; cfg5: 3.3 M
-            // rows, H ~ 1e4.)
-            const double W0 = (double)((int64_t)m->n_cus * 3 * 16);
-            double tail = 0.0; int64_t H = V;
-            while (H > 0) {
-                const double c = (double)m->h_counts[(size_t)(H - 1)];
-                const double q = pow(c, power) / twp, pp = c / (double)tw;
-                if (W0 * 5.0 * (tail + q * q + pp * pp) >= 0.1) break;
-                tail += q * q + pp * pp; H--;
-            }
-            m->hot_rows_auto = H;
-            // A second, sharper reason to keep a row out of the lock protocol: the pair holds its syn0 row's lock for its whole
-            // duration, so the pairs whose context is row i run one after the other — p_i * pairs of them, while the launch as a
-            // whole lasts pairs / W pair-times.  A row with W * p_i near 1 therefore becomes the critical path of the launch
-            // (measured: ONE vertex with 1e-4 of all tokens in an otherwise flat 1 M-row vocabulary — W * p = 1.2 — slows the lock
-            // kernel by 20-25 %; the bench graph's busiest row has 0.36).  Rows beyond 0.5 go to the atomics side.
-            int64_t Hs = 0;
-            while (Hs < V && W0 * (double)m->h_counts[(size_t)Hs] / (double)tw > 0.5) Hs++;
-            m->hot_rows_serial = Hs;
-        }
+        const double twp = m->stats.neg_norm, power = 0.75;
         double d1 = 0.0;
         for (int64_t i = 0; i < V; i++) { d1 = (i == 0) ? pow((double)m->h_counts[0], power) / twp : d1 + pow((double)m->h_counts[(size_t)i], power) / twp; cum[(size_t)i] = d1; }
         dge_tmp<double> d_cum; dge_tmp<int32_t> d_g, d_m; dge_tmp<char> d_tmp2;
@@ -767,15 +736,7 @@ extern "C" int dge_model_create(int device, const dge_train_config* cfg, const i
         // inner-node table (V rows allocated, V-1 used: the tables stay the same size for the delta exchange) and paths
         std::vector<int64_t> node_w;
         const int longest = dge_huffman_paths(m->h_counts.data(), V, m->h_hs_off, m->h_hs_points, m->h_hs_codes, &node_w);
-        // cold inner nodes: on fewer than 2e-5 of all paths (their weights ascend with the node number: a prefix)
-        { int64_t tot = 0; for (int64_t c : m->h_counts) tot += c;
-          const int64_t limit = (int64_t)((double)tot * 2e-5);
-          m->hs_cold_auto = (int32_t)(std::upper_bound(node_w.begin(), node_w.end(), limit) - node_w.begin());
-          // busy inner nodes: on a tenth of all paths and more (a suffix; the balanced tree of a flat vocabulary has 15 of them, a skewed one a few more) — at most 64
-          const int64_t busy = (int64_t)((double)tot * 0.1);
-          m->hs_rep_auto = (int32_t)std::min<int64_t>(64, node_w.end() - std::lower_bound(node_w.begin(), node_w.end(), busy));
-          for (int k = 0; k < 32; k++)     // first node on more than k/32 of all paths (weights ascend with the node number)
-              m->hs_rep_thr32[k] = (int32_t)(std::upper_bound(node_w.begin(), node_w.end(), (int64_t)((double)tot * k / 32.0)) - node_w.begin()); }
+        schedule_stats_hs(m->stats, node_w);
         // (behind the table: HS_REP_ROWS spare rows for k_sgns_train_hsw's copies of the busiest inner nodes — zero between launches)
         MC(table_alloc(&m->d_syn1, tab + 64 + (size_t)HS_REP_ROWS * m->stride, device, st, &m->placed_seen[2], &m->placed_best[2], &m->placed_worst[2]));
         MH(hipMemsetAsync(m->d_syn1, 0, (tab + 64 + (size_t)HS_REP_ROWS * m->stride) * sizeof(float), st));
@@ -815,12 +776,12 @@ static int ensure_work(dge_model* m, int64_t n_rows, int32_t L) {
 }
 
 // the trainer kernels are compiled per row width in sgns_train_dch.hip (one object per DCH)
-void dge_launch_train_dch1(const TrainParams& p, int pol, bool big, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st);
-void dge_launch_train_dch2(const TrainParams& p, int pol, bool big, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st);
-void dge_launch_train_dch3(const TrainParams& p, int pol, bool big, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st);
-void dge_launch_train_dch4(const TrainParams& p, int pol, bool big, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st);
-void dge_launch_train_dch6(const TrainParams& p, int pol, bool big, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st);
-void dge_launch_train_dch8(const TrainParams& p, int pol, bool big, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st);
+void dge_launch_train_dch1(const TrainParams& p, const TrainPlan& plan, hipStream_t st);
+void dge_launch_train_dch2(const TrainParams& p, const TrainPlan& plan, hipStream_t st);
+void dge_launch_train_dch3(const TrainParams& p, const TrainPlan& plan, hipStream_t st);
+void dge_launch_train_dch4(const TrainParams& p, const TrainPlan& plan, hipStream_t st);
+void dge_launch_train_dch6(const TrainParams& p, const TrainPlan& plan, hipStream_t st);
+void dge_launch_train_dch8(const TrainParams& p, const TrainPlan& plan, hipStream_t st);
 
 // Launch timing: a pair of events per kernel launch, read by dge_model_stats.  A host that trains in a long loop without asking for
 // stats must not pile up event handles: launches of one model complete in stream order, so once 64 pairs are pending the finished
@@ -853,57 +814,6 @@ static int timing_end(dge_model* m, EventPair& ev, int rc_so_far) {
     return DGE_OK;
 }
 
-// Head of the vocabulary inside ONE BLOCK of an n-rank block schedule (dge_model_set_partition).  A block's live rows are the V / n rows of its
-// partition, and a row of the partition takes n times its share of the block's accesses (negatives drawn from the whole table are moved to the
-// partition's row nearest below: n rows' worth of draws; contexts: the pairs whose context lies in the partition), so over the locked rows the
-// expected failures per try-lock are W * 5 * n^2 * sum_{partition}(q_i^2 + p_i^2) ~ W * 5 * n * sum_{all}(q_i^2 + p_i^2): the rule of
-// dge_model_create with the bound divided by n.  And a context row whose own pairs — serialised by its lock — are more than half of what one worker
-// trains in the launch (W * n * p_i > 0.5) goes to the atomics side as well.  Rows [0, head) take atomics, the rest stay under the commit locks.
-// Round 5, with the hottest rows' chains gone (the accumulator banks), the head size was swept again per graph (profiles/r05_skewed_knobs_*.txt, r05_blocks_head_quality_*.txt):
-// a block's speed has a flat optimum — cfg3_zipf 20 000 .. 160 000 rows within 2 %, cfg5 15 000 .. 60 000 (best 30 000: 8.47e7 against 8.31e7 at the 60 320 of the
-// 0.1 bound), the cfg3-sized community graph with a Zipf fifth 20 000 .. 40 000 (10 % faster than the 183 340 of the 0.1 bound) — and the embedding does not depend on it
-// (AUC / loss equal to the fourth digit from 10 000 to 183 340 rows).  A bound of 0.2 puts all three inside their optimum (44 222 / ~30 000 / 60 380 rows).
-static int64_t block_head(dge_model* m, int n, int64_t W) {
-    if (m->block_head_n == n && m->block_head_workers == W) return m->block_head_rows;
-    const double power = 0.75, twp = m->neg_norm, tw = (double)std::max<int64_t>(m->total_words, 1);
-    double tail = 0.0; int64_t H = m->V;
-    const double bound = 0.2 / (5.0 * (double)W * (double)std::max(n, 1));     // (round 5: 0.1 until the accumulator banks; see below)
-    while (H > 0) {
-        const double c = (double)m->h_counts[(size_t)(H - 1)];
-        const double q = pow(c, power) / twp, pp = c / tw;
-        if (tail + q * q + pp * pp >= bound) break;
-        tail += q * q + pp * pp; H--;
-    }
-    int64_t Hs = 0;
-    while (Hs < m->V && (double)W * (double)n * (double)m->h_counts[(size_t)Hs] / tw > 0.5) Hs++;
-    m->block_head_n = n; m->block_head_workers = W; m->block_head_rows = std::max(H, Hs);
-    return m->block_head_rows;
-}
-
-// What update_policy 0 resolves to for a device-filling launch over the whole vocabulary on one GPU — 5 (commit locks), 7 (locks, the head by atomics) or 2
-// (atomics); the owner-computes schedule (8) is taken instead of 2 where it applies (train_rows).  The rule's constants were fitted on the four bench graphs
-// and then checked — and moved — against a sweep of vocabulary size x popularity exponent x row width (scripts/policy_sweep.py, profiles/r04_policy_sweep.txt):
-//   * the commit locks are the fast schedule while a try-lock rarely fails: expected failures per attempt ~ workers * 5 * sum q_i^2 < 0.4 on a vocabulary of
-//     >= 131 072 rows (round 3: 0.25 and 262 144 — a flat 200 000-row vocabulary runs 1.46e9 edges/s under locks against 1.19e9 owner-computes);
-//   * a skewed vocabulary keeps the locks for its tail when the head that has to leave them is at most a quarter of the rows (round 3: an eighth — rank^-0.5
-//     popularity over 300 000 rows: 9.5e8 against 7.3e8 owner-computes);
-//   * when the busiest row's share caps the workers below a quarter of the device (48 / its share of the tokens < 4096 workers; train_rows then caps the workers at 96 in flight), the lock protocol has
-//     nothing to win over atomics (rank^-1 over 300 000 words: 1.37e8 against 5.9e7).
-// (the first two conditions alone: a try-lock on a syn1neg row rarely fails — what the hierarchical-softmax kernel's lock form needs; it never locks a context row,
-//  so a vocabulary with a handful of rows whose OWN pairs would serialise under a syn0 lock, policy 7 with a tiny head, takes it as well)
-static bool syn1neg_locks_work(const dge_model* m) {
-    const double fail = (double)((int64_t)m->n_cus * 3 * 16) * 5.0 * m->neg_collision;
-    return (int64_t)(48.0 / std::max(m->row_share_max, 1e-12)) >= 4096 && m->V >= 131072 && fail < 0.4;
-}
-static int auto_policy(const dge_model* m, bool hs) {
-    if (hs) return 2;
-    const double fail = (double)((int64_t)m->n_cus * 3 * 16) * 5.0 * m->neg_collision;
-    if ((int64_t)(48.0 / std::max(m->row_share_max, 1e-12)) < 4096) return 2;
-    if (m->V >= 131072 && fail < 0.4) return m->hot_rows_serial > 0 ? 7 : 5;
-    if (m->V >= 131072 && m->hot_rows_auto <= m->V / 4) return 7;
-    return 2;
-}
-
 // k_sgns_train_hsw's copies of the busiest inner nodes: row j of `rows` += its HS_REP - 1 copies, which are cleared (one workgroup a node; runs behind the trainer)
 __global__ void k_hs_rep_fold(float* rows, float* rep, int32_t n_rep, int32_t stride) {
     const int j = blockIdx.x;
@@ -929,349 +839,67 @@ static int train_rows(dge_model* m, const int32_t* d_rows, int64_t n_rows, int32
         m->seen_rows = d_rows; m->seen_n = n_rows; m->seen_L = L; m->seen_gen = corpus_gen;
     }
 
+    int64_t knob[DGE_TUNE_COUNT];      // one snapshot of the tuning knobs for the whole launch
+    for (int k = 0; k < DGE_TUNE_COUNT; k++) knob[k] = g_dge_tuning[k];
+
     TrainParams p;
     p.sen = m->d_sen; p.len = m->d_len; p.wb = m->d_wb;
     p.syn0 = m->d_syn0; p.syn1neg = m->d_syn1neg; p.exp_table = m->d_exp;
     p.ctab = m->d_ctab;
     p.run_base = m->d_run_base; p.run_row = m->d_run_row; p.exc_slot = m->d_exc_slot; p.exc_row = m->d_exc_row;
-    p.n_runs = g_dge_tuning[DGE_TUNE_TABLE_RUNS] == 0 ? 0 : m->n_runs; p.n_exc = m->n_exc; p.T_inv = 1.0 / (double)std::max<int64_t>(m->T, 1);
+    p.n_runs = knob[DGE_TUNE_TABLE_RUNS] == 0 ? 0 : m->n_runs; p.n_exc = m->n_exc; p.T_inv = 1.0 / (double)std::max<int64_t>(m->T, 1);
     p.n_rows = n_rows; p.L = L; p.W = m->cfg.window; p.K = m->cfg.negative; p.stride = m->stride;
     p.V = m->V; p.T = m->T; p.seed = m->cfg.seed;
     p.T_magic = ~0ull / (uint64_t)std::max<int64_t>(m->T, 1); p.W_magic = ~0ull / (uint64_t)std::max(m->cfg.window, 1);
     p.gidx_base = (int64_t)epoch * total_walks + walk_index_base;
-    p.words_done_base = (int64_t)epoch * m->total_words + words_before;
-    p.all_words = (int64_t)std::max(m->cfg.epochs, 1) * m->total_words;
+    p.words_done_base = (int64_t)epoch * m->stats.total_words + words_before;
+    p.all_words = (int64_t)std::max(m->cfg.epochs, 1) * m->stats.total_words;
     p.words_scale = words_scale;
     p.alpha0 = m->cfg.alpha; p.min_alpha = m->cfg.min_alpha;
     p.D = m->D;
     p.counters = m->d_counters;
-    p.next_walk = nullptr; p.wd_ticks = 0;
     p.locks = m->d_locks;
     p.syn1 = m->d_syn1; p.hs_off = m->d_hs_off; p.hs_points = m->d_hs_points; p.hs_codes = m->d_hs_codes;
-    p.hs_hot0 = 0x7fffffff; p.hs_n_hot = 0; p.hs_drain = 1; p.hot_rows = 0; p.hs_cold = 0; p.hs_wave = 0;
-    p.hs_rep0 = 0x7fffffff; p.hs_rep_n = 0; for (int k = 0; k < HS_REP; k++) p.hs_rep_thr[k] = 0x7fffffff;
-    p.part_n = m->part_n; p.part_ctx = m->part_ctx; p.part_tgt = m->part_tgt; p.syn0_free = 0; p.acc_rows = 0; p.acc_drain = 16;
+    p.part_n = m->part_n; p.part_ctx = m->part_ctx; p.part_tgt = m->part_tgt;
     p.N_magic = 0xFFFFFFFFu / (uint32_t)std::max(m->part_n, 1);
     p.big_seg_shift = 0;
     p.filler_row = (int32_t)(0xFFFFFFF0u / ((uint32_t)m->stride * 4u)) - 1;      // offset + the largest in-row displacement stays below 2^32
-    if (g_dge_tuning[DGE_TUNE_SEGMENT_SHIFT] >= 0) p.big_seg_shift = (int32_t)g_dge_tuning[DGE_TUNE_SEGMENT_SHIFT];   // tests: several segments on a small table
-    const bool part = m->part_n > 1;
-    const bool hs = m->cfg.use_hs != 0;
+    if (knob[DGE_TUNE_SEGMENT_SHIFT] >= 0) p.big_seg_shift = (int32_t)knob[DGE_TUNE_SEGMENT_SHIFT];   // tests: several segments on a small table
 
-    // auto: where the Hogwild kernels are bound by contention on a FLAT vocabulary — one too small for row locks (they fall back to
-    // atomics: cfg2), a block of a schedule of 3 and more ranks (V/N live rows per table) — the owner-computes schedule is the faster
-    // one at equal link-prediction AUC (one block of 8 ranks 5.7e8 vs 4.6e8 edges/s, a 100 k-row vocabulary at D = 128 6.8e8 vs 4.2e8:
-    // profiles/r02_quality_sorted.txt).  A skewed vocabulary stays with the mixed policy 7: a synchronous mini-batch hands a hot row
-    // thousands of terms at once with no feedback between them, and the embedding diverges (dge_sorted_batch_items).
-    bool sorted_auto = false;
-    if (m->cfg.update_policy == 0 && m->cfg.workers == 0 && !hs && (uint64_t)m->V * (uint64_t)m->stride * 4ull < 0xFFFFFFFFull) {
-        const bool locks_work = auto_policy(m, hs) != 2;                                            // -> commit locks, all rows (5) or the tail (7)
-        if (part) sorted_auto = m->part_n >= 2 && dge_sorted_batch_items(m, m->part_n) > 0;         // (per rank on cfg3, owner-computes vs locks, round 3 with the items made once per batch: N = 2 7.5e8 vs 7.2e8, N = 4 7.8e8 vs 7.4e8, N = 8 7.5e8 vs 4.8e8)
-        else sorted_auto = !locks_work && dge_sorted_batch_items(m, 1) > 0;                         // (what used to fall back to atomics)
-    }
-    const bool allow_unsafe = g_dge_tuning[DGE_TUNE_ALLOW_UNSAFE] > 0;
-    const double launch_pairs = (double)n_rows * dge_expected_pairs_per_walk(L, m->cfg.window) / ((double)m->part_n * (double)m->part_n);      // (full-length walks: an upper estimate)
-    if ((m->cfg.update_policy == 8 && m->cfg.workers != 1) || sorted_auto) {
-        // owner-computes schedule (sgns_sorted.hip): items sorted by row, no locks, no atomics, deterministic
-        if (hs) DGE_FAIL(DGE_ERR_ARG, "update_policy 8 does not carry the hierarchical-softmax term");
-        // FORCED on a vocabulary the rule would not pick it for (dge_sorted_batch_items == 0): a small vocabulary is merely slow, but on a skewed one the busiest row takes
-        // thousands of terms of one synchronous mini-batch with no feedback between them and the tables go to NaN within an epoch (profiles/r02_quality_zipf_sorted_diverges.txt;
-        // rank^-1 over 50 000 words: 9 % of a million-item mini-batch on one row).  Refused instead (round 5; a mini-batch size set by hand — DGE_TUNE_SORTED_WALKS — is the caller's business).
-        if (!sorted_auto && !allow_unsafe && g_dge_tuning[DGE_TUNE_SORTED_WALKS] <= 0 && dge_sorted_batch_items(m, m->part_n) == 0) {
-            const double hottest = std::min(1.0, m->row_share_max * (double)std::max(m->part_n, 1));
-            const double mb_items = std::min((double)(1 << 20), launch_pairs * (double)(m->cfg.negative + 1));
-            if (hottest * mb_items > 8192.0)
-                DGE_FAIL(DGE_ERR_ARG, "update_policy 8 (owner-computes) on this vocabulary: its busiest row holds %.2g of the terms, ~%.0f of one synchronous mini-batch "
-                         "with no feedback between them (the schedule keeps that below 4096; far beyond, the tables diverge): use update_policy 0 (auto), 2 or 7", hottest, hottest * mb_items);
-        }
-        EventPair ev;
-        if ((rc = timing_begin(m, ev, 0))) return rc;
-        if ((rc = timing_end(m, ev, dge_sorted_train(m, p)))) return rc;
-        m->launches++;
-        m->last_policy = 8; m->last_workers = 0; m->last_hot_rows = 0;
-        m->last_kernel = part ? "k_sorted_phase (owner-computes, one block of the multi-GPU schedule: k_block_emit + 2 item sorts + 2 phases)" : "k_sorted_phase (owner-computes: k_sorted_emit + 2 item sorts + 2 phases)";
-        return DGE_OK;
-    }
-    int64_t workers;
-    if (m->cfg.workers == 0) {
-        // fill the device: 4 blocks of 16 workers per CU, but never more concurrent walks than half the vocabulary
-        // (Hogwild's premise is sparse collisions: measured, a 2.3k-row table keeps 0.99 cosine to the in-order
-        // result up to ~1k workers and loses it beyond; the reference ran 8 workers on <= 6.4k rows)
-        const int auto_pol = m->cfg.update_policy == 0 ? auto_policy(m, hs) : 0;
-        const bool auto_locked = auto_pol == 5, auto_mixed = auto_pol == 7;
-        const int blocks_per_cu = (m->cfg.update_policy == 5 || m->cfg.update_policy == 6 || m->cfg.update_policy == 7 || auto_locked || auto_mixed) ? ((m->cfg.update_policy == 7 || auto_mixed) ? (m->stride <= 128 ? DGE_HOTMIX_WAVES : 2) : (m->stride == 64 ? 4 : DGE_LOCKED_WAVES)) : 4;   // (rows of one chunk leave room for a 4th wave per SIMD in the lock kernel; a 5th under atomics gains nothing: cfg2 7.6e8 either way)   // what the kernel's VGPR budget keeps resident
-        workers = (int64_t)m->n_cus * blocks_per_cu * 16;
-        // Round 5 (scripts/small_vocab_workers.py, profiles/r05_small_vocab_workers*.txt): measured again on the reference's own tract size — 6 408 rows, D = 20, a graph with
-        // community structure — with what matters downstream instead of the cosine to the in-order result: held-out link AUC and loss.  Negative sampling: AUC 0.9295 at
-        // 3 204 ... 16 384 workers alike (sequential oracle 0.9294, its 8 Hogwild threads 0.9274), loss 0.6928 -> 0.6942 at 9 612 (sequential 0.6924, 8 threads 0.7111);
-        // with the hierarchical softmax 9 612 workers keep AUC 0.9213 / loss 0.737 (8 CPU threads: 0.9207 / 0.741) and 12 816 lose it (0.915 / 0.81).  So from 4 096
-        // rows on the cap is 1.5 workers a row: cfg1 7.2e8 -> 1.28e9 edges/s, with the tree term 1.64e8 -> 5.1e8.  Below 4 096 rows the round-1 cap stays.
-        // The small-row kernel (rows of 17 .. 32 floats without the tree term: k_sgns_train_small) reaches its request-rate ceiling with ONE worker a row — 1.41e9 edges/s
-        // at 6 408, 9 612 and 16 384 workers alike, loss 0.6935 / 0.6943 / 0.716 (profiles/r05_small_row_kernel.txt) — so it runs one a row.
-        const bool small_kernel = !hs && m->part_n <= 1 && m->cfg.dim > 16 && m->cfg.dim <= 32 && m->stride == 64 && g_dge_tuning[DGE_TUNE_SMALL_ROWS] != 0;
-        workers = std::min(workers, std::max<int64_t>(64, m->V >= 4096 ? (small_kernel ? m->V : m->V * 3 / 2) : m->V / 2));
-        // ... nor so many that ONE row has dozens of its updates in flight at once: every one of them is computed from the same stale row, and their
-        // sum — along the direction the contexts share — is a gradient step M times too long.  A vocabulary whose busiest row takes 9 % of the tokens
-        // (Zipf(1) over 50 000 words: text without sub-sampling, not a flow graph) went to NaN within one launch of 16 384 workers
-        // (scripts/policy_sweep.py, round 4); cfg3 with Zipf destinations and cfg5 keep 34 and 18 in flight and train to the atomics-free AUC.
-        // Round 5 swept that bound on a graph WITH structure whose busiest vertex holds 2.8 % of the tokens (scripts/hot_row_inflight.py, profiles/r05_hot_row_inflight.txt;
-        // sequential oracle AUC 0.7472 / loss 1.988, its 8 Hogwild threads 0.7346 / 2.044): 24 / 48 / 96 in flight 0.7469 / 0.7464 / 0.7454 at loss 1.97, 192: 0.7402 / 2.00,
-        // 384: 0.7333 / 2.08 — and the SPEED peaks at 96 (3.2e8 edges/s; 2.7e8 at 48, 3.0e8 at 192: beyond, the busiest rows' atomics queue at the memory side).  So: 96.
-        // Copies of the hottest rows (what k_sgns_train_hsw does for the Huffman root) would lift the atomic wall, not this one: staleness caps the in-flight count first.
-        workers = std::min(workers, std::max<int64_t>(64, (int64_t)(96.0 / std::max(m->row_share_max, 1e-12))));
-        workers = std::min(workers, (n_rows + 15) / 16 * 16);
-    } else workers = m->cfg.workers;
-    if (m->cfg.workers == 0 && g_dge_tuning[DGE_TUNE_WORKERS] > 0) workers = std::min<int64_t>(g_dge_tuning[DGE_TUNE_WORKERS], (n_rows + 15) / 16 * 16);     // ablation knob
-    p.n_workers = workers;
-    // update policy (see Policy<>, k_sgns_train_locked and dge_train_config.update_policy)
-    int pol = m->cfg.update_policy;
-    if (pol == 0) {
-        // auto.  The commit-lock kernel is the fast one while lock attempts rarely fail: a try fails when the row is among
-        // the ~5 rows another worker holds, i.e. with probability ~ workers * 5 * sum_i q_i^2 (q = unigram^0.75 sampling
-        // probabilities).  cfg3 (uniform-ish, 1M rows, 12k workers): 0.07 -> locked, 8.9e8 edges/s.  A Zipf-popular
-        // vocabulary (cfg5) gives >> 1: the same kernel spins on its hot rows (measured 5e5 edges/s) while memory-side
-        // atomics are indifferent to the skew (5.9e7 = their byte rate) -> atomics.
-        // In between (a skewed head over a long tail — cfg5, and what real trip data looks like) the head rows alone are
-        // taken out of the lock protocol: policy 7.  (auto_policy above)
-        pol = workers == 1 ? 100 : auto_policy(m, hs);
-    }
-    // FORCED commit locks (5 / 6) on a vocabulary with a busy row: a pair holds its context row's lock for its whole duration, so the pairs of row i run one behind
-    // the other — p_i x pairs of them while the launch as a whole should last pairs / W pair-times — and the waiting workers keep hammering that lock word: measured
-    // (profiles/r04_policy_sweep.txt) 60x slower at W x p = 6 (rank^-0.5 over 1e6 rows), "minutes" on rank^-1.  Auto moves such rows to the atomics side (7); a forced 5 / 6 is
-    // refused beyond W x p = 2 (the community graph's W x p = 1.2 runs 1.8x slower: still a choice).  Same rule inside a block, whose rows take n times their share.
-    if ((m->cfg.update_policy == 5 || m->cfg.update_policy == 6) && workers > 1 && !allow_unsafe) {
-        const double chain = (double)workers * m->row_share_max * (double)std::max(m->part_n, 1);
-        // (and only where that chain is long: a contended hand-over of a row lock takes ~100 us — rank^-0.5 over 1e6 rows: 38 000 pairs of the busiest row in 5 s —, so a
-        //  launch whose busiest row has fewer than 50 000 pairs is merely slow for seconds: the edge-case tests on 1- and 3-row vocabularies)
-        if (chain > 2.0 && m->row_share_max * (double)std::max(m->part_n, 1) * launch_pairs > 5e4)
-            DGE_FAIL(DGE_ERR_ARG, "update_policy %d (commit locks on every row) on this vocabulary: its busiest row holds %.2g of the tokens, %lld workers x that share = %.1f pairs "
-                     "queue behind ONE row lock at any time and the launch would be that row's chain (bound 2): use update_policy 0 (auto) or 7 (the head by atomics)",
-                     m->cfg.update_policy, m->row_share_max, (long long)workers, chain);
-    }
-    if (pol == 7) {
-        const double fail_all = (double)((int64_t)m->n_cus * 3 * 16) * 5.0 * m->neg_collision;
-        // a flat vocabulary with a few busy rows: only those; a skewed one: the whole head
-        p.hot_rows = (int32_t)std::min<int64_t>((m->cfg.update_policy == 0 && fail_all < 0.25) ? m->hot_rows_serial : std::max(m->hot_rows_auto, m->hot_rows_serial), m->V);
-        if (g_dge_tuning[DGE_TUNE_HOT_ROWS] >= 0) p.hot_rows = (int32_t)std::min<int64_t>(g_dge_tuning[DGE_TUNE_HOT_ROWS], m->V);     // ablation knob
-        // off unless asked for: measured on cfg3_zipf it buys 2-4 % and shifts the trained scores (profiles/r03_zipf_ablation.txt)
-        p.acc_rows = g_dge_tuning[DGE_TUNE_ACC_ROWS] > 0 ? (int32_t)std::min<int64_t>(g_dge_tuning[DGE_TUNE_ACC_ROWS], 64) : 0;       // (the kernel caps it at what its LDS holds)
-        if (g_dge_tuning[DGE_TUNE_ACC_DRAIN] > 0) p.acc_drain = (int32_t)std::min<int64_t>(g_dge_tuning[DGE_TUNE_ACC_DRAIN], 1 << 20);
-    }
-    if (pol == 100 || (workers == 1 && pol != 5 && pol != 6 && pol != 7 && pol != 2 && pol != 1)) pol = 0;   // in-order: plain accesses
-    if (pol == 3 || pol == 8) pol = 0;          // (policy 8 with one worker: the in-order schedule)
-    if (part && L > 64) DGE_FAIL(DGE_ERR_ARG, "the block schedule keeps a walk's tokens in registers: walks of up to 64 tokens, not %d", L);
-    if (part) {
-        // One block of the multi-GPU schedule: the live rows are V/part_n per table, so lock attempts collide part_n times
-        // as often as on the whole table (measured on cfg3 with bench.py --sim-ranks, profiles/r01_block_schedule_sim.txt).
-        p.hot_rows = 0;
-        // A skewed vocabulary keeps the head / tail split inside a block (round 4; until then such a block ran with float atomics on every row): the
-        // block's own head — block_head, the one-GPU rule with the block's collision rate — by atomics through the workgroup's atomics wave, the tail
-        // under the commit locks.  Two resident workgroups of 12 workers a compute unit (k_sgns_train_locked<HOTMIX, PART>).
-        const int64_t w_mixed = (int64_t)m->n_cus * 2 * 12;
-        const int64_t head_b = (m->cfg.update_policy == 0 || m->cfg.update_policy == 7) && workers > 1 && m->V / m->part_n >= 32768 ? block_head(m, m->part_n, w_mixed) : 0;
-        const int64_t head_knob = g_dge_tuning[DGE_TUNE_HOT_ROWS];
-        // with the hierarchical softmax (round 4): the in-order schedule or memory-side atomics, as on one GPU — inner-node rows are split by node % n like the
-        // vocabulary rows, every block visits every centre for the path nodes of its target partition (k_sgns_train<.., HS, PART>)
-        if (hs) pol = pol == 0 ? 20 : 22;
-        else if (pol == 0) pol = 20;
-        else if (m->cfg.update_policy == 0) {
-            const double per_worker = 5.0 * m->neg_collision * (double)m->part_n;
-            const int64_t w_max = per_worker > 0 ? (int64_t)(0.37 / per_worker) / 256 * 256 : workers;
-            if (m->V >= 262144 && w_max >= workers) pol = 25;                  // cfg3: up to 4 ranks
-            else if (m->V >= 262144 && w_max >= 4096) {
-                // more ranks: also take the pair's syn0 row out of the lock protocol (it is held for the whole pair: at
-                // 8 ranks 10 % of the live syn0 rows are locked at any time and every tenth pair is aborted and retried);
-                // its update goes out as atomics behind the last unlock.  8 192 workers (2 resident blocks a CU): 4.6e8 edges/s
-                // per rank against 3.7e8 with the syn0 locks and 3.6e8 with atomics everywhere.
-                pol = 27; p.hot_rows = 0; p.syn0_free = 1;
-                if (m->cfg.workers == 0) { workers = std::min<int64_t>(workers, (int64_t)m->n_cus * 2 * 16); p.n_workers = workers; }
-            } else if (m->V / m->part_n >= 32768 && head_b <= m->V / 4) {
-                // a skewed vocabulary (cfg5, cfg3 with Zipf destinations): the block's head by atomics, its tail under the locks
-                pol = 27; p.hot_rows = (int32_t)head_b; p.syn0_free = 0;
-                if (m->cfg.workers == 0) { workers = std::min<int64_t>(workers, (int64_t)m->n_cus * 2 * 16); p.n_workers = workers; }
-            } else pol = 22;
-        }
-        else if (pol == 2) pol = 22;
-        else if (pol == 5) pol = 25;
-        else if (pol == 7) { pol = 27; p.hot_rows = (int32_t)head_b; p.syn0_free = 1; }      // locks on syn1neg's tail only (the pair's syn0 row by atomics)
-        else DGE_FAIL(DGE_ERR_ARG, "the block schedule runs under update_policy 0 (auto), 2, 3, 5 or 7, not %d", m->cfg.update_policy);
-        if (pol == 27) {
-            if (head_knob >= 0) p.hot_rows = (int32_t)std::min<int64_t>(head_knob, m->V);                                       // ablation knobs
-            if (g_dge_tuning[DGE_TUNE_BLOCK_SYN0_FREE] >= 0) p.syn0_free = g_dge_tuning[DGE_TUNE_BLOCK_SYN0_FREE] > 0 ? 1 : 0;
-            // the partition's hottest rows of BOTH tables add up in the atomics wave's LDS accumulators (lk_atomics_wave, LkAcc): in a block one row's atomics are the
-            // longest chain of the launch
-            // longest chain of the launch (cfg3_zipf at 8 ranks: 22.6 -> 15.2 ms a block).  Updates a flush: what keeps a row's parked updates — at most one flush short
-            // in every workgroup — under 2 048, half of what the owner-computes schedule lets a row take from one stale value (dge_sorted_batch_items); measured on the
-            // cfg3-sized Zipf graph at 8 ranks with 512 workgroups: 4 a flush AUC 0.826 / loss 1.280 (banks off 0.817 / 1.285), 8 a flush 0.825 / 1.296, 16 a flush
-            // diverges (profiles/r05_blocks_acc_quality_zipf.txt).  (the kernel caps the rows at what its LDS holds: 16 a bank, 8 from 129 floats a row on)
-            // (the flush period is set below, once the launch's workgroups are known)
-            // ... where that chain is long against the block: the partition's busiest row takes part_n x max(its share of the contexts, K x its share of the negative
-            // draws) of the block's pairs, ~78 ns each, against ~3 TB/s of row traffic for a pair.  Where it is short the banks buy nothing and cost a little: the
-            // community graph with a Zipf fifth (chain a quarter of the block) loses 0.0034 AUC / 2.3 % of the loss with them and gains 1 % (tests/test_gpu_blocks_scale.py).
-            const double top = (double)m->h_counts[0];
-            const double chain_share = (double)m->part_n * std::max(top / (double)std::max<int64_t>(m->total_words, 1), (double)m->cfg.negative * pow(top, 0.75) / m->neg_norm);
-            const double pair_s = 8.0 * (double)m->stride * (double)(m->cfg.negative + 2) / 3e12;
-            // (scripts/block_head_rule.py: that ratio is 1.08 on cfg3_zipf — banks: +50 % and a better AUC —, 0.55 on cfg5 — +10 % —, 0.32 on the community graph: on from 0.4)
-            const int32_t auto_rows = chain_share * 78e-9 > 0.4 * pair_s ? 16 : 0;
-            p.acc_rows = g_dge_tuning[DGE_TUNE_ACC_ROWS] >= 0 ? (int32_t)std::min<int64_t>(g_dge_tuning[DGE_TUNE_ACC_ROWS], 64) : auto_rows;
-        }
-    }
-    size_t shmem = 0;
-    if (hs) {
-        pol = pol == 0 ? 10 : (pol == 20 ? 30 : (pol == 22 ? 32 : 12));      // dge_model_create admitted policies 0/2/3 only; 30 / 32: one block of the multi-GPU schedule
-        if ((pol == 12 || pol == 32) && workers > 1) {         // (one worker: the sequential schedule — no LDS accumulators, no cold class, every node by atomics it waits for)
-            // LDS accumulators for the inner nodes nearest the root: 30 KB a block (3 blocks a CU stay resident beside the atomics wave's boxes)
-            const int64_t row_b = (int64_t)m->stride * 4 + 4;
-            p.hs_n_hot = (int32_t)std::min<int64_t>(std::max<int64_t>(m->V - 1, 0), 30720 / row_b);
-            p.hs_hot0 = (int32_t)(std::max<int64_t>(m->V - 1, 0) - p.hs_n_hot);
-            p.hs_drain = 64;
-            if (g_dge_tuning[DGE_TUNE_HS_DRAIN] >= 1) p.hs_drain = (int32_t)g_dge_tuning[DGE_TUNE_HS_DRAIN];      // ablation knob
-            // the cold end of the tree: plain read-modify-write instead of atomics (see k_sgns_train)
-            p.hs_cold = (int32_t)std::min<int64_t>(m->hs_cold_auto, p.hs_hot0);
-            if (g_dge_tuning[DGE_TUNE_HS_COLD] >= 0) p.hs_cold = (int32_t)std::min<int64_t>(g_dge_tuning[DGE_TUNE_HS_COLD], p.hs_hot0);
-            shmem = (size_t)p.hs_n_hot * (size_t)row_b;
-        }
-    }
-    unsigned threads = workers == 1 ? 64u : 256u;
-    unsigned blocks = (unsigned)((workers * 16 + threads - 1) / threads);
-    const bool big_tables = (uint64_t)m->V * (uint64_t)m->stride * 4ull >= 0xFFFFFFFFull || g_dge_tuning[DGE_TUNE_FORCE_SEGMENTS] > 0;
-    // (from 65 536 vocabulary rows on, like the atomics wave below: on the reference's own 6 408-row tract vocabulary the walks in flight are capped by the
-    //  vocabulary — 801 waves — and the pair-by-pair kernel's 3 204 groups are faster: 1.64e8 against 1.22e8 edges/s; DGE_TUNE_HS_CENTRE = 1 forces it)
-    if (pol == 12 && workers > 1 && m->stride <= 256 && L <= 64 && !big_tables &&
-        (g_dge_tuning[DGE_TUNE_HS_CENTRE] > 0 || (g_dge_tuning[DGE_TUNE_HS_CENTRE] < 0 && m->V >= 65536))) {
-        // Hierarchical softmax, a wave per centre (k_sgns_train_hsw, round 4): the centre's path nodes stay in the registers of a wave's four groups for all
-        // its contexts and their gathered updates leave once per centre.  `workers` = walks in flight = waves that train: two resident workgroups of three
-        // such waves (and one atomics wave) a compute unit; never more than an eighth of the vocabulary (a wave works on four context rows at a time).
-        pol = 13;
-        int nw = 3;
-        // ... and where the negative-sampling kernels would run under commit locks (a flat vocabulary: auto_policy 5), the pair's negatives and the centre's
-        // gathered syn1neg update go under the rows' locks instead of out as atomics (k_sgns_train_hsw<.., NLOCK>) — in ONE workgroup of seven training waves a
-        // compute unit, which share their LDS accumulators (DGE_TUNE_HS_CENTRE: 1 keeps atomics, 2 = locks in workgroups of three waves, 3 = of seven)
-        const int64_t centre_knob = g_dge_tuning[DGE_TUNE_HS_CENTRE];
-        // ... and on a SKEWED vocabulary whose head the mixed policy 7 would take out of the lock protocol (round 5): the same kernel with that head by atomics, the tail's
-        // negatives under locks (p.hot_rows; DGE_TUNE_HOT_ROWS sets it by hand)
-        const bool mixed_ok = m->V >= 131072 && (int64_t)(48.0 / std::max(m->row_share_max, 1e-12)) >= 4096 && std::max(m->hot_rows_auto, m->hot_rows_serial) <= m->V / 4;
-        if (centre_knob == 2 || centre_knob == 3 || (centre_knob < 0 && m->cfg.update_policy == 0 && (syn1neg_locks_work(m) || mixed_ok))) {
-            const bool mixed = !syn1neg_locks_work(m) && mixed_ok && centre_knob < 0;
-            pol = (centre_knob == 2 || m->stride > 128 || mixed) ? 14 : 15;      // (rows of more than 128 floats: three-wave workgroups only — seven waves' message boxes do not fit the LDS; a head by atomics: three waves to an atomics wave, not seven)
-            if (pol == 15) nw = 7;
-            if (!syn1neg_locks_work(m) && mixed_ok) p.hot_rows = (int32_t)std::min<int64_t>(std::max(m->hot_rows_auto, m->hot_rows_serial), m->V);
-            if (g_dge_tuning[DGE_TUNE_HOT_ROWS] >= 0) p.hot_rows = (int32_t)std::min<int64_t>(g_dge_tuning[DGE_TUNE_HOT_ROWS], m->V);
-        }
-        if (m->cfg.workers == 0 && !(g_dge_tuning[DGE_TUNE_WORKERS] > 0))
-            workers = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((int64_t)m->n_cus * (nw == 3 ? (m->stride <= 128 ? 6 : 3) : 7), std::max<int64_t>(1, m->V / 8)), std::max<int64_t>(16, (int64_t)(12.0 / std::max(m->row_share_max, 1e-12)))));      // (wide rows: one three-wave workgroup a compute unit)
-        workers = std::max<int64_t>(1, std::min<int64_t>(workers, n_rows));
-        p.n_workers = workers;
-        blocks = (unsigned)((workers + nw - 1) / nw);
-        threads = (unsigned)(nw + 1) * 64u;
-        // an LDS accumulator now takes one addition per CENTRE (16 pairs' worth on cfg3): drained every 4 additions instead of every 64 — every 8 where seven
-        // waves share it (the same number of additions parked device-wide: workgroups x drain)
-        p.hs_drain = g_dge_tuning[DGE_TUNE_HS_DRAIN] >= 1 ? (int32_t)g_dge_tuning[DGE_TUNE_HS_DRAIN] : (nw == 3 ? 4 : 8);
-        // Measured on cfg3 and the cfg3-sized community graph (profiles/r04_hs_waves7.txt; three waves, drain 4: 3.3e8 edges/s, AUC 0.9534): seven waves with 15 KB of
-        // accumulators (the 29 nodes next to the root) and a drain every 8 additions 3.6e8 at AUC 0.9533; with 30 KB 3.64e8 / 0.9526, with 60 KB 3.7e8 / 0.9519 — every
-        // accumulator is a row whose readers lag workgroups x drain / 2 updates behind, so fewer of them and shared by more waves is the better trade (three waves at
-        // drain 8: 3.63e8 / 0.9518).
-        // The busiest inner nodes in copies instead of LDS accumulators (k_sgns_train_hsw, HS_REP): the default; DGE_TUNE_HS_HOT_KB > 0 brings the accumulators back
-        // (that many KB of them; the drain period then matters again) for comparison.
-        const int64_t hot_kb_knob = g_dge_tuning[DGE_TUNE_HS_HOT_KB];
-        if (hot_kb_knob <= 0 && m->hs_rep_auto > 0 && m->V > 1) {
-            const int64_t n_rep = std::min<int64_t>(std::min<int64_t>(m->hs_rep_auto, HS_REP_NODES), m->V - 1);
-            p.hs_rep_n = (int32_t)n_rep; p.hs_rep0 = (int32_t)(m->V - 1 - n_rep);      // (the copies: rows V .. of syn1, zero between launches: k_hs_rep_fold)
-            // copies per node: ceil(share of the paths x F), F = HS_REP (the root: HS_REP = 16 copies, a node on half the paths 8, ...; DGE_TUNE_HS_COPIES = F for comparison: 4 = the root four copies, ...)
-            { const int64_t f_knob = g_dge_tuning[DGE_TUNE_HS_COPIES];
-              const int F = (int)std::min<int64_t>(HS_REP, f_knob >= 1 ? f_knob : (int64_t)HS_REP);
-              for (int k = 1; k < HS_REP; k++) p.hs_rep_thr[k] = k < F ? std::max(m->hs_rep_thr32[std::min(31, k * 32 / F)], p.hs_rep0) : 0x7fffffff;      // more than k copies: share x F > k
-              p.hs_rep_thr[0] = 0; }
-            p.hs_n_hot = 0; p.hs_hot0 = (int32_t)std::max<int64_t>(m->V - 1, 0); shmem = 0;
-            { const int64_t cold_knob = g_dge_tuning[DGE_TUNE_HS_COLD]; p.hs_cold = (int32_t)std::min<int64_t>(cold_knob >= 0 ? cold_knob : (int64_t)m->hs_cold_auto, p.hs_rep0); }
-        } else {                   // LDS accumulators (DGE_TUNE_HS_HOT_KB > 0; or a tree without a busy node): seven waves, one workgroup a compute unit — up to 100 KB; three waves, two workgroups — up to 30 KB each
-            const int64_t row_b = (int64_t)m->stride * 4 + 4;
-            const int64_t hot_kb = g_dge_tuning[DGE_TUNE_HS_HOT_KB];
-            p.hs_n_hot = (int32_t)std::min<int64_t>(std::max<int64_t>(m->V - 1, 0), (hot_kb > 0 ? std::min<int64_t>(hot_kb, nw == 7 ? 100 : 30) * 1024 : (nw == 7 ? 15360 : 30720)) / row_b);
-            p.hs_hot0 = (int32_t)(std::max<int64_t>(m->V - 1, 0) - p.hs_n_hot);
-            { const int64_t cold_knob = g_dge_tuning[DGE_TUNE_HS_COLD]; p.hs_cold = (int32_t)std::min<int64_t>(cold_knob >= 0 ? cold_knob : (int64_t)m->hs_cold_auto, p.hs_hot0); }
-            shmem = (size_t)p.hs_n_hot * (size_t)row_b;
-        }
-    }
-    // (not on small vocabularies, where the worker count is capped at half the rows and every pair is a latency chain: the reference's own
-    //  801 x 8 tract graph with hierarchical softmax runs 407 ms per 6.5e7 pairs on its 3 204 workers, 552 ms on 2 400 workers and a wave)
-    if ((pol == 12 || pol == 32) && workers > 1 && (g_dge_tuning[DGE_TUNE_HS_WAVE] > 0 || (g_dge_tuning[DGE_TUNE_HS_WAVE] < 0 && m->V >= 65536))) {
-        // hierarchical softmax under atomics: every workgroup's fourth wave issues the atomics of its 12 workers (k_sgns_train, lk_atomics_wave)
-        p.hs_wave = 1;
-        // (three workgroups a compute unit stay resident next to their LDS accumulators and message boxes: DGE_HS_WAVES)
-        if (m->cfg.workers == 0 && !(g_dge_tuning[DGE_TUNE_WORKERS] > 0)) { workers = std::max<int64_t>(std::min<int64_t>(workers / 16 * 12, (int64_t)m->n_cus * DGE_HS_WAVES * 12), 2); p.n_workers = workers; }
-        blocks = (unsigned)((workers + 11) / 12);
-    }
-    if ((pol == 7 || pol == 27) && workers > 1) {
-        // the mixed kernels keep every workgroup's fourth wave for the head rows' atomics (k_sgns_train_locked): 12 workers a workgroup
-        if (m->cfg.workers == 0 && !(g_dge_tuning[DGE_TUNE_WORKERS] > 0)) { workers = std::max<int64_t>(workers / 16 * 12, 2); p.n_workers = workers; }
-        blocks = (unsigned)((workers + 11) / 12);
-        if (pol == 27) p.acc_drain = g_dge_tuning[DGE_TUNE_ACC_DRAIN] > 0 ? (int32_t)std::min<int64_t>(g_dge_tuning[DGE_TUNE_ACC_DRAIN], 1 << 20)
-                                                                        : (int32_t)std::max<int64_t>(1, std::min<int64_t>(8, 2048 / std::max(blocks, 1u)));
-    }
-
-    // per-segment descriptors (TableView) for tables of 4 GiB and more; DGE_TUNE_FORCE_SEGMENTS selects that code path on small
-    // tables too so that the parity tests can cover it
-    const bool big = (uint64_t)m->V * (uint64_t)m->stride * 4ull >= 0xFFFFFFFFull || g_dge_tuning[DGE_TUNE_FORCE_SEGMENTS] > 0;
-    // Walks handed out by a launch-wide counter wherever several workers run, the order of the walks is free (not the in-order schedule) and
-    // a worker trains enough walks for the hand-out to even anything out.  Measured on one model in one process (scripts/ab_inproc.py): cfg3
-    // 415 against 426 ms per launch, cfg3_zipf 666 against 678, hierarchical softmax 3.24 against 3.28 s, atomics 914 against 925; cfg2 under
-    // atomics (6 walks per worker) 5.6 against 5.4 — there the workers keep their fixed walks.
-    if (workers > 1 && n_rows >= 32 * workers && pol != 0 && !(g_dge_tuning[DGE_TUNE_STATIC_WALKS] > 0)) {
-        p.next_walk = m->d_counters + 2;
-        DGE_HIP(hipMemsetAsync(p.next_walk, 0, sizeof(unsigned long long), st));
-    }
-    // A launch whose length is one busy row's chain of pairs — forced policy 5 or 6 on a vocabulary with such a row — is bound by a pair's latency, not by
-    // requests, and the 11 dependent LDS reads of the table's run form are slower than a table look-up that hits the caches (15.4-15.9 s against 12.8 s
-    // on the community graph of scripts/quality_scale.py): there the table stays.
-    if (m->hot_rows_serial > 0 && workers > 1) p.n_runs = 0;
-    // The lock kernels' watchdog: a worker that is still waiting for a row lock when the launch has run 100x longer than its bytes take at the roofline (+ 5 s) gives up,
-    // counts itself in counters[3] and leaves; dge_model_stats then reports DGE_ERR_STATE.  Checked on the waiting paths only (100 MHz s_memrealtime ticks).
-    {
-        const double bytes = launch_pairs * 8.0 * (double)m->stride * (double)(m->cfg.negative + 2);
-        double budget_s = 5.0 + 100.0 * bytes / 8e12;
-        if (g_dge_tuning[DGE_TUNE_WATCHDOG_MS] > 0) budget_s = (double)g_dge_tuning[DGE_TUNE_WATCHDOG_MS] * 1e-3;
-        // only where the commit locks on every row were FORCED (update_policy 5 / 6): what auto picks them for cannot make them wait, and the watchdog is its own kernel
-        // instantiation so that the headline launch does not pay for it (sgns_kernels.h: WDOG)
-        const bool forced_locks = m->cfg.update_policy == 5 || m->cfg.update_policy == 6;
-        p.wd_ticks = (!forced_locks || g_dge_tuning[DGE_TUNE_WATCHDOG_MS] == 0) ? 0ull : (uint64_t)(budget_s * 1e8);
-    }
+    // the schedule (sgns_plan.h) and what it sets
+    TrainPlan plan;
+    if ((rc = plan_train(m->cfg, m->stats, m->h_counts.data(), m->part_n, n_rows, L, knob, m->block_head_memo, &plan))) DGE_FAIL(rc, "%s", plan.error);
+    p.n_workers = plan.workers;
+    p.hot_rows = plan.hot_rows; p.acc_rows = plan.acc_rows; p.acc_drain = plan.acc_drain; p.syn0_free = plan.syn0_free;
+    p.hs_hot0 = plan.hs_hot0; p.hs_n_hot = plan.hs_n_hot; p.hs_drain = plan.hs_drain; p.hs_cold = plan.hs_cold; p.hs_wave = plan.hs_wave;
+    p.hs_rep0 = plan.hs_rep0; p.hs_rep_n = plan.hs_rep_n; for (int k = 0; k < HS_REP; k++) p.hs_rep_thr[k] = plan.hs_rep_thr[k];
+    p.wd_ticks = plan.wd_ticks;
+    if (plan.runs_off) p.n_runs = 0;
+    p.next_walk = plan.walk_counter ? m->d_counters + 2 : nullptr;
+    if (plan.walk_counter) DGE_HIP(hipMemsetAsync(p.next_walk, 0, sizeof(unsigned long long), st));
     // k_sgns_train_hsw's copies of the busiest inner nodes must be zero when the launch starts.  k_hs_rep_fold leaves them so behind every launch; an abandoned launch
     // (an error between the two) would not — so they are cleared here as well (hs_rep_n x 15 rows, < 1 MB)
     if (p.hs_rep_n > 0) DGE_HIP(hipMemsetAsync(m->d_syn1 + (size_t)m->V * m->stride, 0, (size_t)(HS_REP - 1) * (size_t)p.hs_rep_n * (size_t)m->stride * sizeof(float), st));
-    // rows of 17 .. 32 floats under the atomics policy (the reference's own layerSize 20): half a wave a worker, a row = one request each way (k_sgns_train_small)
-    const bool small_rows = pol == 2 && (workers > 1 || g_dge_tuning[DGE_TUNE_SMALL_ROWS] > 0) && m->cfg.dim > 16 && m->cfg.dim <= 32 && m->stride == 64 && L <= 64 && !big && g_dge_tuning[DGE_TUNE_SMALL_ROWS] != 0;
-    if (small_rows) { threads = 256u; blocks = (unsigned)((workers * 32 + 255) / 256); }
+
     EventPair ev;
     if ((rc = timing_begin(m, ev, 0))) return rc;
-    if (small_rows) hipLaunchKernelGGL((k_sgns_train_small<32>), dim3(blocks), dim3(threads), 0, st, p);
+    if (plan.form == TrainForm::Sorted) rc = dge_sorted_train(m, p);
+    else if (plan.form == TrainForm::SmallRows) hipLaunchKernelGGL((k_sgns_train_small<32>), dim3(plan.blocks), dim3(plan.threads), 0, st, p);
     else
     switch (m->stride / 64) {
-        case 1: dge_launch_train_dch1(p, pol, big, blocks, threads, shmem, st); break;
-        case 2: dge_launch_train_dch2(p, pol, big, blocks, threads, shmem, st); break;
-        case 3: dge_launch_train_dch3(p, pol, big, blocks, threads, shmem, st); break;
-        case 4: dge_launch_train_dch4(p, pol, big, blocks, threads, shmem, st); break;
-        case 6: dge_launch_train_dch6(p, pol, big, blocks, threads, shmem, st); break;
-        default: dge_launch_train_dch8(p, pol, big, blocks, threads, shmem, st); break;
+        case 1: dge_launch_train_dch1(p, plan, st); break;
+        case 2: dge_launch_train_dch2(p, plan, st); break;
+        case 3: dge_launch_train_dch3(p, plan, st); break;
+        case 4: dge_launch_train_dch4(p, plan, st); break;
+        case 6: dge_launch_train_dch6(p, plan, st); break;
+        default: dge_launch_train_dch8(p, plan, st); break;
     }
     if (p.hs_rep_n > 0)      // the copies of the busiest inner nodes go back into their rows (and are zero again for the next launch's memset to find nothing)
         hipLaunchKernelGGL(k_hs_rep_fold, dim3((unsigned)p.hs_rep_n), dim3(128), 0, st, m->d_syn1 + (size_t)p.hs_rep0 * m->stride, m->d_syn1 + (size_t)m->V * m->stride, p.hs_rep_n, m->stride);
-    if ((rc = timing_end(m, ev, DGE_OK))) return rc;
+    if ((rc = timing_end(m, ev, rc))) return rc;
     m->launches++;
-    {   // which trainer kernel ran (dge_model_kernel): the bench line names it from here, not from the policy number
-        const int base = pol >= 30 ? pol - 30 : (pol >= 20 ? pol - 20 : (pol >= 10 ? pol - 10 : pol));
-        const bool blk = pol >= 20;
-        std::string k;
-        if (pol == 13) k = "k_sgns_train_hsw<atomics, 3 waves> (hierarchical softmax, a wave per centre)";
-        else if (pol == 14) k = std::string("k_sgns_train_hsw<negatives under commit locks") + (p.hot_rows > 0 ? ", head rows by atomics" : "") + ", 3 waves> (hierarchical softmax, a wave per centre)";
-        else if (pol == 15) k = std::string("k_sgns_train_hsw<negatives under commit locks") + (p.hot_rows > 0 ? ", head rows by atomics" : "") + ", 7 waves> (hierarchical softmax, a wave per centre)";
-        else if (base == 5 || base == 6 || base == 7) k = std::string("k_sgns_train_locked<") + (base == 6 ? "strict" : "relaxed") + (base == 7 ? ", head rows by atomics" : "") + (blk ? ", one block" : "") + ">";
-        else if (small_rows) k = "k_sgns_train_small<atomics, 32 lanes a worker>";
-        else k = std::string("k_sgns_train<") + (base == 2 ? "atomics" : (base == 1 ? "row rmw" : "in-order")) + (hs ? ", hierarchical softmax pair by pair" : "") + (blk ? ", one block" : "") + ">";
-        m->last_kernel = k;
-    }
-    m->last_policy = pol >= 30 ? pol - 30 : (pol >= 20 ? pol - 20 : (pol == 13 ? 2 : (pol == 14 || pol == 15 ? (p.hot_rows > 0 ? 7 : 5) : (pol >= 10 ? pol - 10 : pol)))); m->last_workers = workers; m->last_hot_rows = p.hot_rows;
-    DGE_HIP(hipGetLastError());
+    m->last_plan = plan; m->has_plan = true;
+    if (plan.form != TrainForm::Sorted) DGE_HIP(hipGetLastError());
     return DGE_OK;
 }
 
@@ -1440,7 +1068,7 @@ extern "C" int dge_model_stats(const dge_model* mc, dge_train_stats* out) {
     DGE_HIP(hipMemcpy(c, m->d_counters, sizeof(c), hipMemcpyDeviceToHost));
     out->pairs = (int64_t)c[0]; out->words = (int64_t)c[1];
     out->kernel_ms = m->kernel_ms; out->walk_kernel_ms = m->walk_ms; out->launches = m->launches;
-    if (c[3]) {     // a lock kernel's watchdog ended a launch (train_rows: wd_ticks): reported once, here — the first call that looks at the device after the launch
+    if (c[3]) {     // a lock kernel's watchdog ended a launch (plan_train: wd_ticks): reported once, here — the first call that looks at the device after the launch
         DGE_HIP(hipMemsetAsync(m->d_counters + 3, 0, sizeof(unsigned long long), m->stream));
         DGE_HIP(hipStreamSynchronize(m->stream));
         DGE_FAIL(DGE_ERR_STATE, "a training launch was ended by its watchdog: %llu workers waited for row locks beyond the launch's time budget and left their walks untrained "
@@ -1586,7 +1214,7 @@ extern "C" int dge_model_tune_placement(dge_model* m, const dge_walks* w, int64_
     DGE_HIP(hipMemcpyAsync(counters, m->d_counters, sizeof(counters), hipMemcpyDeviceToHost, st));
     DGE_HIP(hipStreamSynchronize(st));
     const double k_ms = m->kernel_ms, w_ms = m->walk_ms; const int64_t launches = m->launches;
-    const int lp = m->last_policy; const int64_t lw = m->last_workers; const int32_t lh = m->last_hot_rows;
+    const TrainPlan last_plan = m->last_plan; const bool has_plan = m->has_plan;
 
     std::vector<void*> graveyard;
     double best = 0, first = 0;
@@ -1639,7 +1267,7 @@ extern "C" int dge_model_tune_placement(dge_model* m, const dge_walks* w, int64_
     DGE_HIP(hipStreamSynchronize(st));
     int rc2 = drain_events(m);
     m->kernel_ms = k_ms; m->walk_ms = w_ms; m->launches = launches;
-    m->last_policy = lp; m->last_workers = lw; m->last_hot_rows = lh;
+    m->last_plan = last_plan; m->has_plan = has_plan;
     m->seen_gen = 0;                                           // (the next launch derives its rows again)
     if (rc == DGE_OK) rc = rc2;
     if (ms_before) *ms_before = first; if (ms_after) *ms_after = best; if (arrays_moved) *arrays_moved = moved;
@@ -1673,10 +1301,10 @@ extern "C" int dge_model_table_runs(const dge_model* m, int32_t* n_runs, int32_t
 
 extern "C" int dge_model_schedule(const dge_model* m, int32_t* update_policy, int64_t* workers, int32_t* hot_rows) {
     if (!m) DGE_FAIL(DGE_ERR_ARG, "dge_model_schedule: null model");
-    if (m->last_policy < 0) DGE_FAIL(DGE_ERR_STATE, "dge_model_schedule: nothing has been trained yet");
-    if (update_policy) *update_policy = m->last_policy;
-    if (workers) *workers = m->last_workers;
-    if (hot_rows) *hot_rows = m->last_hot_rows;
+    if (!m->has_plan) DGE_FAIL(DGE_ERR_STATE, "dge_model_schedule: nothing has been trained yet");
+    if (update_policy) *update_policy = m->last_plan.reported_policy();
+    if (workers) *workers = m->last_plan.workers;
+    if (hot_rows) *hot_rows = m->last_plan.hot_rows;
     return DGE_OK;
 }
 
@@ -1695,8 +1323,8 @@ extern "C" int dge_model_lock_stats(const dge_model* mc, int64_t* pairs_put_back
 
 extern "C" int dge_model_kernel(const dge_model* m, char* buf, int32_t cap) {
     if (!m || !buf || cap <= 0) DGE_FAIL(DGE_ERR_ARG, "dge_model_kernel: bad argument");
-    if (m->last_policy < 0) DGE_FAIL(DGE_ERR_STATE, "dge_model_kernel: nothing has been trained yet");
-    snprintf(buf, (size_t)cap, "%s", m->last_kernel.c_str());
+    if (!m->has_plan) DGE_FAIL(DGE_ERR_STATE, "dge_model_kernel: nothing has been trained yet");
+    snprintf(buf, (size_t)cap, "%s", m->last_plan.kernel_name().c_str());
     return DGE_OK;
 }
 

@@ -7,22 +7,11 @@
 
 #include "dge_algos.h"
 #include "dge_internal.h"
+#include "sgns_plan.h"      // HS_REP*, DGE_*_WAVES; TrainPlan (launch_train_b)
 
 #define EXP_TABLE_SIZE 1000
 #define MAX_EXP 6
-#define HS_REP 16            /* most copies an inner node has during a launch of k_sgns_train_hsw (the root's) */
-#define HS_REP_NODES 64      /* at most this many inner nodes have copies */
-#define HS_REP_ROWS ((HS_REP - 1) * HS_REP_NODES)      /* spare rows behind syn1 for them */
 #define NEG_BATCH 5
-#ifndef DGE_LOCKED_WAVES
-#define DGE_LOCKED_WAVES 3
-#endif
-#ifndef DGE_HOTMIX_WAVES
-#define DGE_HOTMIX_WAVES 3
-#endif
-#ifndef DGE_HS_WAVES
-#define DGE_HS_WAVES 3
-#endif
 
 // ------------------------------------------------------------------------------------------ trainer
 struct TrainParams {
@@ -1993,57 +1982,65 @@ k_sgns_train_small(TrainParams p) {
     }
 }
 
+// the kernel instantiation of a plan's form and flags (sgns_plan.h; TrainForm::SmallRows and Sorted are launched by sgns.hip)
 template <int DCH, bool BIG>
-static inline void launch_train_b(const TrainParams& p, int pol, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st) {
-    switch (pol) {
-        case 0: hipLaunchKernelGGL((k_sgns_train<DCH, 0, BIG, false, false>), dim3(blocks), dim3(threads), 0, st, p); break;
-        case 1: hipLaunchKernelGGL((k_sgns_train<DCH, 1, BIG, false, false>), dim3(blocks), dim3(threads), 0, st, p); break;
-        case 10: hipLaunchKernelGGL((k_sgns_train<DCH, 0, BIG, true, false>), dim3(blocks), dim3(threads), 0, st, p); break;    // + hierarchical softmax
-        case 12: hipLaunchKernelGGL((k_sgns_train<DCH, 2, BIG, true, false>), dim3(blocks), dim3(threads), shmem, st, p); break;
-        case 13: if constexpr (DCH <= 4 && !BIG) hipLaunchKernelGGL((k_sgns_train_hsw<DCH, false, 3>), dim3(blocks), dim3(threads), shmem, st, p); break;   // hierarchical softmax, a wave per centre
-        case 14:                                                                                                                                             // ... the negatives under commit locks
-            if constexpr (DCH <= 4 && !BIG) {
-                if (p.hot_rows > 0) hipLaunchKernelGGL((k_sgns_train_hsw<DCH, true, 3, true>), dim3(blocks), dim3(threads), shmem, st, p);                   // (a skewed vocabulary: its head by atomics)
-                else hipLaunchKernelGGL((k_sgns_train_hsw<DCH, true, 3>), dim3(blocks), dim3(threads), shmem, st, p);
-            }
+static inline void launch_train_b(const TrainParams& p, const TrainPlan& pl, hipStream_t st) {
+    const dim3 g(pl.blocks), b(pl.threads);
+    switch (pl.form) {
+        case TrainForm::InOrder:
+            if (pl.hs) {      // + hierarchical softmax
+                if (pl.part) hipLaunchKernelGGL((k_sgns_train<DCH, 0, BIG, true, true>), g, b, 0, st, p);
+                else hipLaunchKernelGGL((k_sgns_train<DCH, 0, BIG, true, false>), g, b, 0, st, p);
+            } else if (pl.part) hipLaunchKernelGGL((k_sgns_train<DCH, 0, BIG, false, true>), g, b, 0, st, p);      // block schedule of the multi-GPU path (dge_model_set_partition)
+            else hipLaunchKernelGGL((k_sgns_train<DCH, 0, BIG, false, false>), g, b, 0, st, p);
             break;
-        case 15:                                                                                                                                             // ... seven such waves a workgroup
-            if constexpr (DCH <= 2 && !BIG) {
-                // (the workgroup's 41 KB of static LDS and these up to 60 KB together pass 64 KB: asked for per kernel; an error comes back from the launch)
-                if (p.hot_rows > 0) {
-                    (void)hipFuncSetAttribute((const void*)k_sgns_train_hsw<DCH, true, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                    hipLaunchKernelGGL((k_sgns_train_hsw<DCH, true, 7, true>), dim3(blocks), dim3(threads), shmem, st, p);
-                } else {
-                    (void)hipFuncSetAttribute((const void*)k_sgns_train_hsw<DCH, true, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-                    hipLaunchKernelGGL((k_sgns_train_hsw<DCH, true, 7>), dim3(blocks), dim3(threads), shmem, st, p);
+        case TrainForm::RowRmw: hipLaunchKernelGGL((k_sgns_train<DCH, 1, BIG, false, false>), g, b, 0, st, p); break;
+        case TrainForm::Atomics:
+            if (pl.hs) {
+                if (pl.part) hipLaunchKernelGGL((k_sgns_train<DCH, 2, BIG, true, true>), g, b, pl.shmem, st, p);
+                else hipLaunchKernelGGL((k_sgns_train<DCH, 2, BIG, true, false>), g, b, pl.shmem, st, p);
+            } else if (pl.part) hipLaunchKernelGGL((k_sgns_train<DCH, 2, BIG, false, true>), g, b, 0, st, p);
+            else hipLaunchKernelGGL((k_sgns_train<DCH, 2, BIG, false, false>), g, b, 0, st, p);
+            break;
+        case TrainForm::HsCentre:      // hierarchical softmax, a wave per centre
+            if constexpr (DCH <= 4 && !BIG) {
+                if (!pl.nlock) hipLaunchKernelGGL((k_sgns_train_hsw<DCH, false, 3>), g, b, pl.shmem, st, p);
+                else if (pl.waves == 3) {      // ... the negatives under commit locks
+                    if (pl.head) hipLaunchKernelGGL((k_sgns_train_hsw<DCH, true, 3, true>), g, b, pl.shmem, st, p);      // (a skewed vocabulary: its head by atomics)
+                    else hipLaunchKernelGGL((k_sgns_train_hsw<DCH, true, 3>), g, b, pl.shmem, st, p);
+                } else if constexpr (DCH <= 2) {      // ... seven such waves a workgroup
+                    // (the workgroup's 41 KB of static LDS and these up to 60 KB together pass 64 KB: asked for per kernel; an error comes back from the launch)
+                    if (pl.head) {
+                        (void)hipFuncSetAttribute((const void*)k_sgns_train_hsw<DCH, true, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.shmem);
+                        hipLaunchKernelGGL((k_sgns_train_hsw<DCH, true, 7, true>), g, b, pl.shmem, st, p);
+                    } else {
+                        (void)hipFuncSetAttribute((const void*)k_sgns_train_hsw<DCH, true, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.shmem);
+                        hipLaunchKernelGGL((k_sgns_train_hsw<DCH, true, 7>), g, b, pl.shmem, st, p);
+                    }
                 }
             }
             break;
-        case 5:
-            if (p.wd_ticks) hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, false, true>), dim3(blocks), dim3(threads), 0, st, p);      // (forced: with the watchdog)
-            else hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, false>), dim3(blocks), dim3(threads), 0, st, p);
+        case TrainForm::Locked:
+            if (pl.hotmix) {
+                if (pl.part) hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, true, true>), g, b, 0, st, p);
+                else hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, true, false>), g, b, 0, st, p);
+            } else if (pl.part) {
+                if (pl.wdog) hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, true, true>), g, b, 0, st, p);
+                else hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, true>), g, b, 0, st, p);
+            } else if (pl.strict) {
+                if (pl.wdog) hipLaunchKernelGGL((k_sgns_train_locked<DCH, true, BIG, false, false, true>), g, b, 0, st, p);
+                else hipLaunchKernelGGL((k_sgns_train_locked<DCH, true, BIG, false, false>), g, b, 0, st, p);
+            } else {
+                if (pl.wdog) hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, false, true>), g, b, 0, st, p);      // (forced: with the watchdog)
+                else hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, false>), g, b, 0, st, p);
+            }
             break;
-        case 6:
-            if (p.wd_ticks) hipLaunchKernelGGL((k_sgns_train_locked<DCH, true, BIG, false, false, true>), dim3(blocks), dim3(threads), 0, st, p);
-            else hipLaunchKernelGGL((k_sgns_train_locked<DCH, true, BIG, false, false>), dim3(blocks), dim3(threads), 0, st, p);
-            break;
-        case 7: hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, true, false>), dim3(blocks), dim3(threads), 0, st, p); break;
-        // block schedule of the multi-GPU path (dge_model_set_partition): in-order, atomics, commit locks
-        case 20: hipLaunchKernelGGL((k_sgns_train<DCH, 0, BIG, false, true>), dim3(blocks), dim3(threads), 0, st, p); break;
-        case 22: hipLaunchKernelGGL((k_sgns_train<DCH, 2, BIG, false, true>), dim3(blocks), dim3(threads), 0, st, p); break;
-        case 30: hipLaunchKernelGGL((k_sgns_train<DCH, 0, BIG, true, true>), dim3(blocks), dim3(threads), 0, st, p); break;      // ... with the hierarchical softmax
-        case 32: hipLaunchKernelGGL((k_sgns_train<DCH, 2, BIG, true, true>), dim3(blocks), dim3(threads), shmem, st, p); break;
-        case 25:
-            if (p.wd_ticks) hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, true, true>), dim3(blocks), dim3(threads), 0, st, p);
-            else hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, true>), dim3(blocks), dim3(threads), 0, st, p);
-            break;
-        case 27: hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, true, true>), dim3(blocks), dim3(threads), 0, st, p); break;
-        default: hipLaunchKernelGGL((k_sgns_train<DCH, 2, BIG, false, false>), dim3(blocks), dim3(threads), 0, st, p); break;
+        default: break;
     }
 }
 template <int DCH>
-static inline void launch_train(const TrainParams& p, int pol, bool big, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st) {
-    if (big) launch_train_b<DCH, true>(p, pol, blocks, threads, shmem, st);
-    else launch_train_b<DCH, false>(p, pol, blocks, threads, shmem, st);
+static inline void launch_train(const TrainParams& p, const TrainPlan& pl, hipStream_t st) {
+    if (pl.big) launch_train_b<DCH, true>(p, pl, st);
+    else launch_train_b<DCH, false>(p, pl, st);
 }
 

@@ -692,33 +692,6 @@ static void launch_finish_any(int dch, const SortedParams& q, hipStream_t st) {
     }
 }
 
-// Items of one synchronous mini-batch.  Within a mini-batch the context rows are frozen and every row takes its terms without feedback
-// from the other side, so the size is set by TERMS PER LIVE ROW: measured (scripts/quality_sorted.py, profiles/r02_quality_sorted.txt)
-// the link-prediction AUC equals the atomics schedule's up to ~120 items per row and mini-batch, slips by 0.001 per ~70 items beyond and
-// collapses between 320 and 390 (8 ranks: 73 ms per episode at 128 items per row, 69 at 256 — not worth the margin) —
-// and the HOTTEST row counts, not the average one: on a Zipf-popular graph a head row took > 1e5 terms of a 96-per-row mini-batch and
-// the tables went to NaN within an epoch.  Hence: 128 items per live row, at most 4096 for the hottest row, and no mini-batch below 5e5
-// items (the two sorts and ~16 launches per mini-batch need that much to pay): 0 = this vocabulary is too skewed or too small.
-int64_t dge_sorted_batch_items(const dge_model* m, int part_n) {
-    const int n = std::max(part_n, 1);
-    const int64_t live_rows = std::max<int64_t>(1, m->V / n);
-    const double hottest = std::min(1.0, m->row_share_max * (double)n);      // its share of one block's terms
-    int64_t items = std::min<int64_t>(96ll << 20, 128 * live_rows);
-    // (round 5: 4 096 for the busiest row, was 2 048 — on cfg3 that bound was the one that bound (its busiest vertex holds 30x the mean count: 8.8 M items where the
-    //  128-a-row rule allows 16 M) and an epoch of the cfg3-sized community graph on 8 ranks ends at the same AUC 0.9596 / loss 0.474 with 18 M-item mini-batches — the
-    //  busiest row at ~4 200 terms — as with 9 M, 10 % faster; 36 M (a whole episode, 288 a row) loses it: 0.9565 / 0.497.  scripts/blocks_minibatch_quality.py,
-    //  profiles/r05_blocks_minibatch_quality.txt)
-    items = std::min<int64_t>(items, (int64_t)(4096.0 / std::max(hottest, 1e-12)));
-    // (wide rows: from half a million items on — round 4: a 50 000-row vocabulary with rank^-0.5 popularity lands at 0.9 M and ran 3.4e8 edges/s at D = 256 under this
-    //  schedule against 2.1e8 under the atomics the rule used to leave it with: scripts/policy_sweep.py)
-    //  — on rows of more than 128 floats: with D = 64 the same vocabulary runs 7.9e8 under atomics against 4.2e8 here; the sorts do not shrink with the row)
-    // One block of the multi-GPU schedule on a vocabulary large enough for the lock kernels (>= 32 768 rows a partition): those — the mixed kernel on a skewed
-    // vocabulary — are the alternative there, not atomics, and a mini-batch that the busiest row keeps small loses to them: cfg5 at 2 ranks landed at 0.7 M items and
-    // ran 4.6e7 edges/s per rank here against 8.6e7 under the mixed kernel at 4 ranks (round 5).  From 4 M items on (cfg3's blocks: 16 .. 18 M).
-    if (n >= 2 && m->V / n >= 32768) return items >= (4 << 20) ? items : 0;
-    return items >= (m->stride > 128 ? (1 << 19) : (1 << 20)) ? items : 0;
-}
-
 struct CastI64 { __host__ __device__ int64_t operator()(int32_t x) const { return (int64_t)x; } };
 // The item sorts.  rocprim's onesweep sorts 8 key bits per pass; row numbers of 17 .. 18 bits (cfg2; a block of the 8- or 4-rank schedule) take
 // 3 passes there and 2 with 9-bit digits (scripts/micro/sort_bits.hip: 48 M items of 17 bits 1.01 ms against 1.15, 12.8 M 0.31 against 0.37;
@@ -782,8 +755,8 @@ int dge_sorted_train(dge_model* m, const TrainParams& p) {
     while ((1ll << obits) < m->V) obits++;
     const int ks1 = 1 + obits, ks2 = 11 + obits;
     // mini-batches of whole walks (dge_sorted_batch_items: ~128 items per live row, the hottest row bounded)
-    int64_t want_items = dge_sorted_batch_items(m, p.part_n);
-    if (want_items == 0) want_items = 1 << 20;         // asked for explicitly on a vocabulary the rule would not pick it for (train_rows has checked that it is safe)
+    int64_t want_items = dge_sorted_batch_items(m->stats, p.part_n);
+    if (want_items == 0) want_items = 1 << 20;         // asked for explicitly on a vocabulary the rule would not pick it for (plan_train has checked that it is safe)
     // (walks per mini-batch: as many as give want_items — then EVENED OUT over the launch: with 36 M items and 11.4 M a mini-batch the fourth mini-batch was a 1.6 M-item
     //  remainder that cost a tenth of a full one's kernels' fixed parts and went through rocPRIM's small-input merge sort, ~25 launches: 6 % of an 8-rank episode at the
     //  1 M-walk global batch, profiles/r05_sim8_1M_timeline_before.txt)

@@ -8,6 +8,6 @@
 #define DGE_CAT_(a, b) a##b
 #define DGE_CAT(a, b) DGE_CAT_(a, b)
 
-void DGE_CAT(dge_launch_train_dch, DGE_DCH)(const TrainParams& p, int pol, bool big, unsigned blocks, unsigned threads, size_t shmem, hipStream_t st) {
-    launch_train<DGE_DCH>(p, pol, big, blocks, threads, shmem, st);
+void DGE_CAT(dge_launch_train_dch, DGE_DCH)(const TrainParams& p, const TrainPlan& plan, hipStream_t st) {
+    launch_train<DGE_DCH>(p, plan, st);
 }

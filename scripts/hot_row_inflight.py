@@ -1,4 +1,4 @@
-"""How many of ONE row's updates may be in flight?  train_rows caps the workers at 48 / (the busiest row's share of the tokens): round 4 saw a rank^-1 vocabulary go to NaN at
+"""How many of ONE row's updates may be in flight?  plan_train (embedding_amd/csrc/sgns_plan.h) caps the workers at 48 / (the busiest row's share of the tokens): round 4 saw a rank^-1 vocabulary go to NaN at
 1 130 in flight and took 48 without a sweep in between.  A static graph WITH structure and a heavy head: R regions in communities of 64, half of a vertex's flow stays inside its
 community, the other half goes to a region drawn with P(rank r) ~ 1 / (r + 1) over ALL regions (the busiest region: ~4 % of all tokens).  Trained under auto's choice (atomics) with
 the worker count forced to 48 ... 768 / share and to the device's fill; edges/s, link AUC and loss on held-out steps, next to the sequential oracle and its 8 Hogwild threads.

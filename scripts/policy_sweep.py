@@ -1,4 +1,4 @@
-"""Is the auto rule of dge_train_config.update_policy (embedding_amd/csrc/sgns.hip: train_rows) the fastest choice AWAY from the four bench graphs it was
+"""Is the auto rule of dge_train_config.update_policy (embedding_amd/csrc/sgns_plan.h: auto_policy, plan_train) the fastest choice AWAY from the four bench graphs it was
 fitted on?  Synthetic walk corpora over V vocabulary rows whose popularity follows rank^-s (s = 0: flat, 0.5, 1.0: Zipf), L = W = 24, K = 5, D in {64, 128, 256};
 one launch per policy (auto, 2 = atomics, 5 = commit locks, 7 = locks + head by atomics, 8 = owner-computes); a forced policy that a short probe shows to be more
 than 4x slower than the best so far is not run at full length (commit locks on a Zipf head spin for minutes).

@@ -1,4 +1,4 @@
-"""How many concurrent walks may a SMALL vocabulary take?  train_rows caps the workers at half the vocabulary rows (Hogwild's premise: sparse collisions; measured in round 1 as
+"""How many concurrent walks may a SMALL vocabulary take?  plan_train (embedding_amd/csrc/sgns_plan.h) caps the workers at half the vocabulary rows (Hogwild's premise: sparse collisions; measured in round 1 as
 cosine >= 0.99 to the in-order result on a 2.3 k-row table).  On the reference's own tract configuration — 801 regions x 8 slices = 6 408 rows, D = 20, K = 5, L = W = 8
 (J/DeepWalk.java:62-66,89-104) — that is 3 204 workers on a device that holds 16 384, each pair a latency chain (table look-up -> rows -> atomics): 7e8 edges/s, far from any
 bandwidth.  This script trains a tract-sized graph WITH structure (communities of 9 regions, 80 % of a vertex's flow stays inside) with 3 204 ... 16 384 workers and reports

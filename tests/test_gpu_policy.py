@@ -1,4 +1,4 @@
-"""GPU: the auto rule of dge_train_config.update_policy (embedding_amd/csrc/sgns.hip: auto_policy) away from the bench graphs it was fitted on — four points of
+"""GPU: the auto rule of dge_train_config.update_policy (embedding_amd/csrc/sgns_plan.h: auto_policy) away from the bench graphs it was fitted on — four points of
 scripts/policy_sweep.py's grid (the whole table: profiles/r04_policy_sweep.txt), each a regime in which round 3's rule was wrong or unsafe.  Synthetic corpora, V
 vocabulary rows whose popularity follows rank^-s, L = W = 24, K = 5; one launch per policy.  Asserted: auto stays finite and runs at >= 0.8 of the fastest forced
 policy that stays finite.  (w2v.fit(), J/DeepWalk.java:79; the schedules are new.)"""
