@@ -143,3 +143,70 @@ def link_auc_device(model, vocab_ids, test_walks, R, NV, seed=3):
     auc = float((pos > neg).float().mean() + 0.5 * (pos == neg).float().mean())
     loss = float(torch.nn.functional.softplus(-pos.double()).mean() + torch.nn.functional.softplus(neg.double()).mean())
     return auc, loss
+
+
+# ---- the saturated, exactly summable regime (tests/test_oracle_kats.py, tests/test_gpu_conservation.py)
+# Column 0 of every row saturates the score: syn0[:, 0] = 4 and syn1neg[:, 0] = 2 * sign, so f = 8 * sign (+ something tiny) for every pair, beyond
+# MAX_EXP = 6, and word2vec's clamp gives g = (label - 1) * alpha for sign +1 (positives 0, negatives exactly -alpha) and g = label * alpha for sign -1
+# (positives exactly +alpha, negatives 0).  With alpha = min_alpha = 2^-40 and small integers in the columns of the table that stands still, the other
+# table accumulates 2^-40 x (a sum of small integers): every product and partial sum is exact while |sum| < 2^24, whatever the order of the additions.
+SAT_ALPHA = 2.0 ** -40
+SAT_CAP = 1 << 24
+
+
+def saturated_state(V, D, side, sign, seed, mag=3, use_hs=False):
+    """Initial tables of the saturated regime -> {"syn0", "syn1neg"[, "syn1"]}, float32 [V x D] (syn1: [V-1 x D]).
+    side "A": syn0[:, 1:] holds the integer codes (column 1 = 1, the count channel; the others +/- 1 .. mag, never 0) and syn1neg[:, 1:] = 0 accumulates;
+    side "B": the mirror image — syn1neg holds the codes, syn0[:, 1:] = 0 accumulates.  With use_hs, syn1[:, 0] = 2 and the rest zero: the tree step
+    is skipped on every node (|f| >= 6) and syn1 has to come back unchanged."""
+    assert side in ("A", "B") and sign in (1, -1) and D >= 2 and mag >= 1
+    rng = np.random.default_rng([int(seed), V, D])
+    codes = (rng.integers(1, mag + 1, (V, D)) * rng.choice([-1, 1], (V, D))).astype(np.float32)
+    codes[:, 1] = 1.0
+    s0 = np.zeros((V, D), np.float32); s1 = np.zeros((V, D), np.float32)
+    (s0 if side == "A" else s1)[:] = codes
+    s0[:, 0] = 4.0; s1[:, 0] = 2.0 * sign
+    out = {"syn0": s0, "syn1neg": s1}
+    if use_hs:
+        s2 = np.zeros((max(V - 1, 0), D), np.float32); s2[:, 0] = 2.0
+        out["syn1"] = s2
+    return out
+
+
+def device_rows(a, stride, rows=None):
+    """[V x D] -> the C ABI's import shape [rows x stride] (rows: the table's V; zero padding columns, zero rows behind a shorter table such as syn1)."""
+    out = np.zeros((a.shape[0] if rows is None else rows, stride), np.float32)
+    out[:a.shape[0], :a.shape[1]] = a
+    return out
+
+
+class Conservation:
+    """What conservation_diff returns: per row, `expected` / `got` — the count channel in whole updates (signed: negatives count -1, positives +1) —,
+    `deficit` = |expected| - |got| (> 0: updates lost, < 0: a surplus), `other` = the largest |difference| of the remaining columns in units of alpha."""
+
+    def __init__(self, expected, got, other):
+        self.expected, self.got, self.other = expected, got, other
+        self.deficit = np.abs(expected) - np.abs(got)
+
+    @property
+    def exact(self):
+        return bool((self.got == self.expected).all() and (self.other == 0).all())
+
+    def worst(self):
+        r = int(np.argmax(np.abs(self.deficit) + self.other))
+        return "row %d: expected %d updates, got %.3f (other columns off by %.3f alpha); %d rows differ, %d updates of %d missing" % (
+            r, self.expected[r], self.got[r], self.other[r], int(((self.got != self.expected) | (self.other != 0)).sum()),
+            int(self.deficit.sum()), int(np.abs(self.expected).sum()))
+
+
+def conservation_diff(got, want, alpha=SAT_ALPHA):
+    """Trained table `got` against the expected one `want` (both [V x D], the ACCUMULATING table of a saturated run) -> Conservation.
+    Asserts first, on `want`, the condition of the method: every accumulated |value| / alpha is an integer below 2^24 (beyond it float32 sums stop being
+    exact and the comparison would depend on the order of the additions — choose a shorter corpus or smaller codes)."""
+    w = want[:, 1:].astype(np.float64) / alpha
+    assert np.abs(w).max(initial=0.0) < SAT_CAP, "the expected table leaves the exactly summable range: |sum| = %.0f >= 2^24 — shorten the corpus or lower `mag`" % np.abs(w).max()
+    assert (w == np.rint(w)).all(), "the expected table is not a table of whole multiples of alpha: the reference is outside the saturated regime"
+    assert np.array_equal(bits(got[:, 0]), bits(want[:, 0])), "the saturating column moved"
+    g = got[:, 1:].astype(np.float64) / alpha
+    other = np.abs(g[:, 1:] - w[:, 1:]).max(1) if w.shape[1] > 1 else np.zeros(len(w))
+    return Conservation(np.rint(w[:, 0]).astype(np.int64), g[:, 0], other)

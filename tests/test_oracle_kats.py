@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import cosine_rows, layered_graph
+from helpers import SAT_ALPHA, bits, conservation_diff, cosine_rows, layered_graph, saturated_state
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 M64 = (1 << 64) - 1
@@ -193,6 +193,130 @@ def test_vocabulary_table_init_and_pair_enumeration(oracle):
                 if a != W and 0 <= c < len(sen):
                     pairs += 1
     assert pairs == m1.pairs and m1.total_words == sum(len([t for t in row if t >= 0 and t in remap]) for row in walks)
+    # ... and the same loop with the negative draws (enumerate_terms, what test_saturated_regime_equals_int64_sums stands on): its positives are these pairs
+    ctx, tgt, lab = enumerate_terms(walks, order, m1.table(T), W, K, seed, epochs=1)
+    assert int(lab.sum()) == pairs and pairs * (K - 1) < int((lab == 0).sum()) <= pairs * K
+
+
+def enumerate_terms(walks, order, table, W, K, seed, epochs=1, part_n=0):
+    """The (context row, target row, label) terms of a training run in the sequential order, restated in Python: per-(walk, centre) streams, DL4J's window
+    loop, the negative draws — table[(s >> 16) % T], row 0 redrawn as s % (V-1) + 1, a draw equal to the centre skipped — and, with part_n > 1, the block
+    schedule's rule: the blocks in turn, a pair in the block of (its context's, its centre's) partition, one stream a pair, negatives moved into the target
+    partition."""
+    MULT = 25214903917
+    remap = {v: r for r, v in enumerate(order)}
+    V, T, L = len(order), len(table), walks.shape[1]
+    PN = part_n if part_n > 1 else 1
+    ctx, tgt, lab = [], [], []
+    for ep in range(epochs):
+        for blk in range(PN * PN):
+            part_ctx, part_tgt = blk % PN, (blk % PN + blk // PN) % PN
+            for wi, row in enumerate(walks):
+                sen = [remap[t] for t in row if t >= 0 and t in remap]
+                gbase = (ep * len(walks) + wi) * L
+                for i, word in enumerate(sen):
+                    if PN > 1 and word % PN != part_tgt:
+                        continue
+                    s = mix64((seed + gbase + i) & M64)
+                    s = (s * MULT + 11) & M64
+                    b = s % W
+                    s_centre = s
+                    for a in range(b, 2 * W + 1 - b):
+                        c = i - W + a
+                        if a == W or c < 0 or c >= len(sen):
+                            continue
+                        last = sen[c]
+                        if PN > 1:
+                            if last % PN != part_ctx:
+                                continue
+                            s = mix64((s_centre + c) & M64)
+                        ctx.append(last); tgt.append(word); lab.append(1)
+                        for _ in range(K):
+                            s = (s * MULT + 11) & M64
+                            t = int(table[(s >> 16) % T])
+                            if t == 0 and V > 1:
+                                t = s % (V - 1) + 1
+                            if PN > 1:
+                                t = t // PN * PN + part_tgt
+                                if t >= V:
+                                    t -= PN
+                            if t == word:
+                                continue
+                            ctx.append(last); tgt.append(t); lab.append(0)
+    return np.array(ctx, np.int64), np.array(tgt, np.int64), np.array(lab, np.int64)
+
+
+def _saturated_corpus(seed=4, NV=40, n=70, L=9):
+    """a small ragged corpus: Zipf-ish tokens, padding behind every walk's end, holes inside, and vertices too rare for the vocabulary (min_count 2)"""
+    rng = np.random.default_rng(seed)
+    ids = np.minimum(rng.zipf(1.3, size=(n, L)) - 1, NV - 1).astype(np.int32)
+    ids[np.arange(L)[None, :] >= rng.integers(0, L + 1, n)[:, None]] = -1
+    ids[rng.random(ids.shape) < 0.08] = -1
+    return ids, NV
+
+
+def _int64_sums(state, side, sign, ctx, tgt, lab):
+    """what the accumulating table of a saturated run holds, in units of alpha: int64 sums over the terms.  sign +1: a negative term is g = -alpha and a positive
+    one 0; sign -1: a positive term is +alpha and a negative one 0 (helpers.saturated_state)."""
+    g = np.where(lab == 0, -1, 0) if sign > 0 else np.where(lab == 1, 1, 0)
+    live = g != 0
+    ctx, tgt, g = ctx[live], tgt[live], g[live]
+    codes = (state["syn0"] if side == "A" else state["syn1neg"]).astype(np.int64)
+    out = np.zeros(codes.shape, np.int64)
+    if side == "A":
+        np.add.at(out, tgt, g[:, None] * codes[ctx])          # syn1neg[target] += g * syn0[context]
+    else:
+        np.add.at(out, ctx, g[:, None] * codes[tgt])          # syn0[context] += sum over the pair's terms of g * syn1neg[target]
+    return out[:, 1:]
+
+
+@pytest.mark.parametrize("K", [0, 1, 5, 17])
+def test_saturated_regime_equals_int64_sums(oracle, K):
+    """The expected tables of tests/test_gpu_conservation.py come from the sequential oracle; here the oracle meets an independent witness.  In the saturated
+    regime (helpers.saturated_state) a run's result is alpha x (an integer sum over its terms), so the Python enumeration of the terms above predicts it EXACTLY:
+    run A (syn1neg accumulates) and run B (syn0 accumulates), both signs, two epochs, out-of-vocabulary tokens; word2vec order, lane order and the plain loop
+    bit-identical; the block schedule (part_n = 3) against the enumeration with the block rule; and with use_hs and a saturated syn1 the tree step is skipped:
+    syn1 unchanged, the negative-sampling sums as before."""
+    ids, NV = _saturated_corpus()
+    D, W, T, seed, EP = 7, 3, 997, 23, 2
+    cnt = np.bincount(ids[ids >= 0], minlength=NV)
+    order = sorted([v for v in range(NV) if cnt[v] >= 2], key=lambda v: (-cnt[v], v))
+    V = len(order)
+    assert 8 < V < NV and (ids < 0).any()
+    kw = dict(negative=K, min_count=2, epochs=EP, seed=seed, table_size=T, alpha=SAT_ALPHA, min_alpha=SAT_ALPHA)
+    # (the unigram table is the oracle's: test_vocabulary_table_init_and_pair_enumeration restates it in Python on its own; what is independent HERE is the enumeration and the sums)
+    table = oracle.train_sgns(ids, NV, D, W, **dict(kw, epochs=0)).table(T)
+    terms = {pn: enumerate_terms(ids, order, table, W, K, seed, epochs=EP, part_n=pn) for pn in (0, 3)}
+    assert K == 0 or (terms[0][2] == 0).any()
+    for side in "AB":
+        for sign in (1, -1):
+            st = saturated_state(V, D, side, sign, seed=9, mag=7)
+            init = dict(syn0_init=st["syn0"], syn1neg_init=st["syn1neg"])
+            moving, standing = ("syn1neg", "syn0") if side == "A" else ("syn0", "syn1neg")
+            runs = {}
+            for name, extra in (("arith0", dict(arith=0)), ("arith1", dict(arith=1)), ("plain", dict(arith=0)), ("blocks", dict(arith=1, part_n=3)),
+                                ("hs", dict(arith=1, use_hs=True, syn1_init=saturated_state(V, D, side, sign, seed=9, mag=7, use_hs=True)["syn1"]))):
+                oracle.set_plain(name == "plain")
+                try:
+                    runs[name] = oracle.train_sgns(ids, NV, D, W, **kw, **init, **extra)
+                finally:
+                    oracle.set_plain(False)
+            for name, m in runs.items():
+                assert m.vocab_ids.tolist() == order
+                want = _int64_sums(st, side, sign, *terms[3 if name == "blocks" else 0])
+                got = getattr(m, moving)
+                assert np.array_equal(bits(getattr(m, standing)), bits(st[standing])), (side, sign, name)        # the other table stands still
+                assert np.array_equal(bits(got[:, 0]), bits(st[moving][:, 0])), (side, sign, name)
+                assert np.array_equal(got[:, 1:].astype(np.float64) / SAT_ALPHA, want.astype(np.float64)), (side, sign, name)
+                assert m.pairs == int(terms[3 if name == "blocks" else 0][2].sum())
+                d = conservation_diff(got, alpha=SAT_ALPHA, want=np.concatenate([st[moving][:, :1], (want * SAT_ALPHA).astype(np.float32)], 1))
+                assert d.exact and (d.deficit == 0).all(), d.worst()
+            for name in ("arith1", "plain"):
+                assert np.array_equal(bits(getattr(runs[name], moving)), bits(getattr(runs["arith0"], moving))), (side, sign, name)
+            hs = runs["hs"]
+            assert np.array_equal(bits(hs.syn1), bits(saturated_state(V, D, side, sign, seed=9, mag=7, use_hs=True)["syn1"]))
+            if sign < 0:
+                assert int(np.rint(getattr(runs["arith0"], moving)[:, 1].astype(np.float64) / SAT_ALPHA).sum()) == runs["arith0"].pairs      # the count channel's sum: every positive pair once
 
 
 def test_sigmoid_table_and_lane_order_agreement(oracle):
