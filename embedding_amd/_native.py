@@ -29,6 +29,12 @@ class TrainStats(C.Structure):
                 ("walk_kernel_ms", C.c_double), ("launches", C.c_int64)]
 
 
+class EvalResult(C.Structure):
+    """struct dge_eval_result (include/dge.h) — what dge_model_eval_links / dge_model_eval_sgns hand back."""
+    _fields_ = [("pairs", C.c_int64), ("negatives", C.c_int64), ("skipped", C.c_int64), ("auc", C.c_double),
+                ("loss", C.c_double), ("kernel_ms", C.c_double)]
+
+
 # every symbol include/dge.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int
 _P = C.POINTER
@@ -85,6 +91,9 @@ SIGNATURES = {
     "dge_model_schedule": (_int, [_vp, _P(_i32), _P(_i64), _P(_i32)]),
     "dge_model_kernel": (_int, [_vp, C.c_char_p, _i32]),
     "dge_model_lock_stats": (_int, [_vp, _P(_i64), _P(_i64), _P(_i64)]),
+    "dge_model_score_pairs": (_int, [_vp, _vp, _vp, _i64, _vp]),
+    "dge_model_eval_links": (_int, [_vp, _vp, _i64, _i64, _i32, C.c_uint64, _P(EvalResult)]),
+    "dge_model_eval_sgns": (_int, [_vp, _vp, _i64, _i64, C.c_uint64, _P(EvalResult)]),
     "dge_write_vec": (_int, [_vp, _vp, C.c_char_p, _int]),
     "dge_model_free": (None, [_vp]),
     "dge_model_set_partition": (_int, [_vp, _i32, _i32, _i32]),

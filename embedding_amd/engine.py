@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._native import TrainConfig, TrainStats, check, lib
+from ._native import EvalResult, TrainConfig, TrainStats, check, lib
 
 
 def _ptr(a):
@@ -359,6 +359,38 @@ class SgnsModel:
 
     def reset_stats(self):
         check(lib.dge_model_reset_stats(self._h))
+
+    # ---- held-out evaluation (include/dge.h: dge_model_score_pairs / eval_links / eval_sgns); the model is only read
+    def score_pairs(self, ctx_t, tgt_t):
+        """syn0[row(ctx)] . syn1neg[row(tgt)] for vertex-id pairs (torch int32 tensors on the model's device) -> torch float32 tensor there;
+        NaN where an id is outside the vocabulary."""
+        import torch
+        if ctx_t.dtype != torch.int32 or tgt_t.dtype != torch.int32 or ctx_t.numel() != tgt_t.numel():
+            raise ValueError("score_pairs: two int32 tensors of one length")
+        ctx_t = ctx_t.contiguous(); tgt_t = tgt_t.contiguous()
+        out = torch.empty(ctx_t.numel(), dtype=torch.float32, device=ctx_t.device)
+        check(lib.dge_model_score_pairs(self._h, _dev_ptr(ctx_t), _dev_ptr(tgt_t), ctx_t.numel(), _dev_ptr(out)))
+        return out
+
+    @staticmethod
+    def _eval_dict(r):
+        return dict(pairs=r.pairs, negatives=r.negatives, skipped=r.skipped, auc=r.auc, loss=r.loss, kernel_ms=r.kernel_ms)
+
+    def eval_links(self, corpus, regions_per_slice, seed=3, row0=0, n_rows=None):
+        """Link-prediction AUC and loss on the held-out walk steps of corpus rows [row0, row0 + n_rows)."""
+        if n_rows is None:
+            n_rows = corpus.shape[0] - row0
+        r = EvalResult()
+        check(lib.dge_model_eval_links(self._h, corpus._h, int(row0), int(n_rows), int(regions_per_slice), int(seed), C.byref(r)))
+        return self._eval_dict(r)
+
+    def eval_sgns(self, corpus, seed=3, row0=0, n_rows=None):
+        """The negative-sampling objective (mean loss per pair) and AUC over the full-window pairs of corpus rows [row0, row0 + n_rows)."""
+        if n_rows is None:
+            n_rows = corpus.shape[0] - row0
+        r = EvalResult()
+        check(lib.dge_model_eval_sgns(self._h, corpus._h, int(row0), int(n_rows), int(seed), C.byref(r)))
+        return self._eval_dict(r)
 
     def write_vec(self, path, names=None, header=False):
         arr = None

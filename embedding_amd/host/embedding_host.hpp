@@ -383,29 +383,53 @@ class DeepWalk {
     static bool useHierarchicSoftmax;
     // learnEmbedding: every line of the .seq files is a sentence of whitespace-separated names (DefaultTokenizerFactory,
     // :70); trains with the reference's builder values and writes "name v1 .. vD" lines (:82).
+    // Held-out figures of a trained model (no reference counterpart; include/dge.h: dge_model_eval_links / dge_model_eval_sgns — the model is only read).
+    static dge_eval_result evalLinks(dge_model* m, const dge_walks* walks, int regionsPerSlice, uint64_t seed = 3) {
+        int64_t n = 0;
+        dge_check(dge_walks_info(walks, &n, nullptr, nullptr));
+        dge_eval_result r{};
+        dge_check(dge_model_eval_links(m, walks, 0, n, regionsPerSlice, seed, &r));
+        return r;
+    }
+    static dge_eval_result evalSgns(dge_model* m, const dge_walks* walks, uint64_t seed = 3) {
+        int64_t n = 0;
+        dge_check(dge_walks_info(walks, &n, nullptr, nullptr));
+        dge_eval_result r{};
+        dge_check(dge_model_eval_sgns(m, walks, 0, n, seed, &r));
+        return r;
+    }
+    // heldOutFiles / heldOut: .seq files that are NOT trained on; *heldOut receives the negative-sampling loss per pair and the AUC of the trained
+    // model on their sentences (evalSgns; a name the training files never used counts as outside the vocabulary).
     static dge_train_stats learnEmbedding(const std::vector<std::string>& seqFiles, const std::string& outVec, int layerSize,
-                                          int device = 0, int workers = 0, uint64_t seed = 1) {
+                                          int device = 0, int workers = 0, uint64_t seed = 1,
+                                          const std::vector<std::string>& heldOutFiles = {}, dge_eval_result* heldOut = nullptr) {
         std::unordered_map<std::string, int> ids;
         std::vector<std::string> names;
-        std::vector<std::vector<int32_t>> rows;
-        size_t maxLen = 1;
-        for (const std::string& f : seqFiles) {
-            std::ifstream in(f);
-            if (!in) throw std::runtime_error("cannot open " + f);
-            std::string line, tok;
-            while (std::getline(in, line)) {
-                std::istringstream ss(line);
-                std::vector<int32_t> r;
-                while (ss >> tok) {
-                    auto it = ids.find(tok);
-                    if (it == ids.end()) { it = ids.emplace(tok, (int)names.size()).first; names.push_back(tok); }
-                    r.push_back(it->second);
+        auto readSentences = [&](const std::vector<std::string>& files, bool intern, std::vector<int32_t>& walks, size_t& maxLen) {
+            std::vector<std::vector<int32_t>> rows;
+            maxLen = 1;
+            for (const std::string& f : files) {
+                std::ifstream in(f);
+                if (!in) throw std::runtime_error("cannot open " + f);
+                std::string line, tok;
+                while (std::getline(in, line)) {
+                    std::istringstream ss(line);
+                    std::vector<int32_t> r;
+                    while (ss >> tok) {
+                        auto it = ids.find(tok);
+                        if (it == ids.end() && intern) { it = ids.emplace(tok, (int)names.size()).first; names.push_back(tok); }
+                        r.push_back(it == ids.end() ? -1 : it->second);
+                    }
+                    if (!r.empty()) { maxLen = std::max(maxLen, r.size()); rows.push_back(std::move(r)); }
                 }
-                if (!r.empty()) { maxLen = std::max(maxLen, r.size()); rows.push_back(std::move(r)); }
             }
-        }
-        std::vector<int32_t> walks(rows.size() * maxLen, -1);
-        for (size_t i = 0; i < rows.size(); i++) std::copy(rows[i].begin(), rows[i].end(), walks.begin() + i * maxLen);
+            walks.assign(rows.size() * maxLen, -1);
+            for (size_t i = 0; i < rows.size(); i++) std::copy(rows[i].begin(), rows[i].end(), walks.begin() + i * maxLen);
+            return rows.size();
+        };
+        std::vector<int32_t> walks;
+        size_t maxLen = 1;
+        const size_t nRows = readSentences(seqFiles, true, walks, maxLen);
         dge_train_config cfg{};
         cfg.dim = layerSize;                       // .layerSize(layerSize)
         cfg.window = LayeredGraph::numLayer;       // .windowSize(LayeredGraph.numLayer)   :74 (the global, as in the reference)
@@ -418,12 +442,21 @@ class DeepWalk {
         cfg.n_vertices = (int32_t)std::max<size_t>(names.size(), 1);
         cfg.use_hs = useHierarchicSoftmax ? 1 : 0;
         dge_model* m = nullptr;
-        dge_check(dge_train_sgns(device, walks.data(), (int64_t)rows.size(), (int32_t)maxLen, &cfg, &m));
+        dge_check(dge_train_sgns(device, walks.data(), (int64_t)nRows, (int32_t)maxLen, &cfg, &m));
         std::vector<const char*> cn(names.size());
         for (size_t i = 0; i < names.size(); i++) cn[i] = names[i].c_str();
         dge_check(dge_write_vec(m, cn.data(), outVec.c_str(), 0));
         dge_train_stats st{};
         dge_check(dge_model_stats(m, &st));
+        if (heldOut) {
+            std::vector<int32_t> held;
+            size_t heldLen = 1;
+            const size_t nHeld = readSentences(heldOutFiles, false, held, heldLen);
+            dge_walks* hw = nullptr;
+            dge_check(dge_walks_from_host(device, held.data(), (int64_t)nHeld, (int32_t)heldLen, &hw));
+            *heldOut = evalSgns(m, hw);
+            dge_walks_free(hw);
+        }
         dge_model_free(m);
         return st;
     }

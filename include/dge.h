@@ -29,7 +29,8 @@
 extern "C" {
 #endif
 
-#define DGE_VERSION 106   /* 106: dge_selftest_atomics_wave_block; the block kernels' accumulator banks (DGE_TUNE_ACC_ROWS / ACC_DRAIN apply to both tables of a block); k_sgns_train_small and DGE_TUNE_SMALL_ROWS.
+#define DGE_VERSION 106   /* (still 106: the held-out evaluation entries — dge_model_score_pairs, dge_model_eval_links, dge_model_eval_sgns, struct dge_eval_result — were added without a bump: additions only, no struct changed size)
+                             106: dge_selftest_atomics_wave_block; the block kernels' accumulator banks (DGE_TUNE_ACC_ROWS / ACC_DRAIN apply to both tables of a block); k_sgns_train_small and DGE_TUNE_SMALL_ROWS.
                              105: stream-ordered partition copies (dge_model_export/import_partition_async, dge_model_stream), dge_host_sync_count, the lock kernels' watchdog,
                              forced schedules refused where they would diverge or spin (DGE_ERR_ARG), DGE_TUNE_ALLOW_UNSAFE / WATCHDOG_MS / HS_COPIES (additions only) */
 
@@ -273,6 +274,59 @@ int  dge_model_lock_stats(const dge_model* m, int64_t* pairs_put_back, int64_t* 
 /* Blocking waits the library has made in this process so far — stream / device / event synchronisations and blocking copies, counted at every call site.  An episode
  * of the multi-GPU block schedule makes none once its buffers exist (tests/test_gpu_distributed.py counts them); a global batch makes two (the item store's sizes). */
 int  dge_host_sync_count(int64_t* n);
+/* ------------------------------------------------------------------------------------------------
+ * Held-out evaluation (new; what gensim's compute_loss / DL4J's score listeners give a host): pair scores, link-prediction AUC and
+ * the negative-sampling loss, computed on the device from syn0 / syn1neg where they lie (csrc/eval.hip).
+ * Common to the three entries: the model is only READ — tables, lock words, counters, dge_train_stats and what dge_model_schedule
+ * reports stay as they are, bit for bit, and the trainer's per-call buffers are not used (the next dge_model_train sees the model it left).
+ * The kernels run on the model's stream, behind whatever training is queued there; the call returns after the stream has drained.
+ * With a partition set (dge_model_set_partition, n_parts > 1) the tables are in pieces: DGE_ERR_STATE.  Null / negative arguments: DGE_ERR_ARG.
+ * n = 0 / n_rows = 0: DGE_OK, zero counts, NaN figures.  A hierarchical-softmax model (use_hs) is evaluated on syn0 / syn1neg like any
+ * other: the tree term (syn1) is not scored.
+ * One dot-product routine serves all three, with an association order fixed by the row width alone: a pair scored through
+ * dge_model_score_pairs and the same pair scored inside eval_links / eval_sgns have the same bits.  The negatives are drawn by pure
+ * functions of (seed, global row, position) — dge_mix64 is splitmix64, csrc/dge_algos.h — so the counts and the AUC (carried as integer
+ * counts of wins and ties) depend on nothing else; the two loss sums are doubles added in an order fixed by the call's arguments
+ * (per-workgroup partial sums over statically assigned work, combined by one workgroup in a fixed order; no floating-point atomics):
+ * two identical calls return identical bits.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_eval_result {
+    int64_t pairs;      /* positive scores that entered the figures                         */
+    int64_t negatives;  /* negative scores that entered the figures                         */
+    int64_t skipped;    /* candidates left out — eval_links: steps with a vertex outside the vocabulary;
+                           eval_sgns: drawn negatives equal to the centre (pairs * cfg.negative == negatives + skipped) */
+    double  auc;        /* share of (positive, its negative) with pos > neg, ties count 1/2 */
+    double  loss;       /* mean over positives of softplus(-pos) + mean over negatives of
+                           softplus(neg) for eval_links; see eval_sgns for its own form     */
+    double  kernel_ms;  /* HIP-event time of the evaluation kernels                          */
+} dge_eval_result;      /* 48 bytes */
+
+/* score[i] = syn0[row(d_ctx[i])] . syn1neg[row(d_tgt[i])] in f32; NaN where either id is < 0,
+   >= n_vertices or outside the vocabulary.  Ids are the caller's vertex ids, device int32[n],
+   d_score device float[n].  What the trainer calls f for (last_word = ctx, target = tgt). */
+int  dge_model_score_pairs(dge_model* m, const int32_t* d_ctx, const int32_t* d_tgt, int64_t n, float* d_score);
+
+/* Link prediction on held-out walk steps — the measure of tests/helpers.py: link_auc.
+   For every step (a = walk[g][j], b = walk[g][j+1]), both >= 0, g = global row index row0 + i:
+     r   = (b / regions_per_slice) * regions_per_slice + dge_mix64(seed + g * max_len + j) % regions_per_slice      (unsigned 64-bit arithmetic, wrapping)
+     pos = score(ctx = b, tgt = a),  neg = score(ctx = r, tgt = a)
+   a step whose a, b or r is outside the vocabulary (or r >= n_vertices) is skipped and counted. */
+int  dge_model_eval_links(dge_model* m, const dge_walks* w, int64_t row0, int64_t n_rows,
+                          int32_t regions_per_slice, uint64_t seed, dge_eval_result* out);
+
+/* The negative-sampling objective on held-out walks, over the pairs the trainer would form
+   with a full window: the walk's in-vocabulary tokens left-packed as the trainer packs them
+   (ids < 0, >= n_vertices or outside the vocabulary dropped; t_0 .. t_{n-1});
+   for every centre i and context c with 0 < |i - c| <= cfg.window:
+     pos  = score(ctx = t_c, tgt = t_i)
+     for k in 0 .. cfg.negative-1:  slot = dge_mix64(seed + ((g * max_len + i) * max_len + c) * cfg.negative + k) % table_size      (unsigned 64-bit, wrapping)
+                                    row  = the model's unigram table at slot (dge_model_table); skipped if row == row(t_i)
+                                    neg_k = syn0[row(t_c)] . syn1neg[row]
+   loss = ( sum over pairs softplus(-pos) + sum over scored negatives softplus(neg_k) ) / pairs
+   — the per-pair objective word2vec minimises; auc as in the struct, over (pos, neg_k).  Walks of up to 12 288 tokens. */
+int  dge_model_eval_sgns(dge_model* m, const dge_walks* w, int64_t row0, int64_t n_rows,
+                         uint64_t seed, dge_eval_result* out);
+
 /* WordVectorSerializer.writeWordVectors(w2v, path)  J/DeepWalk.java:82: "name v1 .. vD\n" per vocabulary
  * row, no header (header != 0 writes the LINE-style "V D" first line of miscs/taxi_all.txt:1).
  * names[v] is the string of vertex id v; null -> the decimal id. */
