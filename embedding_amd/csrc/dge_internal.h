@@ -1,4 +1,4 @@
-// dge_internal.h — handle layouts and error plumbing shared by graph.hip and sgns.hip.
+// dge_internal.h — handle layouts, error plumbing and the counted host waits shared by every translation unit of libdge.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

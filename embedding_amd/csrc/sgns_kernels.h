@@ -1,5 +1,6 @@
 // sgns_kernels.h — device code of the skip-gram negative-sampling trainer (gfx950): row movers, the two trainer kernels and
-// their launch switch.  Included by sgns.hip (host side, self-tests) and by sgns_train_dch.hip, which is compiled once per
+// their launch switch.  Included by sgns.hip (the launch path), sgns_selftest.hip (self-tests on its primitives), sgns_place.hip and sgns_io.hip
+// (row views, the table's rank-block form) and by sgns_train_dch.hip, which is compiled once per
 // row width (DCH = 64-float chunks per row) so that the 144 kernel instantiations build in parallel.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,6 @@
-// sgns_model.h — the trainer's handle (vocabulary + tables + per-call work buffers), shared by sgns.hip (host side of the C ABI)
-// and sgns_sorted.hip (the owner-computes schedule).
+// sgns_model.h — the trainer's handle (vocabulary + tables + per-call work buffers) and the few internals its translation units call across files:
+// sgns.hip (creation and the launch path), sgns_sorted.hip (the owner-computes schedule), sgns_place.hip (table placement), sgns_io.hip (read-back,
+// `.vec`), sgns_exchange.hip (partitions, deltas, RCCL).  Not in the build stamp: a change of layout that matters to a launch shows in the files that are.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -28,7 +29,7 @@ struct dge_model {
     BlockHeadMemo block_head_memo;              // block_head's latest answer (sgns_plan.h)
     int n_cus = 256;
     float *d_syn0 = nullptr, *d_syn1neg = nullptr, *d_snap = nullptr;
-    int placed_seen[3] = {0, 0, 0}; double placed_best[3] = {0, 0, 0}, placed_worst[3] = {0, 0, 0};   // table_alloc's report for syn0, syn1neg, syn1: candidates probed, their best and worst rate (GB/s)
+    int placed_seen[3] = {0, 0, 0}; double placed_best[3] = {0, 0, 0}, placed_worst[3] = {0, 0, 0};   // dge_table_alloc's report for syn0, syn1neg, syn1: candidates probed, their best and worst rate (GB/s)
     // hierarchical softmax (cfg.use_hs): inner-node table and the Huffman paths in CSR form
     float* d_syn1 = nullptr;
     int64_t* d_hs_off = nullptr; int32_t* d_hs_points = nullptr; uint64_t* d_hs_codes = nullptr;
@@ -70,3 +71,13 @@ struct dge_model {
 struct TrainParams;
 int dge_sorted_train(dge_model* m, const TrainParams& p);
 void dge_sorted_release(dge_model* m);
+
+// Internals the translation units above call across files; hidden, so that the library's exported names stay those of include/dge.h.
+#define DGE_LOCAL __attribute__((visibility("hidden")))
+// table placement (sgns_place.hip): a table of `floats` floats in the best of several candidate allocations under a 2 ms probe (small and very large
+// tables: plain hipMalloc); dge_table_free frees what dge_table_alloc or hipMalloc returned
+DGE_LOCAL int dge_table_alloc(float** out, size_t floats, int device, hipStream_t st, int* seen, double* rate_best, double* rate_worst);
+DGE_LOCAL void dge_table_free(void* p);
+// launch timing (sgns.hip): waits for the model's stream and folds every pending event pair into kernel_ms / walk_ms
+DGE_LOCAL int dge_drain_events(dge_model* m);
+static inline unsigned dge_grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }

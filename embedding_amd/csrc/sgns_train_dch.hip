@@ -1,5 +1,5 @@
 // sgns_train_dch.hip — the trainer kernels of sgns_kernels.h for ONE row width: compiled with -DDGE_DCH=n (n = 64-float chunks
-// per row: 1, 2, 3, 4, 6, 8) into sgns_dch<n>.o; sgns.hip calls dge_launch_train_dch<n>.
+// per row: 1, 2, 3, 4, 6, 8) into sgns_dch<n>.o; train_rows (sgns.hip) calls dge_launch_train_dch<n>.
 #include "sgns_kernels.h"
 
 #ifndef DGE_DCH

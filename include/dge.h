@@ -51,9 +51,12 @@ typedef struct dge_model dge_model;   /* vocabulary + syn0/syn1neg tables, resid
 
 const char* dge_last_error(void);
 int  dge_version(void);
-/* "kernels=<hash> sorted=<hash>": 12 hex digits of the SHA-1 of the trainer kernels' sources this library was built from (sgns_kernels.h + dge_algos.h + sgns.hip — the kernels and the host file that picks their launch geometry and policy;
-   the same + sgns_sorted.hip).  The committed counter profiles (profiles/traffic.json) carry the stamp of the build they were collected with; bench.py
-   quotes a profile's bytes per pair only when the stamp matches the loaded library. */
+/* "kernels=<hash> sorted=<hash>": 12 hex digits of the SHA-1 of the stamped sources this library was built from (sgns_kernels.h + dge_algos.h + sgns_plan.h + sgns.hip;
+   the same + sgns_sorted.hip).  A source is in the stamp if and only if a change to it can change what a training launch reads or writes per pair: the trainer
+   kernels, the schedule, the code that builds what those kernels read (vocabulary order, the unigram table in its block and run forms, Huffman paths, the
+   schedule's statistics) and the code that fills the kernels' parameters and launches.  What decides only time (table placement), what runs between launches
+   (exchange, read-back, output) and what exists for tests (self-tests, probes) is not.  The committed counter profiles (profiles/traffic.json) carry the stamp
+   of the build they were collected with; bench.py quotes a profile's bytes per pair only when the stamp matches the loaded library. */
 const char* dge_build_stamp(void);
 int  dge_device_count(int* n);
 

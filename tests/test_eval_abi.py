@@ -58,4 +58,14 @@ def test_the_build_stamp_is_the_hash_of_the_stamped_sources(dge):
     assert got == want
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "cat sgns_kernels.h dge_algos.h sgns_plan.h sgns.hip |" in mk and "cat sgns_sorted.hip sgns_kernels.h dge_algos.h sgns_plan.h sgns.hip |" in mk
-    assert "eval.o" in mk and "eval" not in "".join(l for l in mk.splitlines() if "HASH" in l)
+    hash_lines = "".join(l for l in mk.splitlines() if "HASH" in l)
+    assert "eval.o" in mk and "eval" not in hash_lines
+    # what only decides time, runs between launches or exists for tests is built into the library and stays out of the stamp
+    objs = next(l for l in mk.splitlines() if l.startswith("OBJS")).split()
+    for unit in ("sgns_place", "sgns_io", "sgns_exchange", "sgns_selftest"):
+        assert os.path.exists(os.path.join(CSRC, unit + ".hip")), unit
+        assert unit + ".o" in objs, unit
+        assert unit not in hash_lines, unit
+    # ... and only sgns.o is compiled with the stamp's flags
+    recipes = [l for l in mk.splitlines() if l.startswith("\t") and "$(STAMP_FLAGS)" in l]
+    assert len(recipes) == 1 and "-c sgns.hip " in recipes[0], recipes
