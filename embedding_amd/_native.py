@@ -35,6 +35,13 @@ class EvalResult(C.Structure):
                 ("loss", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class SeqInfo(C.Structure):
+    """struct dge_seq_info (include/dge.h) — what dge_walks_from_seq_text / dge_walks_from_seq_files report."""
+    _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("rows", C.c_int64), ("tokens", C.c_int64), ("unknown", C.c_int64),
+                ("names_added", C.c_int64), ("max_len", C.c_int32), ("reserved", C.c_int32), ("read_ms", C.c_double),
+                ("kernel_ms", C.c_double)]
+
+
 # every symbol include/dge.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int
 _P = C.POINTER
@@ -64,6 +71,13 @@ SIGNATURES = {
     "dge_sample_walks_device": (_int, [_vp, _i64, _i32, _i64, _int, _i64, _P(_vp), _P(_i64)]),
     "dge_sample_walks_into": (_int, [_vp, _vp, _i64, _i64, _i64, _i64]),
     "dge_walks_from_host": (_int, [_int, _vp, _i64, _i32, _P(_vp)]),
+    "dge_names_create": (_int, [_P(_vp)]),
+    "dge_names_add": (_int, [_vp, _vp, _i64]),
+    "dge_names_count": (_int, [_vp, _P(_i64)]),
+    "dge_names_cstrs": (_int, [_vp, _P(_vp)]),
+    "dge_names_free": (None, [_vp]),
+    "dge_walks_from_seq_text": (_int, [_int, _vp, _i64, _vp, _int, _P(_vp), _P(SeqInfo)]),
+    "dge_walks_from_seq_files": (_int, [_int, _vp, _i32, _vp, _int, _P(_vp), _P(SeqInfo)]),
     "dge_walks_to_host": (_int, [_vp, _vp, _i64]),
     "dge_walks_info": (_int, [_vp, _P(_i64), _P(_i32), _P(_vp)]),
     "dge_walks_add_position_prefix": (_int, [_vp, _i32]),
@@ -123,6 +137,7 @@ SIGNATURES = {
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_fmt_g9": (_int, [_i64, C.c_uint64, _P(_i64), _P(_i64)]),
     "dge_selftest_hot_add": (_int, [_int, _i32, _i64, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
+    "dge_selftest_seq_intern": (_int, [_int, _vp, _i64, _i32, _i64, _vp, _i64, _P(_i64), _P(_i64)]),
 }
 
 

@@ -1,9 +1,10 @@
 """Thin object view of the C ABI (include/dge.h).  All compute happens in libdge.so on the GPU."""
 import ctypes as C
+import os
 
 import numpy as np
 
-from ._native import EvalResult, TrainConfig, TrainStats, check, lib
+from ._native import EvalResult, SeqInfo, TrainConfig, TrainStats, check, lib
 
 
 def _ptr(a):
@@ -133,6 +134,56 @@ class DeviceGraph:
         check(lib.dge_sample_walks_into(self._h, corpus._h, int(row0), int(n_walks), int(seed), int(first_index)))
 
 
+class Names:
+    """Interned token strings, id = position (struct dge_names, include/dge.h): what WalkCorpus.from_seq fills and SgnsModel.write_vec
+    takes.  A host object: it needs no device.  Strings are bytes in the library; `list(names)` decodes them as UTF-8 (bytes that are
+    not UTF-8 come back as surrogate escapes), `names.as_bytes()` hands them out as they are."""
+
+    def __init__(self, initial=None):
+        h = C.c_void_p(0)
+        check(lib.dge_names_create(C.byref(h)))
+        self._h = h
+        if initial:
+            self.add(initial)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.dge_names_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add(self, strs):
+        """Seed names a host already owns ids for (a graph's vertex names): they take the next ids in the order given.  A duplicate, an
+        empty name or one with a whitespace byte is refused (DgeError, code 1) and nothing is added."""
+        enc = [s if isinstance(s, bytes) else str(s).encode("utf-8", "surrogateescape") for s in strs]
+        arr = (C.c_char_p * len(enc))(*enc)
+        check(lib.dge_names_add(self._h, arr, len(enc)))
+
+    def __len__(self):
+        n = C.c_int64(0); check(lib.dge_names_count(self._h, C.byref(n))); return n.value
+
+    def _cstrs(self):
+        """const char* const* of the library's own strings (borrowed until names are added)."""
+        p = C.c_void_p(0); check(lib.dge_names_cstrs(self._h, C.byref(p))); return p
+
+    def as_bytes(self):
+        n = len(self)
+        if n == 0:
+            return []
+        arr = C.cast(self._cstrs(), C.POINTER(C.c_char_p))
+        return [arr[i] for i in range(n)]
+
+    def __iter__(self):
+        return iter([b.decode("utf-8", "surrogateescape") for b in self.as_bytes()])
+
+    def __getitem__(self, i):
+        n = len(self)
+        if not -n <= i < n:
+            raise IndexError(i)
+        return C.cast(self._cstrs(), C.POINTER(C.c_char_p))[i % n].decode("utf-8", "surrogateescape")
+
+
 class WalkCorpus:
     """Walk corpus int32 [n x L] in HBM (replaces the .seq text corpus between J/CrossTimeGraph.java:132-141
     and J/DeepWalk.java:49-56)."""
@@ -148,6 +199,30 @@ class WalkCorpus:
         h = C.c_void_p(0)
         check(lib.dge_walks_from_host(int(device), _ptr(walks), n, L, C.byref(h)))
         return cls(h, int(device))
+
+    @classmethod
+    def from_seq(cls, paths_or_bytes, names=None, intern=True, device=0):
+        """.seq text -> (corpus, names, info): tokenised, interned and packed on the device (include/dge.h: dge_walks_from_seq_files /
+        dge_walks_from_seq_text).  paths_or_bytes: a path, a sequence of paths (taken in order), or the text itself as bytes / bytearray /
+        memoryview.  names: a Names whose entries keep their ids (default: a new, empty one); new names are appended to it in the order of
+        their first appearance.  intern=False adds nothing: a token that is not in `names` becomes -1 in its place and is counted in
+        info["unknown"].  info: the fields of struct dge_seq_info."""
+        if names is None:
+            names = Names()
+        h = C.c_void_p(0); inf = SeqInfo()
+        if isinstance(paths_or_bytes, (bytes, bytearray, memoryview)):
+            data = paths_or_bytes
+            if isinstance(data, bytes):
+                ptr = C.cast(C.c_char_p(data), C.c_void_p); n = len(data)
+            else:
+                view = np.frombuffer(data, np.uint8)
+                ptr = _ptr(view); n = view.size
+            check(lib.dge_walks_from_seq_text(int(device), ptr, n, names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
+        else:
+            paths = [paths_or_bytes] if isinstance(paths_or_bytes, (str, os.PathLike)) else list(paths_or_bytes)
+            arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+            check(lib.dge_walks_from_seq_files(int(device), arr, len(paths), names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
+        return cls(h, int(device)), names, {f[0]: getattr(inf, f[0]) for f in SeqInfo._fields_ if f[0] != "reserved"}
 
     def close(self):
         if getattr(self, "_h", None):
@@ -393,8 +468,11 @@ class SgnsModel:
         return self._eval_dict(r)
 
     def write_vec(self, path, names=None, header=False):
+        """names: a list of str (names[v] = the string of vertex id v; None entries -> the decimal id), a Names, or None."""
         arr = None
-        if names is not None:
+        if isinstance(names, Names):
+            arr = names._cstrs()
+        elif names is not None:
             arr = (C.c_char_p * len(names))(*[n.encode() if n is not None else None for n in names])
         check(lib.dge_write_vec(self._h, arr, str(path).encode(), int(bool(header))))
 

@@ -381,7 +381,7 @@ class DeepWalk {
     // term next to the 5 negatives; true (the default, as for the authors' runs) reproduces that, false is the
     // negative-sampling path BASELINE.json's metric is quoted on.
     static bool useHierarchicSoftmax;
-    // learnEmbedding: every line of the .seq files is a sentence of whitespace-separated names (DefaultTokenizerFactory,
+    // learnEmbedding (below): every line of the .seq files is a sentence of whitespace-separated names (DefaultTokenizerFactory,
     // :70); trains with the reference's builder values and writes "name v1 .. vD" lines (:82).
     // Held-out figures of a trained model (no reference counterpart; include/dge.h: dge_model_eval_links / dge_model_eval_sgns — the model is only read).
     static dge_eval_result evalLinks(dge_model* m, const dge_walks* walks, int regionsPerSlice, uint64_t seed = 3) {
@@ -398,38 +398,55 @@ class DeepWalk {
         dge_check(dge_model_eval_sgns(m, walks, 0, n, seed, &r));
         return r;
     }
+    // The .seq reader as the host used to run it — std::getline, operator>>, a hash map — kept for the equality test (tests/native/host_seq_test.cpp) and as
+    // the yardstick of scripts/seq_ingest_rate.py; learnEmbedding reads through dge_walks_from_seq_files now.  intern = false: a name that is not in `ids`
+    // becomes -1 in its place.  -> rows; walks is [rows x maxLen] padded with -1.
+    static size_t readSentencesHost(const std::vector<std::string>& files, bool intern, std::unordered_map<std::string, int>& ids, std::vector<std::string>& names,
+                                    std::vector<int32_t>& walks, size_t& maxLen) {
+        std::vector<std::vector<int32_t>> rows;
+        maxLen = 1;
+        for (const std::string& f : files) {
+            std::ifstream in(f);
+            if (!in) throw std::runtime_error("cannot open " + f);
+            std::string line, tok;
+            while (std::getline(in, line)) {
+                std::istringstream ss(line);
+                std::vector<int32_t> r;
+                while (ss >> tok) {
+                    auto it = ids.find(tok);
+                    if (it == ids.end() && intern) { it = ids.emplace(tok, (int)names.size()).first; names.push_back(tok); }
+                    r.push_back(it == ids.end() ? -1 : it->second);
+                }
+                if (!r.empty()) { maxLen = std::max(maxLen, r.size()); rows.push_back(std::move(r)); }
+            }
+        }
+        walks.assign(rows.size() * maxLen, -1);
+        for (size_t i = 0; i < rows.size(); i++) std::copy(rows[i].begin(), rows[i].end(), walks.begin() + i * maxLen);
+        return rows.size();
+    }
+    // .seq files -> a corpus resident on the device, tokenised and interned there (include/dge.h: dge_walks_from_seq_files); new names are appended to `names`
+    // when intern is set, otherwise a name that is not in it becomes -1 in its place.  The caller frees the corpus.
+    static dge_walks* readSentences(const std::vector<std::string>& files, bool intern, dge_names* names, int device, dge_seq_info* info = nullptr) {
+        std::vector<const char*> paths;
+        for (const std::string& f : files) paths.push_back(f.c_str());
+        dge_walks* w = nullptr;
+        dge_check(dge_walks_from_seq_files(device, paths.data(), (int32_t)paths.size(), names, intern ? 1 : 0, &w, info));
+        return w;
+    }
     // heldOutFiles / heldOut: .seq files that are NOT trained on; *heldOut receives the negative-sampling loss per pair and the AUC of the trained
     // model on their sentences (evalSgns; a name the training files never used counts as outside the vocabulary).
+    // The corpus never exists on the host: the files' bytes go to the device, which tokenises and interns them and trains where they lie.
     static dge_train_stats learnEmbedding(const std::vector<std::string>& seqFiles, const std::string& outVec, int layerSize,
                                           int device = 0, int workers = 0, uint64_t seed = 1,
                                           const std::vector<std::string>& heldOutFiles = {}, dge_eval_result* heldOut = nullptr) {
-        std::unordered_map<std::string, int> ids;
-        std::vector<std::string> names;
-        auto readSentences = [&](const std::vector<std::string>& files, bool intern, std::vector<int32_t>& walks, size_t& maxLen) {
-            std::vector<std::vector<int32_t>> rows;
-            maxLen = 1;
-            for (const std::string& f : files) {
-                std::ifstream in(f);
-                if (!in) throw std::runtime_error("cannot open " + f);
-                std::string line, tok;
-                while (std::getline(in, line)) {
-                    std::istringstream ss(line);
-                    std::vector<int32_t> r;
-                    while (ss >> tok) {
-                        auto it = ids.find(tok);
-                        if (it == ids.end() && intern) { it = ids.emplace(tok, (int)names.size()).first; names.push_back(tok); }
-                        r.push_back(it == ids.end() ? -1 : it->second);
-                    }
-                    if (!r.empty()) { maxLen = std::max(maxLen, r.size()); rows.push_back(std::move(r)); }
-                }
-            }
-            walks.assign(rows.size() * maxLen, -1);
-            for (size_t i = 0; i < rows.size(); i++) std::copy(rows[i].begin(), rows[i].end(), walks.begin() + i * maxLen);
-            return rows.size();
-        };
-        std::vector<int32_t> walks;
-        size_t maxLen = 1;
-        const size_t nRows = readSentences(seqFiles, true, walks, maxLen);
+        struct Held {      // freed on every way out, exceptions included
+            dge_names* names = nullptr; dge_walks* walks = nullptr; dge_walks* held = nullptr; dge_model* m = nullptr;
+            ~Held() { if (m) dge_model_free(m); if (held) dge_walks_free(held); if (walks) dge_walks_free(walks); if (names) dge_names_free(names); }
+        } h;
+        dge_check(dge_names_create(&h.names));
+        h.walks = readSentences(seqFiles, true, h.names, device);
+        int64_t nNames = 0;
+        dge_check(dge_names_count(h.names, &nNames));
         dge_train_config cfg{};
         cfg.dim = layerSize;                       // .layerSize(layerSize)
         cfg.window = LayeredGraph::numLayer;       // .windowSize(LayeredGraph.numLayer)   :74 (the global, as in the reference)
@@ -439,25 +456,18 @@ class DeepWalk {
         cfg.workers = workers;                     // .workers(8) -> GPU workers
         cfg.alpha = 0.025f; cfg.min_alpha = 1e-4f; // DL4J defaults
         cfg.seed = seed; cfg.table_size = 0;
-        cfg.n_vertices = (int32_t)std::max<size_t>(names.size(), 1);
+        cfg.n_vertices = (int32_t)std::max<int64_t>(nNames, 1);
         cfg.use_hs = useHierarchicSoftmax ? 1 : 0;
-        dge_model* m = nullptr;
-        dge_check(dge_train_sgns(device, walks.data(), (int64_t)nRows, (int32_t)maxLen, &cfg, &m));
-        std::vector<const char*> cn(names.size());
-        for (size_t i = 0; i < names.size(); i++) cn[i] = names[i].c_str();
-        dge_check(dge_write_vec(m, cn.data(), outVec.c_str(), 0));
+        dge_check(dge_train_sgns_device(h.walks, &cfg, &h.m));
+        const char* const* cn = nullptr;
+        dge_check(dge_names_cstrs(h.names, &cn));
+        dge_check(dge_write_vec(h.m, cn, outVec.c_str(), 0));
         dge_train_stats st{};
-        dge_check(dge_model_stats(m, &st));
+        dge_check(dge_model_stats(h.m, &st));
         if (heldOut) {
-            std::vector<int32_t> held;
-            size_t heldLen = 1;
-            const size_t nHeld = readSentences(heldOutFiles, false, held, heldLen);
-            dge_walks* hw = nullptr;
-            dge_check(dge_walks_from_host(device, held.data(), (int64_t)nHeld, (int32_t)heldLen, &hw));
-            *heldOut = evalSgns(m, hw);
-            dge_walks_free(hw);
+            h.held = readSentences(heldOutFiles, false, h.names, device);
+            *heldOut = evalSgns(h.m, h.held);
         }
-        dge_model_free(m);
         return st;
     }
 };

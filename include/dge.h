@@ -132,6 +132,46 @@ int  dge_sample_walks_device(const dge_graph* g, int64_t n_walks, int32_t max_le
 int  dge_sample_walks_into(const dge_graph* g, dge_walks* w, int64_t row0, int64_t n_walks, int64_t seed,
                            int64_t first_index);
 int  dge_walks_from_host(int device, const int32_t* walks, int64_t n_walks, int32_t max_len, dge_walks** out);
+/* ---- .seq text in (new; additions only, DGE_VERSION unchanged): the reference hands its walks to the trainer as text, one walk per line, names joined by
+ * blanks (written J/CrossTimeGraph.java:136-137, read J/DeepWalk.java:49-56).  The text is tokenised, interned and packed on the device (csrc/seq_ingest.hip).
+ *   - The text is BYTES.  A line ends at '\n'; the last line may lack it.  Whitespace is the six bytes 0x09-0x0D and 0x20 (C's isspace in the "C" locale; '\r'
+ *     among them, so CRLF files read the same); every other byte, 0x80-0xFF included, is token material; a token is a maximal run of such bytes, of any length.
+ *   - A line without a token gives no row; row r is the r-th line that has one; max_len is the largest token count of a line (at least 1); rows are padded with -1.
+ *     A text without rows yields what dge_walks_from_host yields for n_walks = 0.
+ *   - Several files are taken in the order given; a file whose last byte is not '\n' ends its last line where it ends (tokens never merge across files).
+ *   - Ids: the names `names` already holds keep ids 0 .. n-1; a new name gets the next id in the order of its FIRST APPEARANCE in the text, and is appended to
+ *     `names`.  intern == 0: nothing is added; a token that is not in `names` becomes -1 in its place (the trainer and the evaluation drop ids < 0 and
+ *     left-pack) and is counted in info.unknown.
+ *   - A NUL byte in the text: DGE_ERR_IO naming its offset (names are handed out as C strings).  A file that is missing or unreadable: DGE_ERR_IO with its path.
+ *     A working set that does not fit in device memory: DGE_ERR_CAP with the bytes asked for.  Null / negative arguments: DGE_ERR_ARG before a device is looked
+ *     for.  On any error *out is NULL and `names` is as it was.
+ *   - Walks and names are a pure function of the bytes and the prior names: no floating point, nothing that depends on timing or launch geometry.
+ * dge_names: interned strings, id = position.  A host object — create / add / count / cstrs need no device. */
+typedef struct dge_names dge_names;
+int  dge_names_create(dge_names** out);
+/* a host that already owns ids (a LayeredGraph's vertex ids) seeds them.  All or nothing: a duplicate (of a held name or within strs), an empty name or one
+ * that holds a whitespace byte (it could never be a token): DGE_ERR_ARG, nothing added */
+int  dge_names_add(dge_names* n, const char* const* strs, int64_t count);
+int  dge_names_count(const dge_names* n, int64_t* count);
+/* borrowed, NUL-terminated, dge_names_count entries — what dge_write_vec takes as `names`; valid until the next call that adds names (an ingest with intern != 0 included) */
+int  dge_names_cstrs(const dge_names* n, const char* const** strs);
+void dge_names_free(dge_names* n);
+
+typedef struct dge_seq_info {
+    int64_t bytes;        /* bytes of text taken (the files' sizes added up)                             */
+    int64_t lines;        /* lines, a last one without '\n' included                                      */
+    int64_t rows;         /* lines with a token = rows of the corpus                                      */
+    int64_t tokens;       /* == (ids >= 0 in the corpus) + unknown                                        */
+    int64_t unknown;      /* intern == 0: tokens that are not in `names` (-1 in the corpus)               */
+    int64_t names_added;
+    int32_t max_len;
+    int32_t reserved;
+    double  read_ms;      /* wall clock spent getting the bytes to the device                             */
+    double  kernel_ms;    /* HIP-event time of the ingest kernels                                         */
+} dge_seq_info;           /* 72 bytes */
+
+int  dge_walks_from_seq_text(int device, const char* text, int64_t n_bytes, dge_names* names, int intern, dge_walks** out, dge_seq_info* info /* may be NULL */);
+int  dge_walks_from_seq_files(int device, const char* const* paths, int32_t n_paths, dge_names* names, int intern, dge_walks** out, dge_seq_info* info /* may be NULL */);
 int  dge_walks_to_host(const dge_walks* w, int32_t* out, int64_t cap_elems);
 /* d_ptr: the corpus in device memory, READ-ONLY for the caller: a trainer keeps what it derived from a corpus the library has not
  * written since (vocabulary rows, word offsets) */
@@ -461,6 +501,11 @@ int  dge_selftest_atomics_wave_block(int device, int32_t n_rows, int32_t n_acc, 
 int  dge_selftest_fmt_g9(int64_t n, uint64_t seed, int64_t* fast_path, int64_t* mismatches);
 int  dge_selftest_hot_add(int device, int32_t n_hot, int64_t n_workers, int32_t iters, int32_t drain, uint64_t seed,
                           int64_t* total_additions, double* max_abs_error);
+/* the .seq ingest's tokeniser and name table on `text` (no prior names), with the token hash cut to hash_bits (1 .. 64) bits and the table started at
+ * initial_slots slots — few bits make distinct strings share a hash (byte comparison, probing), few slots make the table grow and the pass be redone.
+ * ids int32[*n_tokens]: the first-appearance id of every token in text order; *n_names: distinct tokens.  cap < *n_tokens: DGE_ERR_CAP with both counts set. */
+int  dge_selftest_seq_intern(int device, const char* text, int64_t n_bytes, int32_t hash_bits, int64_t initial_slots, int32_t* ids, int64_t cap, int64_t* n_tokens,
+                             int64_t* n_names);
 
 #ifdef __cplusplus
 }
