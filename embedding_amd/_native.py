@@ -42,6 +42,12 @@ class SeqInfo(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class SeqOutInfo(C.Structure):
+    """struct dge_seq_out_info (include/dge.h) — what dge_walks_to_seq_text / dge_walks_write_seq report."""
+    _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("tokens", C.c_int64), ("empty_lines", C.c_int64), ("kernel_ms", C.c_double),
+                ("write_ms", C.c_double)]
+
+
 # every symbol include/dge.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int
 _P = C.POINTER
@@ -78,6 +84,8 @@ SIGNATURES = {
     "dge_names_free": (None, [_vp]),
     "dge_walks_from_seq_text": (_int, [_int, _vp, _i64, _vp, _int, _P(_vp), _P(SeqInfo)]),
     "dge_walks_from_seq_files": (_int, [_int, _vp, _i32, _vp, _int, _P(_vp), _P(SeqInfo)]),
+    "dge_walks_to_seq_text": (_int, [_vp, _i64, _i64, _vp, _int, _vp, _i64, _P(_i64), _P(SeqOutInfo)]),
+    "dge_walks_write_seq": (_int, [_vp, _i64, _i64, _vp, _int, C.c_char_p, _int, _P(SeqOutInfo)]),
     "dge_walks_to_host": (_int, [_vp, _vp, _i64]),
     "dge_walks_info": (_int, [_vp, _P(_i64), _P(_i32), _P(_vp)]),
     "dge_walks_add_position_prefix": (_int, [_vp, _i32]),

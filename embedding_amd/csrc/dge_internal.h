@@ -4,7 +4,10 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <atomic>
+#include <memory>
 #include <string>
+#include <string_view>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/dge.h"
@@ -113,6 +116,16 @@ struct dge_walks {
     uint64_t gen = 0;          // changes whenever the library writes the corpus (a trainer may keep what it derived from an unchanged one)
 };
 uint64_t dge_next_generation();
+
+// interned strings, id = position: a host object, no device involved.  seq_ingest.hip fills it, seq_write.hip reads ptr / len
+struct dge_names {
+    std::vector<std::unique_ptr<char[]>> blobs;     // NUL-terminated strings back to back; a blob never moves once it is in
+    std::vector<const char*> ptr;                   // id -> string
+    std::vector<int64_t> len;
+    int64_t bytes = 0;                              // sum of len
+    std::unordered_set<std::string_view> index;     // for dge_names_add's duplicate check; built on the first add after an ingest appended names
+    size_t indexed = 0;
+};
 
 int dge_graph_ensure_csr(dge_graph* g);
 // launches the strided walk kernel on `stream`; rows [row0,row0+n) of out (row length L)

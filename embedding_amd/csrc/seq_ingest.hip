@@ -49,16 +49,7 @@
 #include "dge_internal.h"
 #include "seq_plan.h"
 
-// ------------------------------------------------------------------------------------------ dge_names: a host object, no device involved
-struct dge_names {
-    std::vector<std::unique_ptr<char[]>> blobs;     // NUL-terminated strings back to back; a blob never moves once it is in
-    std::vector<const char*> ptr;                   // id -> string
-    std::vector<int64_t> len;
-    int64_t bytes = 0;                              // sum of len
-    std::unordered_set<std::string_view> index;     // for dge_names_add's duplicate check; built on the first add after an ingest appended names
-    size_t indexed = 0;
-};
-
+// ------------------------------------------------------------------------------------------ dge_names: a host object, no device involved (the struct: dge_internal.h)
 static void names_index(dge_names* n) {
     for (; n->indexed < n->ptr.size(); n->indexed++) n->index.emplace(n->ptr[n->indexed], (size_t)n->len[n->indexed]);
 }

@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import EvalResult, SeqInfo, TrainConfig, TrainStats, check, lib
+from ._native import EvalResult, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, check, lib
 
 
 def _ptr(a):
@@ -242,6 +242,33 @@ class WalkCorpus:
         out = np.empty((n, L), np.int32)
         check(lib.dge_walks_to_host(self._h, _ptr(out), n * L))
         return out
+
+    def _seq_args(self, names, row0, n_rows):
+        if n_rows is None:
+            n_rows = self.shape[0] - int(row0)
+        if names is not None and not isinstance(names, Names):
+            names = Names(names)
+        return names, int(row0), int(n_rows)
+
+    def write_seq(self, path, names=None, position_prefix=False, row0=0, n_rows=None, append=False):
+        """Rows [row0, row0 + n_rows) as .seq text into `path`, formatted on the device (include/dge.h: dge_walks_write_seq): one line per row, the
+        names of its ids >= 0 joined by one blank; position_prefix writes the token of column j as "j-name".  names: a Names or a list (names[v] = the
+        string of id v); None writes the decimal ids.  append=False creates or truncates the file.  -> the fields of struct dge_seq_out_info."""
+        names, row0, n_rows = self._seq_args(names, row0, n_rows)
+        inf = SeqOutInfo()
+        check(lib.dge_walks_write_seq(self._h, row0, n_rows, names._h if names is not None else None, int(bool(position_prefix)), os.fsencode(path),
+                                      int(bool(append)), C.byref(inf)))
+        return {f[0]: getattr(inf, f[0]) for f in SeqOutInfo._fields_}
+
+    def to_seq_bytes(self, names=None, position_prefix=False, row0=0, n_rows=None):
+        """The same text as write_seq's, into host memory (dge_walks_to_seq_text: a size query, then the text) -> (bytes, info)."""
+        names, row0, n_rows = self._seq_args(names, row0, n_rows)
+        nh = names._h if names is not None else None
+        need = C.c_int64(0); inf = SeqOutInfo()
+        check(lib.dge_walks_to_seq_text(self._h, row0, n_rows, nh, int(bool(position_prefix)), None, 0, C.byref(need), None))
+        buf = np.empty(max(need.value, 1), np.uint8)
+        check(lib.dge_walks_to_seq_text(self._h, row0, n_rows, nh, int(bool(position_prefix)), _ptr(buf), need.value, C.byref(need), C.byref(inf)))
+        return buf[:need.value].tobytes(), {f[0]: getattr(inf, f[0]) for f in SeqOutInfo._fields_}
 
     def add_position_prefix(self, region_count):
         check(lib.dge_walks_add_position_prefix(self._h, int(region_count)))

@@ -186,6 +186,17 @@ class LayeredGraph {
         cache_pos_ = cache_rows_ = 0;
         return out;
     }
+    // the same walks as a corpus that stays on the device (the caller frees it); consumes LayeredGraph::rnd in the same way
+    dge_walks* sampleVertexSequencesDevice(int64_t n) {
+        need_built();
+        dge_walks* w = nullptr;
+        int64_t draws = 0;
+        dge_check(dge_sample_walks_device(h_, n, numLayer, rnd.seed(), 0, rnd.draws(), &w, &draws));
+        rnd.advance(draws);
+        cache_pos_ = cache_rows_ = 0;
+        return w;
+    }
+    int32_t numDeviceIds() const { return nv_; }      // device ids are [0, numDeviceIds())
     const std::string& nameOfDeviceId(int32_t id) const { return id < (int32_t)byId_.size() && byId_[id] ? byId_[id]->name : extra_[id - (int32_t)byId_.size()]->name; }
     dge_graph* handle() { return h_; }
     int64_t numEdges() const { int64_t e = 0; for (const auto& kv : allVertices) e += (int64_t)kv.second->edgesOut.size(); return e; }
@@ -299,25 +310,30 @@ class CrossTimeGraph : public LayeredGraph {
 
  protected:
     friend class SpatialGraph;
+    // The walks are sampled chunk by chunk into a device corpus — LayeredGraph::rnd consumed as sampleVertexSequences consumes it — and each chunk's lines are
+    // formatted on the device and appended to the file (include/dge.h: dge_walks_write_seq): the corpus never comes to the host.  The names go over once, in the
+    // order of the device ids.  A name that could never be read back as one token (empty, holding whitespace) or that two vertices share is refused by
+    // dge_names_add: std::runtime_error, as for every other status.
     static void write_seq(LayeredGraph& g, const std::string& path, int64_t n, bool positionPrefix) {
-        std::ofstream out(path);
-        if (!out) throw std::runtime_error("cannot open " + path);
-        const int L = LayeredGraph::numLayer;
+        struct Held {      // freed on every way out, exceptions included
+            dge_names* names = nullptr; dge_walks* walks = nullptr;
+            ~Held() { if (walks) dge_walks_free(walks); if (names) dge_names_free(names); }
+        } h;
+        if (n <= 0) {      // no walk, no draw: the empty file the reference's loop leaves
+            std::ofstream out(path);
+            if (!out) throw std::runtime_error("cannot open " + path);
+            return;
+        }
+        std::vector<const char*> cn((size_t)g.numDeviceIds());
+        for (size_t v = 0; v < cn.size(); v++) cn[v] = g.nameOfDeviceId((int32_t)v).c_str();
+        dge_check(dge_names_create(&h.names));
+        dge_check(dge_names_add(h.names, cn.data(), (int64_t)cn.size()));
         const int64_t chunk = 1 << 18;
         for (int64_t done = 0; done < n; done += chunk) {
-            int64_t m = std::min(chunk, n - done);
-            std::vector<int32_t> w = g.sampleVertexSequences(m);
-            std::string line;
-            for (int64_t i = 0; i < m; i++) {
-                line.clear();
-                for (int j = 0; j < L && w[(size_t)i * L + j] >= 0; j++) {
-                    if (j) line += ' ';
-                    if (positionPrefix) { line += std::to_string(j); line += '-'; }   // J/SpatialGraph.java:105-108
-                    line += g.nameOfDeviceId(w[(size_t)i * L + j]);
-                }
-                line += '\n';
-                out << line;
-            }
+            const int64_t m = std::min(chunk, n - done);
+            h.walks = g.sampleVertexSequencesDevice(m);
+            dge_check(dge_walks_write_seq(h.walks, 0, m, h.names, positionPrefix ? 1 : 0, path.c_str(), done > 0 ? 1 : 0, nullptr));
+            dge_walks_free(h.walks); h.walks = nullptr;
         }
     }
 };

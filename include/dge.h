@@ -172,6 +172,43 @@ typedef struct dge_seq_info {
 
 int  dge_walks_from_seq_text(int device, const char* text, int64_t n_bytes, dge_names* names, int intern, dge_walks** out, dge_seq_info* info /* may be NULL */);
 int  dge_walks_from_seq_files(int device, const char* const* paths, int32_t n_paths, dge_names* names, int intern, dge_walks** out, dge_seq_info* info /* may be NULL */);
+/* ---- .seq text out (new; additions only, DGE_VERSION unchanged): the mirror image of the entries above — rows [row0, row0 + n_rows) of a resident corpus
+ * as the text the reference's walk stage writes (J/CrossTimeGraph.java:127-148, J/SpatialGraph.java:91-121), sized and spelled on the device
+ * (csrc/seq_write.hip).  The text is this byte string:
+ *   - Row r of [row0, row0 + n_rows) gives one line: the tokens of its entries with id >= 0, in column order, joined by ONE blank (0x20), then '\n'.
+ *   - Entries < 0 are skipped wherever they stand, not only as trailing pad (what embedding_amd/io.py: write_seq does; on everything the sampler produces
+ *     it equals the writer loops of the host mirrors, which stop at the first pad).
+ *   - A row without an id >= 0 is a bare '\n'.  The reader above drops such a line: it gives no row.
+ *   - The token of id v is the bytes of names[v]; with names == NULL it is the decimal form of v, as in dge_write_vec.
+ *   - position_prefix != 0: the token in COLUMN j is preceded by the decimal j and '-' (J/SpatialGraph.java:105-108).  j is the column: a skipped entry does
+ *     not renumber the ones behind it.
+ *   - No NUL byte, no header.  The text is a pure function of the corpus rows, the names and the flag: no floating point, nothing that depends on timing or
+ *     launch geometry.
+ * Statuses:
+ *   - Null w / n_bytes / path, negative row0 / n_rows / cap, text == NULL with cap > 0, row0 + n_rows beyond the corpus: DGE_ERR_ARG, before a device is
+ *     looked for.
+ *   - An id >= dge_names_count(names): DGE_ERR_RANGE naming the row, the column and the id — the least (row, column) that holds one.  It is found in the sizing
+ *     pass, before anything is written: text is untouched, the file is neither created nor truncated nor appended to.
+ *   - dge_walks_to_seq_text: text == NULL with cap == 0 is a size query (DGE_OK, *n_bytes = the text's size).  cap smaller than the text: DGE_ERR_CAP with
+ *     *n_bytes set and text untouched.  Otherwise *n_bytes is the size written.
+ *   - dge_walks_write_seq: append == 0 creates or truncates the file, append != 0 appends to it (a host that samples in chunks writes chunk after chunk).
+ *     Open or write failure: DGE_ERR_IO with the path and the OS error.
+ *   - n_rows == 0: DGE_OK, zero bytes; an empty file is created when append == 0.
+ * Both entries only read the corpus and the names. */
+typedef struct dge_seq_out_info {
+    int64_t bytes;        /* bytes of text produced                                                       */
+    int64_t lines;        /* == n_rows: every row gives a line                                            */
+    int64_t tokens;       /* ids >= 0 written                                                              */
+    int64_t empty_lines;  /* rows without an id >= 0 (a bare '\n')                                         */
+    double  kernel_ms;    /* HIP-event time of the formatting kernels (sizing, scan, every slab's emit)    */
+    double  write_ms;     /* wall clock of getting the bytes off the device and to their place: the slab   */
+                          /* loop — copies to pinned memory and write() / memcpy, overlapped with the emit */
+} dge_seq_out_info;       /* 48 bytes */
+
+int  dge_walks_to_seq_text(const dge_walks* w, int64_t row0, int64_t n_rows, const dge_names* names, int position_prefix,
+                           char* text, int64_t cap, int64_t* n_bytes /* required */, dge_seq_out_info* info /* may be NULL */);
+int  dge_walks_write_seq(const dge_walks* w, int64_t row0, int64_t n_rows, const dge_names* names, int position_prefix,
+                         const char* path, int append, dge_seq_out_info* info /* may be NULL */);
 int  dge_walks_to_host(const dge_walks* w, int32_t* out, int64_t cap_elems);
 /* d_ptr: the corpus in device memory, READ-ONLY for the caller: a trainer keeps what it derived from a corpus the library has not
  * written since (vocabulary rows, word offsets) */

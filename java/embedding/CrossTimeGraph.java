@@ -1,9 +1,7 @@
 package embedding;
 
-import java.io.BufferedWriter;
 import java.io.FileWriter;
 import java.io.IOException;
-import java.io.Writer;
 
 /**
  * Drop-in for the reference's embedding.CrossTimeGraph (J/CrossTimeGraph.java): same public members.  Edge rule (:36-39,
@@ -119,34 +117,31 @@ public class CrossTimeGraph extends LayeredGraph {
         long t2 = System.currentTimeMillis();
         System.out.println("Starting sequence sampling...");
         String path = String.format("../miscs/%d/deepwalkseq-%s/taxi-crosstime.seq", DeepWalk.Year, regionLevel);
-        try (BufferedWriter fout = new BufferedWriter(new FileWriter(path))) {
-            writeWalks(g, fout, numSamples, false);
-        } catch (IOException e) {
+        try {
+            writeWalks(g, path, numSamples, false);
+        } catch (RuntimeException e) {
             e.printStackTrace();
         }
         System.out.format("Sampling %d sequences finished in %f seconds.\n", numSamples, (System.currentTimeMillis() - t2) / 1000.0);
     }
 
-    /** n walks as text lines; positionPrefix writes token j as "j-name" (J/SpatialGraph.java:105-108) */
-    static void writeWalks(LayeredGraph g, Writer out, long n, boolean positionPrefix) throws IOException {
-        final int L = LayeredGraph.numLayer;
+    /**
+     * n walks as text lines into path; positionPrefix writes token j as "j-name" (J/SpatialGraph.java:105-108).  Sampled and formatted on the device block by
+     * block (LayeredGraph.sampleVertexSequencesToSeq): the file's bytes and the state of rnd are those of the loop over sampleVertexSequences(m) this replaces.
+     */
+    static void writeWalks(LayeredGraph g, String path, long n, boolean positionPrefix) {
         final long block = 1 << 18;
-        StringBuilder line = new StringBuilder(16 * L);
         long tenth = Math.max(n / 10, 1);
-        for (long done = 0; done < n; done += block) {
-            int m = (int) Math.min(block, n - done);
-            int[] rows = g.sampleVertexSequences(m);
-            for (int i = 0; i < m; i++) {
-                line.setLength(0);
-                for (int j = 0; j < L && rows[i * L + j] >= 0; j++) {
-                    if (j > 0)
-                        line.append(' ');
-                    if (positionPrefix)
-                        line.append(j).append('-');
-                    line.append(g.nameOfDeviceId(rows[i * L + j]));
-                }
-                out.write(line.append('\n').toString());
+        if (n <= 0) {
+            try {
+                new FileWriter(path).close();
+            } catch (IOException e) {
+                e.printStackTrace();
             }
+        }
+        for (long done = 0; done < n; done += block) {
+            long m = Math.min(block, n - done);
+            g.sampleVertexSequencesToSeq(m, path, positionPrefix, done > 0);
             if ((done + m) / tenth != done / tenth)
                 System.out.format("%d%% finished\n", Math.min(100, (done + m) * 100 / n));
         }

@@ -247,6 +247,22 @@ public class LayeredGraph {
         return out;
     }
 
+    /**
+     * The writer loops' form: the n walks sampleVertexSequences(n) would return, written as .seq lines into path by the device — the walks never come to
+     * the host (NativeEngine.sampleWalksToSeq).  rnd is advanced the same way; append = false creates or truncates the file.
+     */
+    void sampleVertexSequencesToSeq(long n, String path, boolean positionPrefix, boolean append) {
+        if (!aliasBuilt)
+            throw new IllegalStateException("call initiateAliasTables() first (J/LayeredGraph.java:195)");
+        String[] names = new String[byId.length + extraNames.size()];
+        for (int v = 0; v < names.length; v++)
+            names[v] = nameOfDeviceId(v);
+        long state = currentState();
+        long draws = NativeEngine.sampleWalksToSeq(handle, n, numLayer, state ^ JavaRandomState.MULT, 0, 0, names, positionPrefix, path, append);
+        rnd.setSeed(JavaRandomState.jump(state, 2 * draws) ^ JavaRandomState.MULT);
+        cachePos = cacheRows = 0;
+    }
+
     /** name of a device vertex id as returned by sampleVertexSequences */
     public String nameOfDeviceId(int id) {
         return id < byId.length && byId[id] != null ? byId[id].name : extraNames.get(id - byId.length);

@@ -30,6 +30,13 @@ final class NativeEngine {
     static native int graphSampleNext(long g, int v, double x);                          // dge_graph_sample_next
     /** rngMode 0: the java.util.Random(seed) stream continued at firstIndex draws; returns the draws this call consumed */
     static native long sampleWalks(long g, long nWalks, int maxLen, long seed, int rngMode, long firstIndex, int[] out);
+    /**
+     * The walks of sampleWalks, sampled into a corpus that stays on the device and written from there as .seq lines into path — one line per walk, the names
+     * of its vertices joined by blanks, token j as "j-name" with positionPrefix (dge_sample_walks_device, dge_walks_write_seq).  names[v] is the name of
+     * device vertex id v; append = false creates or truncates the file.  Returns the draws this call consumed.
+     */
+    static native long sampleWalksToSeq(long g, long nWalks, int maxLen, long seed, int rngMode, long firstIndex, String[] names, boolean positionPrefix,
+                                        String path, boolean append);
     /** w2v.fit(): returns a model handle (dge_train_sgns) */
     static native long trainSgns(int device, int[] walks, long nWalks, int maxLen, int dim, int window, int negative,
                                  int minCount, int epochs, int workers, float alpha, float minAlpha, long seed, int nVertices,

@@ -1,8 +1,5 @@
 package embedding;
 
-import java.io.BufferedWriter;
-import java.io.FileWriter;
-import java.io.IOException;
 import java.util.ArrayList;
 import java.util.LinkedList;
 import java.util.List;
@@ -109,8 +106,8 @@ public class SpatialGraph extends LayeredGraph {
 
     /**
      * J/SpatialGraph.java:91-121: numSamples walks into ../miscs/&lt;Year&gt;/deepwalkseq-&lt;level&gt;/taxi-spatial.seq, token j of a walk
-     * written as "j-name" (:105-108) so that spatial walks land in the cross-time vocabulary.  Walks come from the device in
-     * blocks (sampleVertexSequences); the lines are those the reference's loop over sampleVertexSequence() writes.
+     * written as "j-name" (:105-108) so that spatial walks land in the cross-time vocabulary.  Walks are sampled and
+     * formatted on the device in blocks (sampleVertexSequencesToSeq); the lines are those the reference's loop over sampleVertexSequence() writes.
      */
     public static void outputSampleSequence(String regionLevel) {
         LayeredGraph.numLayer = SpatialGraph.numLayer;
@@ -118,9 +115,9 @@ public class SpatialGraph extends LayeredGraph {
         long t2 = System.currentTimeMillis();
         System.out.println("Starting sequence sampling...");
         String path = String.format("../miscs/%d/deepwalkseq-%s/taxi-spatial.seq", DeepWalk.Year, regionLevel);
-        try (BufferedWriter fout = new BufferedWriter(new FileWriter(path))) {
-            CrossTimeGraph.writeWalks(g, fout, numSamples, true);
-        } catch (IOException e) {
+        try {
+            CrossTimeGraph.writeWalks(g, path, numSamples, true);
+        } catch (RuntimeException e) {
             e.printStackTrace();
         }
         System.out.format("Sampling %d sequences finished in %d seconds.\n", numSamples, (System.currentTimeMillis() - t2) / 1000);

@@ -88,6 +88,22 @@ JNIEXPORT jlong JNICALL J(sampleWalks)(JNIEnv* e, jclass, jlong g, jlong n, jint
     int rc = dge_sample_walks((dge_graph*)g, n, L, seed, mode, first, (int32_t*)p, &draws);
     e->ReleaseIntArrayElements(out, p, 0); fail(e, rc); return draws;
 }
+JNIEXPORT jlong JNICALL J(sampleWalksToSeq)(JNIEnv* e, jclass, jlong g, jlong n, jint L, jlong seed, jint mode, jlong first, jobjectArray names, jboolean prefix, jstring path,
+                                            jboolean append) {
+    jsize nn = e->GetArrayLength(names); std::vector<const char*> c(nn); std::vector<jstring> js(nn);
+    for (jsize i = 0; i < nn; i++) { js[i] = (jstring)e->GetObjectArrayElement(names, i); c[i] = e->GetStringUTFChars(js[i], nullptr); }
+    const char* p = e->GetStringUTFChars(path, nullptr);
+    dge_names* dn = nullptr; dge_walks* w = nullptr; int64_t draws = 0;
+    int rc = dge_names_create(&dn);
+    if (!rc) rc = dge_names_add(dn, c.data(), nn);
+    if (!rc) rc = dge_sample_walks_device((dge_graph*)g, n, L, seed, mode, first, &w, &draws);
+    if (!rc) rc = dge_walks_write_seq(w, 0, n, dn, prefix ? 1 : 0, p, append ? 1 : 0, nullptr);
+    if (w) dge_walks_free(w);
+    dge_names_free(dn);
+    e->ReleaseStringUTFChars(path, p);
+    for (jsize i = 0; i < nn; i++) e->ReleaseStringUTFChars(js[i], c[i]);
+    fail(e, rc); return draws;
+}
 JNIEXPORT jlong JNICALL J(trainSgns)(JNIEnv* e, jclass, jint device, jintArray walks, jlong n, jint L, jint dim, jint window, jint negative,
                                      jint minCount, jint epochs, jint workers, jfloat alpha, jfloat minAlpha, jlong seed, jint nVertices,
                                      jboolean useHierarchicSoftmax) {
