@@ -48,6 +48,13 @@ class SeqOutInfo(C.Structure):
                 ("write_ms", C.c_double)]
 
 
+class VecInfo(C.Structure):
+    """struct dge_vec_info (include/dge.h) — what dge_vectors_from_vec_text / dge_vectors_from_vec_files report."""
+    _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("rows", C.c_int64), ("values", C.c_int64), ("dropped", C.c_int64), ("missing", C.c_int64),
+                ("names_added", C.c_int64), ("host_values", C.c_int64), ("dim", C.c_int32), ("reserved", C.c_int32), ("read_ms", C.c_double),
+                ("kernel_ms", C.c_double)]
+
+
 # every symbol include/dge.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int
 _P = C.POINTER
@@ -140,6 +147,15 @@ SIGNATURES = {
     "dge_get_tuning": (_int, [_i32, _vp]),
     "dge_ndcg_at_k": (_int, [_int, _vp, _i32, _vp, _i32, _i32, _i32, _P(_dbl), _P(_dbl)]),
     "dge_knn_cosine": (_int, [_int, _vp, _i32, _i32, _i32, _vp, _vp, _P(_dbl)]),
+    "dge_vectors_from_vec_text": (_int, [_int, _vp, _i64, _int, _vp, _int, _P(_vp), _P(VecInfo)]),
+    "dge_vectors_from_vec_files": (_int, [_int, _vp, _i32, _int, _vp, _int, _P(_vp), _P(VecInfo)]),
+    "dge_vectors_from_host": (_int, [_int, _vp, _i64, _i32, _vp, _P(_vp)]),
+    "dge_vectors_info": (_int, [_vp, _P(_i64), _P(_i32), _P(_vp), _P(_vp)]),
+    "dge_vectors_to_host": (_int, [_vp, _vp, _vp, _i64]),
+    "dge_vectors_free": (None, [_vp]),
+    "dge_model_load_vectors": (_int, [_vp, _vp, _P(_i64)]),
+    "dge_knn_cosine_vectors": (_int, [_vp, _i32, _vp, _vp, _P(_dbl)]),
+    "dge_ndcg_at_k_vectors": (_int, [_vp, _vp, _i32, _P(_dbl), _P(_dbl)]),
     "dge_selftest_locked_rows": (_int, [_int, _i32, _i64, _i32, C.c_uint64, _i32, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave": (_int, [_int, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),

@@ -127,6 +127,16 @@ struct dge_names {
     size_t indexed = 0;
 };
 
+// resident float32 [rows x dim], row-major, and one present byte per row: vec_read.hip makes it, sgns_io.hip (dge_model_load_vectors) and knn.hip read it
+struct dge_vectors {
+    int device = 0;
+    int64_t rows = 0;
+    int32_t dim = 0;
+    float* d = nullptr;
+    uint8_t* d_present = nullptr;
+    int64_t n_present = 0;
+};
+
 int dge_graph_ensure_csr(dge_graph* g);
 // launches the strided walk kernel on `stream`; rows [row0,row0+n) of out (row length L)
 int dge_launch_walks_strided(const dge_graph* g, hipStream_t stream, int32_t* d_out, int64_t n, int32_t L,

@@ -230,22 +230,16 @@ __global__ void k_ndcg(const float* __restrict__ gn, const float* __restrict__ g
     if (lane == 0) ratio[r] = dmax != 0.0 ? dcg / dmax : 0.0;
 }
 
-extern "C" int dge_ndcg_at_k(int device, const float* features, int32_t dim, const float* gnd_features, int32_t gnd_dim, int32_t n, int32_t k,
-                             double* ndcg, double* ms_kernels) {
-    if (!features || !gnd_features || !ndcg || n <= 1 || dim <= 0 || gnd_dim <= 0 || k <= 0) DGE_FAIL(DGE_ERR_ARG, "dge_ndcg_at_k: bad argument");
-    if (k > KNN_MAX_K || k > n - 1) DGE_FAIL(DGE_ERR_ARG, "dge_ndcg_at_k: k = %d must be <= %d and < n", k, KNN_MAX_K);
-    if (dim > KNN_MAX_D || gnd_dim > KNN_MAX_D) DGE_FAIL(DGE_ERR_ARG, "dge_ndcg_at_k: dim exceeds %d", KNN_MAX_D);
-    int rc = dge_require_device(device);
-    if (rc) return rc;
-    dge_tmp<float> d_x, d_g, d_inv, d_ginv, d_xn, d_gn, d_od, d_god; dge_tmp<int32_t> d_oi, d_goi; dge_tmp<double> d_ratio;
-    if ((rc = d_x.alloc((size_t)n * dim)) || (rc = d_g.alloc((size_t)n * gnd_dim)) || (rc = d_inv.alloc(n)) || (rc = d_ginv.alloc(n)) ||
+// device form: both feature arrays in device memory
+static int ndcg_device(const float* d_x, int32_t dim, const float* d_g, int32_t gnd_dim, int32_t n, int32_t k, double* ndcg, double* ms_kernels) {
+    int rc;
+    dge_tmp<float> d_inv, d_ginv, d_xn, d_gn, d_od, d_god; dge_tmp<int32_t> d_oi, d_goi; dge_tmp<double> d_ratio;
+    if ((rc = d_inv.alloc(n)) || (rc = d_ginv.alloc(n)) ||
         (rc = d_xn.alloc((size_t)n * 256)) || (rc = d_gn.alloc((size_t)n * 256)) || (rc = d_od.alloc((size_t)n * k)) || (rc = d_god.alloc((size_t)n * k)) ||
         (rc = d_oi.alloc((size_t)n * k)) || (rc = d_goi.alloc((size_t)n * k)) || (rc = d_ratio.alloc(n))) return rc;
-    DGE_HIP(hipMemcpy(d_x.p, features, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice));
-    DGE_HIP(hipMemcpy(d_g.p, gnd_features, (size_t)n * gnd_dim * sizeof(float), hipMemcpyHostToDevice));
     double ms1 = 0, ms2 = 0;
-    if ((rc = knn_device(d_x.p, n, dim, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, &ms1))) return rc;
-    if ((rc = knn_device(d_g.p, n, gnd_dim, k, d_ginv.p, d_gn.p, d_goi.p, d_god.p, &ms2))) return rc;
+    if ((rc = knn_device(d_x, n, dim, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, &ms1))) return rc;
+    if ((rc = knn_device(d_g, n, gnd_dim, k, d_ginv.p, d_gn.p, d_goi.p, d_god.p, &ms2))) return rc;
     const int gdh = (gnd_dim + 1) / 2 <= 16 ? 16 : ((gnd_dim + 1) / 2 <= 32 ? 32 : ((gnd_dim + 1) / 2 <= 64 ? 64 : 128));
     hipLaunchKernelGGL(k_ndcg, dim3((n + 3) / 4), dim3(256), 0, 0, d_gn.p, d_ginv.p, 2 * gdh, n, k, d_oi.p, d_god.p, d_ratio.p);
     DGE_HIP(hipGetLastError());
@@ -256,4 +250,54 @@ extern "C" int dge_ndcg_at_k(int device, const float* features, int32_t dim, con
     *ndcg = s / (double)n;
     if (ms_kernels) *ms_kernels = ms1 + ms2;
     return DGE_OK;
+}
+
+static int ndcg_args(const char* who, int32_t n, int32_t dim, int32_t gnd_dim, int32_t k) {
+    if (n <= 1 || dim <= 0 || gnd_dim <= 0 || k <= 0) DGE_FAIL(DGE_ERR_ARG, "%s: bad argument", who);
+    if (k > KNN_MAX_K || k > n - 1) DGE_FAIL(DGE_ERR_ARG, "%s: k = %d must be <= %d and < n", who, k, KNN_MAX_K);
+    if (dim > KNN_MAX_D || gnd_dim > KNN_MAX_D) DGE_FAIL(DGE_ERR_ARG, "%s: dim exceeds %d", who, KNN_MAX_D);
+    return DGE_OK;
+}
+
+extern "C" int dge_ndcg_at_k(int device, const float* features, int32_t dim, const float* gnd_features, int32_t gnd_dim, int32_t n, int32_t k,
+                             double* ndcg, double* ms_kernels) {
+    if (!features || !gnd_features || !ndcg) DGE_FAIL(DGE_ERR_ARG, "dge_ndcg_at_k: bad argument");
+    int rc = ndcg_args("dge_ndcg_at_k", n, dim, gnd_dim, k);
+    if (rc) return rc;
+    if ((rc = dge_require_device(device))) return rc;
+    dge_tmp<float> d_x, d_g;
+    if ((rc = d_x.alloc((size_t)n * dim)) || (rc = d_g.alloc((size_t)n * gnd_dim))) return rc;
+    DGE_HIP(hipMemcpy(d_x.p, features, (size_t)n * dim * sizeof(float), hipMemcpyHostToDevice));
+    DGE_HIP(hipMemcpy(d_g.p, gnd_features, (size_t)n * gnd_dim * sizeof(float), hipMemcpyHostToDevice));
+    return ndcg_device(d_x.p, dim, d_g.p, gnd_dim, n, k, ndcg, ms_kernels);
+}
+
+// ---- the same two entries on resident rows (dge_vectors: vec_read.hip): the kernels above on the pointer the handle holds, no host round trip of the features
+extern "C" int dge_knn_cosine_vectors(const dge_vectors* v, int32_t k, int32_t* out_idx, float* out_dist, double* ms_kernel) {
+    if (!v || !out_idx || !out_dist || k <= 0) DGE_FAIL(DGE_ERR_ARG, "dge_knn_cosine_vectors: null or negative argument");
+    if (v->rows <= 0 || v->rows > 0x7fffffffLL || v->dim <= 0) DGE_FAIL(DGE_ERR_ARG, "dge_knn_cosine_vectors: %lld rows of dim %d", (long long)v->rows, v->dim);
+    if (k > KNN_MAX_K) DGE_FAIL(DGE_ERR_ARG, "dge_knn_cosine_vectors: k = %d exceeds %d", k, KNN_MAX_K);
+    if (v->dim > KNN_MAX_D) DGE_FAIL(DGE_ERR_ARG, "dge_knn_cosine_vectors: dim = %d exceeds %d", v->dim, KNN_MAX_D);
+    int rc = dge_require_device(v->device);
+    if (rc) return rc;
+    const int n = (int)v->rows;
+    dge_tmp<float> d_inv, d_od, d_xn; dge_tmp<int32_t> d_oi;
+    if ((rc = d_xn.alloc((size_t)n * 256)) || (rc = d_inv.alloc((size_t)n)) || (rc = d_od.alloc((size_t)n * k)) || (rc = d_oi.alloc((size_t)n * k))) return rc;
+    if ((rc = knn_device(v->d, n, v->dim, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, ms_kernel))) return rc;
+    DGE_HIP(hipMemcpy(out_idx, d_oi.p, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    DGE_HIP(hipMemcpy(out_dist, d_od.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost));
+    return DGE_OK;
+}
+
+extern "C" int dge_ndcg_at_k_vectors(const dge_vectors* f, const dge_vectors* gnd, int32_t k, double* ndcg, double* ms_kernels) {
+    if (!f || !gnd || !ndcg) DGE_FAIL(DGE_ERR_ARG, "dge_ndcg_at_k_vectors: null argument");
+    if (f->rows != gnd->rows || f->rows > 0x7fffffffLL) DGE_FAIL(DGE_ERR_ARG, "dge_ndcg_at_k_vectors: %lld rows against %lld: the rows of the two must be the same regions", (long long)f->rows, (long long)gnd->rows);
+    if (f->n_present != f->rows || gnd->n_present != gnd->rows)
+        DGE_FAIL(DGE_ERR_ARG, "dge_ndcg_at_k_vectors: %lld rows of the features and %lld of the ground features are absent: every row must be present in both",
+                 (long long)(f->rows - f->n_present), (long long)(gnd->rows - gnd->n_present));
+    if (f->device != gnd->device) DGE_FAIL(DGE_ERR_ARG, "dge_ndcg_at_k_vectors: the two are on devices %d and %d", f->device, gnd->device);
+    int rc = ndcg_args("dge_ndcg_at_k_vectors", (int32_t)f->rows, f->dim, gnd->dim, k);
+    if (rc) return rc;
+    if ((rc = dge_require_device(f->device))) return rc;
+    return ndcg_device(f->d, f->dim, gnd->d, gnd->dim, (int32_t)f->rows, k, ndcg, ms_kernels);
 }

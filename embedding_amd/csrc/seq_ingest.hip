@@ -4,64 +4,15 @@
 // names joined by blanks.  Tokenising, interning and packing run here on the device; the host only moves bytes.  This translation unit is outside the
 // build stamp: nothing in it is read or written by a training launch.
 //
-// One buffer holds everything the kernels read (seq_plan.h: seq_layout): the names the caller's dge_names already holds, one per line, then every file
-// (or the caller's text) with one pad byte behind it, then blanks up to whole chunks.  The prior names are thereby the first tokens of the buffer and take
-// ids 0 .. n-1 under the same first-appearance rule as every other name.  All offsets and token indices are 64-bit.
-//
-//   k_seq_count / k_seq_emit   per byte: "a token starts here", "newline"; two passes around a scan of the per-chunk counts give token t its first byte
-//                              and its line
-//   k_seq_hash                 token t's length and a 64-bit hash of its bytes
-//   rows                       a scan of "t is the first token of its line" numbers the rows; row_first[r] gives a token its position in the row
-//   k_seq_intern               open addressing, one 8-byte slot per string = the SMALLEST token index seen with that string (its first appearance)
-//   ids                        a scan of "t is its string's first appearance" numbers the names in first-appearance order; id[t] = number of its string
-//   k_seq_pack / k_seq_name_*  ids into int32 [rows x max_len] padded with -1; the new names' bytes into one blob for the host
-//
-// Why the intern pass is right on eight L2s that are not coherent.  A slot's history is EMPTY -> t1 -> t2 < t1 -> ..., every ti a
-// token of ONE string: a slot is claimed once (compare-and-swap from EMPTY) and afterwards only lowered (atomicMin) by tokens that compared equal to
-// the token it held.  Both are agent-scope read-modify-writes and execute at memory, on the slot's true value.  The READ in front of them may return any
-// earlier value of that history:
-//   * EMPTY although the slot is taken: the compare-and-swap fails and returns the true value, and the token goes on with that — one atomic more.
-//   * a token index v of the slot's string that has been lowered since: the byte comparison has the same outcome as against the present value (same
-//     string); if v > t the token issues an atomicMin that may no longer be needed — one atomic more; if v < t the true value is lower still and
-//     skipping the atomic is right.
-// A string never sits in two slots: a token that passed a slot saw a token of ANOTHER string there (true or stale, the slot's string is fixed) or failed
-// its claim against one.  So after the kernel every slot holds the least token index of its string whatever the timing; which slot a string got does
-// depend on timing, and nothing below reads it other than through the token indices.  The bytes, starts, lengths and hashes the pass compares were
-// written by earlier kernels and are only read here.
-// Contention: a token that reads its string in the slot with a first appearance below its own index issues no atomic at all — on a corpus of few names
-// that is nearly every token (atomics on one address complete one after the other).
-#include <errno.h>
-#include <fcntl.h>
-#include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <chrono>
-#include <hipcub/hipcub.hpp>
-#include <memory>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
-#include <string_view>
+// The tokeniser, the name table (with the argument for it on eight L2s that are not coherent) and the byte transport are in seq_tokens.h, which the .vec
+// reader (vec_read.hip) includes too; what is here is the names object, the packing of ids into corpus rows and the entries.
 #include <unordered_set>
 
-#include "dge_algos.h"
-#include "dge_internal.h"
-#include "seq_plan.h"
+#include "seq_tokens.h"
 
 // ------------------------------------------------------------------------------------------ dge_names: a host object, no device involved (the struct: dge_internal.h)
 static void names_index(dge_names* n) {
     for (; n->indexed < n->ptr.size(); n->indexed++) n->index.emplace(n->ptr[n->indexed], (size_t)n->len[n->indexed]);
-}
-
-// blob: count strings, string k at blob + off[k], NUL-terminated; takes the blob over
-static void names_append(dge_names* n, std::unique_ptr<char[]> blob, const int64_t* off, int64_t count) {
-    for (int64_t k = 0; k < count; k++) {
-        n->ptr.push_back(blob.get() + off[k]);
-        n->len.push_back(off[k + 1] - off[k] - 1);
-        n->bytes += off[k + 1] - off[k] - 1;
-    }
-    n->blobs.push_back(std::move(blob));
 }
 
 extern "C" int dge_names_create(dge_names** out) {
@@ -106,180 +57,6 @@ extern "C" int dge_names_cstrs(const dge_names* n, const char* const** strs) {
     return DGE_OK;
 }
 
-// ------------------------------------------------------------------------------------------ kernels
-constexpr int SEQ_BLOCK = 256;
-constexpr unsigned long long SEQ_EMPTY = ~0ull;
-constexpr int SEQ_SHARDS = 256;          // counters of claimed slots, one 128-byte line each
-constexpr int SEQ_SHARD_STRIDE = 16;     // in 8-byte words
-
-// 32 bytes of one lane: bit i of starts = a token starts at base + i (not whitespace, behind whitespace or the buffer's start)
-__device__ __forceinline__ void seq_masks(const uint8_t* buf, int64_t base, uint32_t& starts, uint32_t& nls, uint32_t& nuls) {
-    const uint4 a = *reinterpret_cast<const uint4*>(buf + base), b = *reinterpret_cast<const uint4*>(buf + base + 16);
-    const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    bool prev_ws = base == 0 ? true : seq_is_space(buf[base - 1]);
-    starts = nls = nuls = 0;
-#pragma unroll
-    for (int i = 0; i < 32; i++) {
-        const uint32_t c = (w[i >> 2] >> (8 * (i & 3))) & 0xffu;
-        const bool ws = seq_is_space(c);
-        starts |= (uint32_t)(!ws && prev_ws) << i;
-        nls |= (uint32_t)(c == 10u) << i;
-        nuls |= (uint32_t)(c == 0u) << i;
-        prev_ws = ws;
-    }
-}
-
-// per chunk: token starts (low word) and newlines (high word); the first NUL byte of the buffer
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_count(const uint8_t* buf, int64_t used, int64_t* chunk_tok, int64_t* chunk_nl, unsigned long long* nul_at) {
-    typedef hipcub::BlockReduce<unsigned long long, SEQ_BLOCK> Reduce;
-    __shared__ typename Reduce::TempStorage tmp;
-    const int64_t base = (int64_t)blockIdx.x * SEQ_CHUNK + (int64_t)threadIdx.x * 32;
-    uint32_t starts, nls, nuls;
-    seq_masks(buf, base, starts, nls, nuls);
-    if (nuls) {
-        const int64_t at = base + (__ffs(nuls) - 1);
-        if (at < used) atomicMin(nul_at, (unsigned long long)at);
-    }
-    const unsigned long long sum = Reduce(tmp).Sum((unsigned long long)__popc(starts) | ((unsigned long long)__popc(nls) << 32));
-    if (threadIdx.x == 0) { chunk_tok[blockIdx.x] = (int64_t)(sum & 0xffffffffull); chunk_nl[blockIdx.x] = (int64_t)(sum >> 32); }
-}
-
-// token t (numbered in byte order through the scanned chunk counts): its first byte and the number of newlines in front of it
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_emit(const uint8_t* buf, const int64_t* chunk_tokx, const int64_t* chunk_nlx, int64_t* tok_start, int64_t* tok_line) {
-    typedef hipcub::BlockScan<unsigned long long, SEQ_BLOCK> Scan;
-    __shared__ typename Scan::TempStorage tmp;
-    const int64_t base = (int64_t)blockIdx.x * SEQ_CHUNK + (int64_t)threadIdx.x * 32;
-    uint32_t starts, nls, nuls;
-    seq_masks(buf, base, starts, nls, nuls);
-    unsigned long long before;
-    Scan(tmp).ExclusiveSum((unsigned long long)__popc(starts) | ((unsigned long long)__popc(nls) << 32), before);
-    int64_t t = chunk_tokx[blockIdx.x] + (int64_t)(before & 0xffffffffull);
-    const int64_t line0 = chunk_nlx[blockIdx.x] + (int64_t)(before >> 32);
-    while (starts) {
-        const int i = __ffs(starts) - 1;
-        starts &= starts - 1;
-        tok_start[t] = base + i;
-        tok_line[t] = line0 + __popc(nls & ((1u << i) - 1u));
-        t++;
-    }
-}
-
-__device__ __forceinline__ uint64_t seq_ld8(const uint8_t* p) { uint64_t w; __builtin_memcpy(&w, p, 8); return w; }
-// how many of the word's 8 bytes (lowest first) are token material before the first whitespace byte
-__device__ __forceinline__ int seq_run(uint64_t w) {
-    int n = 8;
-#pragma unroll
-    for (int i = 7; i >= 0; i--) if (seq_is_space((uint32_t)(w >> (8 * i)) & 0xffu)) n = i;
-    return n;
-}
-__device__ __forceinline__ uint64_t seq_keep(uint64_t w, int n) { return n >= 8 ? w : (n == 0 ? 0ull : (w & (~0ull >> (64 - 8 * n)))); }
-
-// The buffer ends in SEQ_TAIL blanks: the 8-byte reads stop at a whitespace byte inside the allocation.
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_hash(const uint8_t* buf, const int64_t* tok_start, int64_t T, int32_t hash_bits, int64_t* tok_len, uint64_t* tok_hash) {
-    const int64_t t = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (t >= T) return;
-    const uint8_t* p = buf + tok_start[t];
-    uint64_t h = 0x9E3779B97F4A7C15ull;
-    int64_t len = 0;
-    for (;;) {
-        const uint64_t w = seq_ld8(p + len);
-        const int n = seq_run(w);
-        h = (h ^ seq_keep(w, n)) * 0xFF51AFD7ED558CCDull;
-        h ^= h >> 32;
-        len += n;
-        if (n < 8) break;
-    }
-    h = dge_mix64(h ^ (uint64_t)len);
-    if (hash_bits < 64) h &= (1ull << hash_bits) - 1ull;
-    tok_len[t] = len;
-    tok_hash[t] = h;
-}
-
-__device__ __forceinline__ bool seq_same_bytes(const uint8_t* a, const uint8_t* b, int64_t len) {
-    for (int64_t k = 0; k < len; k += 8) {
-        const int n = len - k >= 8 ? 8 : (int)(len - k);
-        if (seq_keep(seq_ld8(a + k), n) != seq_keep(seq_ld8(b + k), n)) return false;
-    }
-    return true;
-}
-
-// the argument for this kernel is at the head of the file
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_intern(const uint8_t* buf, const int64_t* tok_start, const int64_t* tok_len, const uint64_t* tok_hash, int64_t T,
-                                                          unsigned long long* table, int64_t mask, int64_t* tok_slot, unsigned long long* claims,
-                                                          unsigned long long claim_limit, int* give_up) {
-    const int64_t t = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (t >= T) return;
-    if (__hip_atomic_load(give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;       // a stale 0 only costs this token's work
-    const uint64_t h = tok_hash[t];
-    const int64_t len = tok_len[t];
-    const uint8_t* mine = buf + tok_start[t];
-    int64_t s = (int64_t)(h & (uint64_t)mask);
-    for (int64_t probes = 0; probes <= mask; probes++, s = (s + 1) & mask) {
-        unsigned long long cur = __hip_atomic_load(table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == SEQ_EMPTY) {
-            cur = atomicCAS(table + s, SEQ_EMPTY, (unsigned long long)t);
-            if (cur == SEQ_EMPTY) {
-                tok_slot[t] = s;
-                const unsigned long long had = atomicAdd(claims + (blockIdx.x % SEQ_SHARDS) * SEQ_SHARD_STRIDE, 1ull);
-                if (had >= claim_limit) __hip_atomic_store(give_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // more than half full: redo with more slots
-                return;
-            }
-        }
-        if (tok_hash[cur] == h && tok_len[cur] == len && seq_same_bytes(buf + tok_start[cur], mine, len)) {
-            if (cur > (unsigned long long)t) atomicMin(table + s, (unsigned long long)t);
-            tok_slot[t] = s;
-            return;
-        }
-    }
-    __hip_atomic_store(give_up, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);               // came round: the table is full
-}
-
-struct SeqRowFlag {      // token t opens a row: the first text token of its line (the prior names in front open none)
-    const int64_t* line; int64_t P, T;
-    __device__ int64_t operator()(int64_t t) const { return (t >= P && t < T && (t == P || line[t - 1] != line[t])) ? 1 : 0; }
-};
-struct SeqFirstFlag {    // token t is the first appearance of its string
-    const unsigned long long* table; const int64_t* slot; int64_t T;
-    __device__ int64_t operator()(int64_t t) const { return (t < T && table[slot[t]] == (unsigned long long)t) ? 1 : 0; }
-};
-struct SeqNameLen {      // bytes of new name k in the blob, its NUL included
-    const int64_t* name_tok; const int64_t* tok_len; int64_t n;
-    __device__ int64_t operator()(int64_t k) const { return k < n ? tok_len[name_tok[k]] + 1 : 0; }
-};
-
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_row_first(const int64_t* rowx, int64_t P, int64_t T, int64_t* row_first) {
-    const int64_t t = P + (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (t >= T) return;
-    if (rowx[t + 1] != rowx[t]) row_first[rowx[t]] = t;
-    if (t == T - 1) row_first[rowx[T]] = T;
-}
-
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_max_len(const int64_t* row_first, int64_t rows, unsigned long long* max_len) {
-    typedef hipcub::BlockReduce<unsigned long long, SEQ_BLOCK> Reduce;
-    __shared__ typename Reduce::TempStorage tmp;
-    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    const unsigned long long mine = r < rows ? (unsigned long long)(row_first[r + 1] - row_first[r]) : 0ull;
-    const unsigned long long m = Reduce(tmp).Reduce(mine, hipcub::Max());
-    if (threadIdx.x == 0) atomicMax(max_len, m);
-}
-
-// id of token t = the number of its string among the first appearances; with intern == 0 a string that first appears behind the prior names is unknown
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_ids(const unsigned long long* table, const int64_t* tok_slot, const int64_t* namex, int64_t P, int64_t T, int intern,
-                                                       int32_t* tok_id, unsigned long long* unknown) {
-    typedef hipcub::BlockReduce<unsigned long long, SEQ_BLOCK> Reduce;
-    __shared__ typename Reduce::TempStorage tmp;
-    const int64_t t = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    unsigned long long u = 0;
-    if (t < T) {
-        const int64_t rep = (int64_t)table[tok_slot[t]];
-        const bool unk = !intern && rep >= P;
-        tok_id[t] = unk ? -1 : (int32_t)namex[rep];
-        u = (unk && t >= P) ? 1ull : 0ull;
-    }
-    const unsigned long long sum = Reduce(tmp).Sum(u);
-    if (threadIdx.x == 0 && sum) atomicAdd(unknown, sum);
-}
-
 __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_pack(const int32_t* tok_id, const int64_t* rowx, const int64_t* row_first, int64_t P, int64_t T, int64_t max_len, int32_t* out) {
     const int64_t t = P + (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
     if (t >= T) return;
@@ -287,288 +64,12 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_pack(const int32_t* tok_id, c
     out[r * max_len + (t - row_first[r])] = tok_id[t];
 }
 
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_name_tok(const int64_t* namex, int64_t P, int64_t T, int64_t* name_tok) {
-    const int64_t t = P + (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (t >= T) return;
-    if (namex[t + 1] != namex[t]) name_tok[namex[t] - P] = t;
-}
-
-__global__ void __launch_bounds__(SEQ_BLOCK) k_seq_name_bytes(const uint8_t* buf, const int64_t* tok_start, const int64_t* tok_len, const int64_t* name_tok, const int64_t* name_off,
-                                                              int64_t n, uint8_t* blob) {
-    const int64_t k = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (k >= n) return;
-    const int64_t t = name_tok[k], len = tok_len[t];
-    const uint8_t* src = buf + tok_start[t];
-    uint8_t* dst = blob + name_off[k];
-    for (int64_t i = 0; i < len; i++) dst[i] = src[i];
-    dst[len] = 0;
-}
-
-// ------------------------------------------------------------------------------------------ host side of one ingest
 namespace {
 
-struct SeqPiece { const char* path = nullptr; const uint8_t* mem = nullptr; int fd = -1; int64_t size = 0; };
-
-struct SeqRun {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ka = nullptr, kb = nullptr, copied[2] = {nullptr, nullptr};
-    uint8_t* pin[2] = {nullptr, nullptr};
-    std::vector<SeqPiece> pieces;
-    seq_layout L;
-    int64_t held = 0;                 // device bytes this call holds (for DGE_ERR_CAP's message)
-    double read_ms = 0, kernel_ms = 0;
-    // device results
-    dge_tmp<uint8_t> buf;
-    dge_tmp<int64_t> tok_start, tok_len, tok_slot, rowx, row_first, namex;
-    dge_tmp<uint64_t> tok_hash;
-    dge_tmp<unsigned long long> table;
-    dge_tmp<int32_t> tok_id;
-    int64_t P = 0, T = 0, lines = 0, rows = 0, max_len = 1, n_names = 0, unknown = 0;
-    ~SeqRun() {
-        for (SeqPiece& p : pieces) if (p.fd >= 0) close(p.fd);
-        for (int i = 0; i < 2; i++) { if (pin[i]) (void)hipHostFree(pin[i]); if (copied[i]) (void)hipEventDestroy(copied[i]); }
-        if (ka) (void)hipEventDestroy(ka);
-        if (kb) (void)hipEventDestroy(kb);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-template <typename T>
-int seq_alloc(SeqRun& R, dge_tmp<T>& t, int64_t n, const char* what) {
-    if (t.p) { (void)hipFree(t.p); t.p = nullptr; }
-    const size_t bytes = (size_t)(n > 0 ? n : 1) * sizeof(T);
-    const hipError_t e = hipMalloc((void**)&t.p, bytes);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        t.p = nullptr;
-        DGE_FAIL(DGE_ERR_CAP, "seq ingest: the working set does not fit in device memory: %lld bytes for %s on top of the %lld this call holds", (long long)bytes, what, (long long)R.held);
-    }
-    if (e != hipSuccess) { t.p = nullptr; DGE_FAIL(DGE_ERR_DEVICE, "seq ingest: hipMalloc of %lld bytes for %s failed: %s", (long long)bytes, what, hipGetErrorName(e)); }
-    R.held += (int64_t)bytes;
-    return DGE_OK;
-}
-template <typename T>
-void seq_release(SeqRun& R, dge_tmp<T>& t, int64_t n) { if (t.p) { (void)hipFree(t.p); t.p = nullptr; R.held -= (int64_t)((size_t)(n > 0 ? n : 1) * sizeof(T)); } }
-
-#define SEQ_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
-
-int seq_read_back(SeqRun& R, void* dst, const void* src, size_t bytes) {
-    DGE_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, R.stream));
-    DGE_HIP(hipStreamSynchronize(R.stream));
-    return DGE_OK;
-}
-int seq_kernels_begin(SeqRun& R) { DGE_HIP(hipEventRecord(R.ka, R.stream)); return DGE_OK; }
-int seq_kernels_end(SeqRun& R) {
-    DGE_HIP(hipEventRecord(R.kb, R.stream));
-    DGE_HIP(hipEventSynchronize(R.kb));
-    float ms = 0.f;
-    DGE_HIP(hipEventElapsedTime(&ms, R.ka, R.kb));
-    R.kernel_ms += ms;
-    return DGE_OK;
-}
-unsigned seq_grid(int64_t n) { return (unsigned)((n + SEQ_BLOCK - 1) / SEQ_BLOCK); }
-
-template <typename In>
-int seq_scan(SeqRun& R, In in, int64_t* out, int64_t n) {      // out[i] = sum of in[0 .. i), n entries
-    size_t bytes = 0;
-    DGE_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), R.stream));
-    dge_tmp<uint8_t> tmp;
-    SEQ_TRY(seq_alloc(R, tmp, (int64_t)bytes, "the scan's scratch"));
-    DGE_HIP(rocprim::exclusive_scan((void*)tmp.p, bytes, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), R.stream));
-    DGE_HIP(hipStreamSynchronize(R.stream));
-    seq_release(R, tmp, (int64_t)bytes);
-    return DGE_OK;
-}
-
-// The joined stream — prior names, then every piece with its pad byte — produced front to back into a pinned buffer.
-struct SeqJoiner {
-    SeqRun& R; const std::string& prefix;
-    int64_t in_prefix = 0; size_t k = 0; int64_t at = 0; uint8_t last = '\n';
-    int fill(uint8_t* dst, int64_t cap, int64_t* got) {
-        int64_t n = 0;
-        while (n < cap) {
-            if (in_prefix < (int64_t)prefix.size()) {
-                const int64_t m = std::min<int64_t>(cap - n, (int64_t)prefix.size() - in_prefix);
-                memcpy(dst + n, prefix.data() + in_prefix, (size_t)m);
-                in_prefix += m; n += m;
-                continue;
-            }
-            if (k >= R.pieces.size()) break;
-            SeqPiece& p = R.pieces[k];
-            if (at < p.size) {
-                int64_t m = std::min<int64_t>(cap - n, p.size - at);
-                if (p.mem) memcpy(dst + n, p.mem + at, (size_t)m);
-                else {
-                    const ssize_t r = read(p.fd, dst + n, (size_t)m);
-                    if (r < 0 && errno == EINTR) continue;
-                    if (r <= 0) DGE_FAIL(DGE_ERR_IO, "cannot read %s: %s after %lld of %lld bytes", p.path, r < 0 ? strerror(errno) : "the file ends", (long long)at, (long long)p.size);
-                    m = (int64_t)r;
-                }
-                last = dst[n + m - 1];
-                at += m; n += m;
-                continue;
-            }
-            dst[n++] = seq_pad_byte(p.size, last);
-            k++; at = 0; last = '\n';
-        }
-        *got = n;
-        return DGE_OK;
-    }
-};
-
-// buffer offset -> offset in the caller's text (the pieces taken one after the other, pads and prefix not counted) and the piece it lies in
-int64_t seq_text_offset(const SeqRun& R, int64_t at, size_t* piece) {
-    int64_t before = 0;
-    for (size_t k = 0; k < R.pieces.size(); k++) {
-        if (at < R.L.offset[k] + R.pieces[k].size + 1) { *piece = k; return before + (at - R.L.offset[k]); }
-        before += R.pieces[k].size;
-    }
-    *piece = 0;
-    return at;
-}
-
-struct SeqOptions { int32_t hash_bits = 64; int64_t initial_slots = 0; int intern = 1; };
-
-// everything up to the per-token ids; what leaves the device is up to the caller
+// everything up to the per-token ids of a .seq text; what leaves the device is up to the caller
 int seq_ingest(SeqRun& R, const dge_names* names, const SeqOptions& opt, const char* who) {
-    using clock = std::chrono::steady_clock;
-    // ---- layout
-    std::string prefix;
-    if (names) {
-        prefix.reserve((size_t)(names->bytes + (int64_t)names->ptr.size()));
-        for (size_t i = 0; i < names->ptr.size(); i++) { prefix.append(names->ptr[i], (size_t)names->len[i]); prefix.push_back('\n'); }
-        R.P = (int64_t)names->ptr.size();
-    }
-    std::vector<int64_t> sizes;
-    for (const SeqPiece& p : R.pieces) sizes.push_back(p.size);
-    if (!seq_plan_layout((int64_t)prefix.size(), sizes.data(), (int64_t)sizes.size(), &R.L)) DGE_FAIL(DGE_ERR_ARG, "%s: the text's size leaves 64 bits", who);
-    DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-    DGE_HIP(hipEventCreate(&R.ka));
-    DGE_HIP(hipEventCreate(&R.kb));
-    // ---- bytes to the device: chunk c + 1 is read (or copied out of the caller's memory) into one pinned buffer while chunk c leaves the other
-    const auto t0 = clock::now();
-    SEQ_TRY(seq_alloc(R, R.buf, R.L.padded, "the text"));
-    {
-        const int64_t PIN = (int64_t)16 << 20;
-        const int64_t pin_bytes = std::min<int64_t>(PIN, std::max<int64_t>(R.L.used, 1));
-        for (int i = 0; i < 2; i++) {
-            DGE_HIP(hipHostMalloc((void**)&R.pin[i], (size_t)pin_bytes, hipHostMallocDefault));
-            DGE_HIP(hipEventCreateWithFlags(&R.copied[i], hipEventDisableTiming));
-        }
-        SeqJoiner join{R, prefix};
-        int64_t done = 0;
-        for (int64_t c = 0; done < R.L.used; c++) {
-            const int b = (int)(c & 1);
-            if (c >= 2) DGE_HIP(hipEventSynchronize(R.copied[b]));
-            int64_t got = 0;
-            SEQ_TRY(join.fill(R.pin[b], std::min<int64_t>(pin_bytes, R.L.used - done), &got));
-            if (got <= 0) DGE_FAIL(DGE_ERR_IO, "%s: the input ended %lld bytes short", who, (long long)(R.L.used - done));
-            DGE_HIP(hipMemcpyAsync(R.buf.p + done, R.pin[b], (size_t)got, hipMemcpyHostToDevice, R.stream));
-            DGE_HIP(hipEventRecord(R.copied[b], R.stream));
-            done += got;
-        }
-        DGE_HIP(hipMemsetAsync(R.buf.p + R.L.used, ' ', (size_t)(R.L.padded - R.L.used), R.stream));
-        DGE_HIP(hipStreamSynchronize(R.stream));
-    }
-    R.read_ms = std::chrono::duration<double, std::milli>(clock::now() - t0).count();
-
-    // ---- classify: token starts and newlines per chunk, scanned; a NUL byte ends the call
-    const int64_t n_chunks = (R.L.padded - SEQ_TAIL) / SEQ_CHUNK;
-    dge_tmp<int64_t> chunk_tok, chunk_nl, chunk_tokx, chunk_nlx, tok_line;
-    dge_tmp<unsigned long long> words;        // [0] first NUL, [1] longest row, [2] unknown tokens, [3] give_up (as int); then the claim counters
-    const int64_t n_words = 4 + (int64_t)SEQ_SHARDS * SEQ_SHARD_STRIDE;
-    SEQ_TRY(seq_alloc(R, chunk_tok, n_chunks + 1, "the chunk counts"));
-    SEQ_TRY(seq_alloc(R, chunk_nl, n_chunks + 1, "the chunk counts"));
-    SEQ_TRY(seq_alloc(R, chunk_tokx, n_chunks + 1, "the chunk counts"));
-    SEQ_TRY(seq_alloc(R, chunk_nlx, n_chunks + 1, "the chunk counts"));
-    SEQ_TRY(seq_alloc(R, words, n_words, "the counters"));
-    SEQ_TRY(seq_kernels_begin(R));
-    DGE_HIP(hipMemsetAsync(words.p, 0, (size_t)n_words * 8, R.stream));
-    DGE_HIP(hipMemsetAsync(words.p, 0xFF, 8, R.stream));
-    DGE_HIP(hipMemsetAsync(chunk_tok.p + n_chunks, 0, 8, R.stream));
-    DGE_HIP(hipMemsetAsync(chunk_nl.p + n_chunks, 0, 8, R.stream));
-    if (n_chunks) hipLaunchKernelGGL(k_seq_count, dim3((unsigned)n_chunks), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.L.used, chunk_tok.p, chunk_nl.p, words.p);
-    SEQ_TRY(seq_scan(R, chunk_tok.p, chunk_tokx.p, n_chunks + 1));
-    SEQ_TRY(seq_scan(R, chunk_nl.p, chunk_nlx.p, n_chunks + 1));
-    SEQ_TRY(seq_kernels_end(R));
-    unsigned long long nul_at = 0;
-    int64_t total_nl = 0;
-    SEQ_TRY(seq_read_back(R, &nul_at, words.p, 8));
-    SEQ_TRY(seq_read_back(R, &R.T, chunk_tokx.p + n_chunks, 8));
-    SEQ_TRY(seq_read_back(R, &total_nl, chunk_nlx.p + n_chunks, 8));
-    if (nul_at != SEQ_EMPTY) {
-        size_t piece = 0;
-        const int64_t off = seq_text_offset(R, (int64_t)nul_at, &piece);
-        if (R.pieces[piece].path) DGE_FAIL(DGE_ERR_IO, "%s: a NUL byte at offset %lld of the text (in %s): names are handed out as C strings", who, (long long)off, R.pieces[piece].path);
-        DGE_FAIL(DGE_ERR_IO, "%s: a NUL byte at offset %lld of the text: names are handed out as C strings", who, (long long)off);
-    }
-    R.lines = total_nl - R.P;
-    const int64_t T = R.T, P = R.P;
-    if (T < P) DGE_FAIL(DGE_ERR_STATE, "%s: the prior names did not come back as %lld tokens", who, (long long)P);
-
-    // ---- tokens: first byte, line, length, hash
-    SEQ_TRY(seq_alloc(R, R.tok_start, T, "the tokens' offsets"));
-    SEQ_TRY(seq_alloc(R, tok_line, T, "the tokens' lines"));
-    SEQ_TRY(seq_alloc(R, R.tok_len, T, "the tokens' lengths"));
-    SEQ_TRY(seq_alloc(R, R.tok_hash, T, "the tokens' hashes"));
-    SEQ_TRY(seq_alloc(R, R.rowx, T + 1, "the tokens' rows"));
-    SEQ_TRY(seq_kernels_begin(R));
-    if (n_chunks) hipLaunchKernelGGL(k_seq_emit, dim3((unsigned)n_chunks), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, chunk_tokx.p, chunk_nlx.p, R.tok_start.p, tok_line.p);
-    if (T) hipLaunchKernelGGL(k_seq_hash, dim3(seq_grid(T)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.tok_start.p, T, opt.hash_bits, R.tok_len.p, R.tok_hash.p);
-    // ---- rows
-    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqRowFlag{tok_line.p, P, T}), R.rowx.p, T + 1));
-    SEQ_TRY(seq_kernels_end(R));
-    SEQ_TRY(seq_read_back(R, &R.rows, R.rowx.p + T, 8));
-    seq_release(R, tok_line, T);
-    SEQ_TRY(seq_alloc(R, R.row_first, R.rows + 1, "the rows' first tokens"));
-    SEQ_TRY(seq_kernels_begin(R));
-    if (T > P) {
-        hipLaunchKernelGGL(k_seq_row_first, dim3(seq_grid(T - P)), dim3(SEQ_BLOCK), 0, R.stream, R.rowx.p, P, T, R.row_first.p);
-        hipLaunchKernelGGL(k_seq_max_len, dim3(seq_grid(R.rows)), dim3(SEQ_BLOCK), 0, R.stream, R.row_first.p, R.rows, words.p + 1);
-    }
-    SEQ_TRY(seq_kernels_end(R));
-    unsigned long long longest = 0;
-    SEQ_TRY(seq_read_back(R, &longest, words.p + 1, 8));
-    R.max_len = std::max<int64_t>((int64_t)longest, 1);
-
-    // ---- intern: redone with eight times the slots while a pass gives up (seq_plan.h)
-    SEQ_TRY(seq_alloc(R, R.tok_slot, T, "the tokens' slots"));
-    int64_t slots = seq_slots_first(T, opt.initial_slots);
-    for (;;) {
-        SEQ_TRY(seq_alloc(R, R.table, slots, "the name table"));
-        const bool last = slots >= seq_slots_cap(T);
-        const unsigned long long limit = last ? ~0ull : (unsigned long long)std::max<int64_t>(slots / 2 / SEQ_SHARDS, 1);
-        SEQ_TRY(seq_kernels_begin(R));
-        DGE_HIP(hipMemsetAsync(R.table.p, 0xFF, (size_t)slots * 8, R.stream));
-        DGE_HIP(hipMemsetAsync(words.p + 3, 0, (size_t)(n_words - 3) * 8, R.stream));
-        if (T) hipLaunchKernelGGL(k_seq_intern, dim3(seq_grid(T)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.tok_start.p, R.tok_len.p, R.tok_hash.p, T, R.table.p, slots - 1,
-                                  R.tok_slot.p, words.p + 4, limit, reinterpret_cast<int*>(words.p + 3));
-        SEQ_TRY(seq_kernels_end(R));
-        int give_up = 0;
-        SEQ_TRY(seq_read_back(R, &give_up, words.p + 3, 4));
-        if (!give_up) break;
-        if (last) DGE_FAIL(DGE_ERR_STATE, "%s: a name table of %lld slots filled on %lld tokens", who, (long long)slots, (long long)T);
-        R.held -= slots * 8;
-        (void)hipFree(R.table.p); R.table.p = nullptr;
-        slots = seq_slots_next(slots, T);
-    }
-
-    // ---- ids in first-appearance order
-    SEQ_TRY(seq_alloc(R, R.namex, T + 1, "the names' numbers"));
-    SEQ_TRY(seq_alloc(R, R.tok_id, T, "the tokens' ids"));
-    SEQ_TRY(seq_kernels_begin(R));
-    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqFirstFlag{R.table.p, R.tok_slot.p, T}), R.namex.p, T + 1));
-    SEQ_TRY(seq_kernels_end(R));
-    SEQ_TRY(seq_read_back(R, &R.n_names, R.namex.p + T, 8));
-    if (R.n_names > 0x7fffffffLL) DGE_FAIL(DGE_ERR_RANGE, "%s: %lld names do not fit int32 ids", who, (long long)R.n_names);
-    SEQ_TRY(seq_kernels_begin(R));
-    if (T) hipLaunchKernelGGL(k_seq_ids, dim3(seq_grid(T)), dim3(SEQ_BLOCK), 0, R.stream, R.table.p, R.tok_slot.p, R.namex.p, P, T, opt.intern, R.tok_id.p, words.p + 2);
-    SEQ_TRY(seq_kernels_end(R));
-    unsigned long long unknown = 0;
-    SEQ_TRY(seq_read_back(R, &unknown, words.p + 2, 8));
-    R.unknown = (int64_t)unknown;
-    return DGE_OK;
+    SEQ_TRY(seq_tokenise(R, names, who));
+    return seq_intern(R, R.tok_start.p, R.T, opt, who);
 }
 
 // corpus + new names + info out of a finished seq_ingest
@@ -580,26 +81,12 @@ int seq_finish(SeqRun& R, dge_names* names, int intern, dge_walks** out, dge_seq
     SEQ_TRY(seq_kernels_begin(R));
     DGE_HIP(hipMemsetAsync(walks.p, 0xFF, (size_t)std::max<int64_t>(R.rows * R.max_len, 1) * sizeof(int32_t), R.stream));
     if (T > P) hipLaunchKernelGGL(k_seq_pack, dim3(seq_grid(T - P)), dim3(SEQ_BLOCK), 0, R.stream, R.tok_id.p, R.rowx.p, R.row_first.p, P, T, R.max_len, walks.p);
-    // ---- the new names' bytes: one blob, string k at name_off[k]
-    const int64_t n_new = intern ? R.n_names - P : 0;
-    dge_tmp<int64_t> name_tok, name_off;
-    dge_tmp<uint8_t> blob;
-    std::vector<int64_t> off((size_t)n_new + 1, 0);
-    std::unique_ptr<char[]> host_blob;
-    if (n_new > 0) {
-        SEQ_TRY(seq_alloc(R, name_tok, n_new, "the new names' tokens"));
-        SEQ_TRY(seq_alloc(R, name_off, n_new + 1, "the new names' offsets"));
-        hipLaunchKernelGGL(k_seq_name_tok, dim3(seq_grid(T - P)), dim3(SEQ_BLOCK), 0, R.stream, R.namex.p, P, T, name_tok.p);
-        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqNameLen{name_tok.p, R.tok_len.p, n_new}), name_off.p, n_new + 1));
-        SEQ_TRY(seq_read_back(R, off.data(), name_off.p, (size_t)(n_new + 1) * 8));
-        SEQ_TRY(seq_alloc(R, blob, off[(size_t)n_new], "the new names' bytes"));
-        hipLaunchKernelGGL(k_seq_name_bytes, dim3(seq_grid(n_new)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.tok_start.p, R.tok_len.p, name_tok.p, name_off.p, n_new, blob.p);
-    }
     SEQ_TRY(seq_kernels_end(R));
-    if (n_new > 0) {
-        host_blob.reset(new char[(size_t)off[(size_t)n_new]]);
-        SEQ_TRY(seq_read_back(R, host_blob.get(), blob.p, (size_t)off[(size_t)n_new]));
-    }
+    // ---- the new names' bytes
+    const int64_t n_new = intern ? R.n_names - P : 0;
+    std::vector<int64_t> off;
+    std::unique_ptr<char[]> host_blob;
+    SEQ_TRY(seq_new_names(R, R.tok_start.p, n_new, off, host_blob));
     // nothing can fail from here on: the names and the corpus change hands together
     if (n_new > 0) names_append(names, std::move(host_blob), off.data(), n_new);
     dge_walks* w = new dge_walks();

@@ -1,5 +1,5 @@
 // sgns_io.hip — what a host reads back from a trained model (libdge.so, gfx950): the tables' host mirrors (dge_model_vectors and its family), the
-// vocabulary's counts, Huffman paths and unigram table, and the `.vec` text file.  Runs between launches: outside the build stamp (dge_build_stamp, include/dge.h).
+// vocabulary's counts, Huffman paths and unigram table, and the `.vec` text file — and the way back in, dge_model_load_vectors.  Runs between launches: outside the build stamp (dge_build_stamp, include/dge.h).
 #include <string.h>
 
 #include <algorithm>
@@ -150,5 +150,38 @@ extern "C" int dge_write_vec(dge_model* m, const char* const* names, const char*
     }
     if (writer.joinable()) writer.join();
     if (fclose(f) != 0 || !ok) DGE_FAIL(DGE_ERR_IO, "dge_write_vec: write to %s failed", path);
+    return DGE_OK;
+}
+
+// syn0 row r := row vocab_ids[r] of v where v holds that row; a lane per element, the padded row stride honoured
+__global__ void k_load_vectors(const int32_t* __restrict__ vocab_ids, int64_t V, int32_t D, int32_t stride, const float* __restrict__ rows, const uint8_t* __restrict__ present,
+                               int64_t n_rows, float* __restrict__ syn0, unsigned long long* __restrict__ rows_set) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= V * D) return;
+    const int64_t r = i / D; const int32_t j = (int32_t)(i - r * D);
+    const int64_t id = vocab_ids[r];
+    if (id < 0 || id >= n_rows || !present[id]) return;
+    syn0[r * stride + j] = rows[id * D + j];
+    if (j == 0) atomicAdd(rows_set, 1ull);
+}
+
+extern "C" int dge_model_load_vectors(dge_model* m, const dge_vectors* v, int64_t* rows_set) {
+    if (!m || !v) DGE_FAIL(DGE_ERR_ARG, "dge_model_load_vectors: null argument");
+    if (v->dim != m->D) DGE_FAIL(DGE_ERR_ARG, "dge_model_load_vectors: the vectors have dim %d, the model %d", v->dim, m->D);
+    if (v->device != m->device) DGE_FAIL(DGE_ERR_ARG, "dge_model_load_vectors: the vectors are on device %d, the model on %d", v->device, m->device);
+    if (m->part_n > 1) DGE_FAIL(DGE_ERR_STATE, "dge_model_load_vectors: a partition is set (n_parts = %d): the tables are in pieces — call dge_model_set_partition(m, 1, 0, 0) first", m->part_n);
+    DGE_HIP(hipSetDevice(m->device));
+    dge_tmp<unsigned long long> count;
+    int rc = count.alloc(1);
+    if (rc) return rc;
+    DGE_HIP(hipMemsetAsync(count.p, 0, 8, m->stream));
+    const int64_t n = m->V * (int64_t)m->D;
+    if (n && v->rows) hipLaunchKernelGGL(k_load_vectors, dim3(dge_grid_for(n, 256)), dim3(256), 0, m->stream, m->d_vocab_ids, m->V, m->D, m->stride, v->d, v->d_present, v->rows, m->d_syn0,
+                                         count.p);
+    DGE_HIP(hipGetLastError());
+    unsigned long long set = 0;
+    DGE_HIP(hipMemcpyAsync(&set, count.p, 8, hipMemcpyDeviceToHost, m->stream));
+    DGE_HIP(hipStreamSynchronize(m->stream));
+    if (rows_set) *rows_set = (int64_t)set;
     return DGE_OK;
 }

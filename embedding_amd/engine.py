@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import EvalResult, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, check, lib
+from ._native import EvalResult, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -280,6 +280,88 @@ class WalkCorpus:
         check(lib.dge_count_tokens(self._h, int(row0), int(n_rows), int(n_vertices), _dev_ptr(d_counts)))
 
 
+class Vectors:
+    """float32 rows [rows x dim] in HBM with one present byte per row (struct dge_vectors, include/dge.h): what a .vec file holds, aligned by name."""
+
+    def __init__(self, handle, device):
+        self._h = handle
+        self.device = device
+
+    @classmethod
+    def from_vec(cls, paths_or_bytes, header=False, names=None, intern=True, device=0):
+        """.vec text -> (vectors, names, info): tokenised, interned and converted on the device (include/dge.h: dge_vectors_from_vec_files /
+        dge_vectors_from_vec_text); every value is the float32 nearest its exact decimal.  paths_or_bytes: a path, a sequence of paths (taken in
+        order), or the text itself as bytes / bytearray / memoryview.  header=True: every file opens with a "V D" line, which is checked.  names: a
+        Names whose entries keep their ids (default: a new, empty one); row i of the result is the vector of names[i].  intern=True appends new
+        names in the order of their first appearance; intern=False drops rows whose name is unknown (info["dropped"]).  info: the fields of struct
+        dge_vec_info."""
+        if names is None:
+            names = Names()
+        h = C.c_void_p(0); inf = VecInfo()
+        if isinstance(paths_or_bytes, (bytes, bytearray, memoryview)):
+            data = paths_or_bytes
+            if isinstance(data, bytes):
+                ptr = C.cast(C.c_char_p(data), C.c_void_p); n = len(data)
+            else:
+                view = np.frombuffer(data, np.uint8)
+                ptr = _ptr(view); n = view.size
+            check(lib.dge_vectors_from_vec_text(int(device), ptr, n, int(bool(header)), names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
+        else:
+            paths = [paths_or_bytes] if isinstance(paths_or_bytes, (str, os.PathLike)) else list(paths_or_bytes)
+            arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
+            check(lib.dge_vectors_from_vec_files(int(device), arr, len(paths), int(bool(header)), names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
+        return cls(h, int(device)), names, {f[0]: getattr(inf, f[0]) for f in VecInfo._fields_ if f[0] != "reserved"}
+
+    @classmethod
+    def from_host(cls, rows, present=None, device=0):
+        rows = np.ascontiguousarray(rows, np.float32)
+        n, dim = rows.shape
+        if present is not None:
+            present = np.ascontiguousarray(present, np.uint8)
+            if present.shape != (n,):
+                raise ValueError("present must hold one entry per row")
+        h = C.c_void_p(0)
+        check(lib.dge_vectors_from_host(int(device), _ptr(rows), n, dim, _ptr(present), C.byref(h)))
+        return cls(h, int(device))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.dge_vectors_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    @property
+    def shape(self):
+        n = C.c_int64(0); d = C.c_int32(0)
+        check(lib.dge_vectors_info(self._h, C.byref(n), C.byref(d), None, None))
+        return n.value, d.value
+
+    def to_host(self):
+        n, d = self.shape
+        out = np.empty((n, d), np.float32)
+        check(lib.dge_vectors_to_host(self._h, _ptr(out), None, n * d))
+        return out
+
+    def present(self):
+        pres = np.empty(self.shape[0], np.uint8)
+        check(lib.dge_vectors_to_host(self._h, None, _ptr(pres), 0))
+        return pres.astype(bool)
+
+    def knn(self, k):
+        """The k nearest other rows of every row in cosine distance (dge_knn_cosine_vectors) -> (idx int32 [n x k], dist float32 [n x k], kernel_ms)."""
+        n = self.shape[0]
+        idx = np.empty((n, int(k)), np.int32); dist = np.empty((n, int(k)), np.float32); ms = C.c_double(0)
+        check(lib.dge_knn_cosine_vectors(self._h, int(k), _ptr(idx), _ptr(dist), C.byref(ms)))
+        return idx, dist, ms.value
+
+    def ndcg_against(self, gnd, k=10):
+        """nDCG@k of these rows' neighbours under the ground features `gnd` (dge_ndcg_at_k_vectors) -> (nDCG, kernel ms)."""
+        out = C.c_double(0); ms = C.c_double(0)
+        check(lib.dge_ndcg_at_k_vectors(self._h, gnd._h, int(k), C.byref(out), C.byref(ms)))
+        return out.value, ms.value
+
+
 def make_config(dim, window, n_vertices, negative=5, min_count=2, epochs=1, workers=0, alpha=0.025, min_alpha=1e-4,
                 seed=1, table_size=100_000_000, update_policy=0, use_hs=False):
     """struct dge_train_config, field by field (a ctypes view, not a mirror of DeepWalk: use_hs defaults to the plain
@@ -502,6 +584,12 @@ class SgnsModel:
         elif names is not None:
             arr = (C.c_char_p * len(names))(*[n.encode() if n is not None else None for n in names])
         check(lib.dge_write_vec(self._h, arr, str(path).encode(), int(bool(header))))
+
+    def load_vectors(self, v):
+        """syn0 rows of the vocabulary words that `v` (a Vectors) holds := v's rows (dge_model_load_vectors) -> how many rows were set."""
+        n = C.c_int64(0)
+        check(lib.dge_model_load_vectors(self._h, v._h, C.byref(n)))
+        return n.value
 
     # --- multi-GPU exchange (include/dge.h, last section)
     def schedule(self):

@@ -29,3 +29,13 @@ def ndcg_against_gpu(features, gnd_features, k=10, device=0):
     check(lib.dge_ndcg_at_k(int(device), f.ctypes.data_as(C.c_void_p), f.shape[1], g.ctypes.data_as(C.c_void_p), g.shape[1], len(f), int(k),
                             C.byref(out), C.byref(ms)))
     return out.value, ms.value
+
+
+def knn_cosine_vectors(vectors, k):
+    """knn_cosine_gpu on resident rows (an engine.Vectors, e.g. from Vectors.from_vec): dge_knn_cosine_vectors, no host copy of the features."""
+    return vectors.knn(k)
+
+
+def ndcg_vectors(vectors, gnd_vectors, k=10):
+    """ndcg_against_gpu on two resident row sets aligned by name (engine.Vectors): dge_ndcg_at_k_vectors."""
+    return vectors.ndcg_against(gnd_vectors, k)

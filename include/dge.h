@@ -483,6 +483,72 @@ int  dge_ndcg_at_k(int device, const float* features, int32_t dim, const float* 
                    double* ndcg, double* ms_kernels);
 
 /* ------------------------------------------------------------------------------------------------
+ * .vec text in (new; additions only, DGE_VERSION unchanged): the file dge_write_vec / WordVectorSerializer.writeWordVectors leaves (J/DeepWalk.java:82) and
+ * the reference's evaluators load (P/embeddingEvaluation_tract.py:113-117,139-166), read on the device into resident float32 rows aligned by name
+ * (csrc/vec_read.hip; the decimal conversion: csrc/vec_parse.h).
+ *   - The text is BYTES.  A line ends at '\n'; the last line may lack it.  Whitespace is the six bytes 0x09-0x0D and 0x20 (C's isspace in the "C" locale; '\r'
+ *     among them, so CRLF files read the same); every other byte, 0x80-0xFF included, is token material; a token is a maximal run of such bytes, of any length.
+ *     A line without a token is skipped (trailing blanks on a line, as in miscs/taxi_all.txt, change nothing).  A NUL byte: DGE_ERR_IO naming its offset.
+ *   - Rows.  Every other line is a row: its first token is the row's name, the rest are its values.  The first row fixes dim = tokens - 1 >= 1; a row with another
+ *     token count: DGE_ERR_IO naming the least such line, with the count found and the count expected.
+ *   - header == 0: there is no header line.  header != 0: the first line with a token of EVERY piece (file, or the text) must be two unsigned decimal integers
+ *     "V D" (miscs/taxi_all.txt:1); after reading, V must equal that piece's row count and D must equal dim, else DGE_ERR_IO carrying both numbers.  A piece
+ *     without a token has no such line and passes.  A text without any row has dim = the first header's D (0 with header == 0).
+ *   - Several files are taken in the order given; a file whose last byte is not '\n' ends its last line where it ends (no token and no line crosses a file);
+ *     all files share one dim; with header != 0 each carries its own header.
+ *   - A value token is  [+-] digits [. digits] [(e|E) [+-] digits]  with at least one digit in front of the exponent (".5" and "5." are values, "." is not), or
+ *     inf / infinity / nan with an optional sign in any letter case.  Anything else — hex floats, nan(...), "1e", a trailing letter — is DGE_ERR_IO naming the
+ *     least byte offset of such a token, with its piece, line and column.  The value is the binary32 NEAREST THE EXACT DECIMAL VALUE, TIES TO EVEN; overflow
+ *     gives +-inf, underflow goes through the denormals to +-0 with the sign kept ("-0" is 0x80000000), nan is a quiet NaN with the token's sign: what glibc's
+ *     strtof returns in the "C" locale, for tokens of any length (800 digits, 0e999999, 1e-9999).  Not what a reader that goes through a double returns.
+ *   - Names and alignment (the .seq reader's rule, applied to rows).  The names `names` already holds keep ids 0 .. n-1.  intern != 0: a new name gets the next id
+ *     in the order of its first appearance and is appended.  intern == 0: a row whose name is unknown is dropped and counted (info.dropped); its values are
+ *     still checked.  The result has dge_names_count(names) rows AFTER the call; row i is the vector of names[i], present[i] says whether the text held it;
+ *     absent rows are all-zero and counted (info.missing).  A name on two rows, in any piece: DGE_ERR_IO naming the second occurrence (the least such line).
+ *   - A text with several kinds of error reports the first of: NUL, malformed header, ragged row, bad value, duplicate name, header counts.  A file that is
+ *     missing or unreadable: DGE_ERR_IO with its path.  A working set beyond device memory: DGE_ERR_CAP.  Null / negative arguments: DGE_ERR_ARG before a device
+ *     is looked for.  On any error *out is NULL and `names` is as it was.
+ *   - The result is a pure function of the bytes, the prior names and the flags.  No floating-point operation decides a bit of it; nothing depends on timing or
+ *     launch geometry.  Value tokens the device routine hands back (more than 19 significant digits with a non-zero tail, or a power of ten outside its
+ *     128-bit range — never a token of <= 19 digits with |value| in [1e-10, 1e10]) are finished by the host with strtof and counted in info.host_values;
+ *     both paths give the correctly rounded value, so a result never depends on which took a token.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_vectors dge_vectors;      /* resident float32 [rows x dim], row-major, + one present byte per row */
+typedef struct dge_vec_info {
+    int64_t bytes;         /* bytes of text taken (the files' sizes added up)                              */
+    int64_t lines;         /* lines, a last one without '\n' included                                      */
+    int64_t rows;          /* rows read: lines with a token that are no header line, dropped ones included */
+    int64_t values;        /* rows * dim                                                                   */
+    int64_t dropped;       /* intern == 0: rows whose name is not in `names`                               */
+    int64_t missing;       /* rows of the result the text did not hold (present == 0, all-zero)            */
+    int64_t names_added;
+    int64_t host_values;   /* value tokens finished by the host path (rows that are kept only)             */
+    int32_t dim;
+    int32_t reserved;
+    double  read_ms;       /* wall clock spent getting the bytes to the device                             */
+    double  kernel_ms;     /* HIP-event time of the kernels                                                */
+} dge_vec_info;            /* 88 bytes */
+
+int  dge_vectors_from_vec_text (int device, const char* text, int64_t n_bytes, int header, dge_names* names, int intern, dge_vectors** out, dge_vec_info* info /* may be NULL */);
+int  dge_vectors_from_vec_files(int device, const char* const* paths, int32_t n_paths, int header, dge_names* names, int intern, dge_vectors** out, dge_vec_info* info /* may be NULL */);
+/* rows: host float32 [n_rows x dim]; present: host, one byte a row (non-zero = present), NULL = every row */
+int  dge_vectors_from_host(int device, const float* rows, int64_t n_rows, int32_t dim, const uint8_t* present /* NULL: all */, dge_vectors** out);
+/* d_ptr / d_present: device memory, READ-ONLY for the caller; any output may be NULL */
+int  dge_vectors_info(const dge_vectors* v, int64_t* rows, int32_t* dim, const float** d_ptr, const uint8_t** d_present);
+/* out: host [rows x dim], cap_elems floats (smaller: DGE_ERR_CAP), or NULL: the rows are not copied and only present is filled; present: host [rows] */
+int  dge_vectors_to_host(const dge_vectors* v, float* out /* may be NULL */, uint8_t* present /* may be NULL */, int64_t cap_elems);
+void dge_vectors_free(dge_vectors* v);
+
+/* syn0 row of every vocabulary word whose vertex id is a present row of v := that row (continuing from published vectors).  v's dim must equal the model's
+ * (DGE_ERR_ARG); other rows, syn1neg and the counters stay untouched; *rows_set (may be NULL) = how many rows were set.  Ordered on the model's stream, behind
+ * whatever training is queued there; returns after the stream has drained.  With a partition set: DGE_ERR_STATE. */
+int  dge_model_load_vectors(dge_model* m, const dge_vectors* v, int64_t* rows_set);
+
+/* the two quality entries above on resident rows: the same kernels, no host round trip of the features */
+int  dge_knn_cosine_vectors(const dge_vectors* v, int32_t k, int32_t* out_idx, float* out_dist, double* ms_kernel);           /* absent rows are zero vectors */
+int  dge_ndcg_at_k_vectors(const dge_vectors* f, const dge_vectors* gnd, int32_t k, double* ndcg, double* ms_kernels);         /* equal row counts, every row present in both: else DGE_ERR_ARG */
+
+/* ------------------------------------------------------------------------------------------------
  * Ablation / test knobs of the trainer (process-wide relaxed atomics; nothing in a normal run sets them).  value < 0 puts
  * a knob back to the library's own rule.
  * ---------------------------------------------------------------------------------------------- */
