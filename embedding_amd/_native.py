@@ -55,6 +55,13 @@ class VecInfo(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class OdInfo(C.Structure):
+    """struct dge_od_info (include/dge.h) — what dge_graph_add_od_files / dge_graph_add_od_texts report."""
+    _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("flows", C.c_int64), ("edges", C.c_int64), ("dropped", C.c_int64), ("regions", C.c_int64),
+                ("sources", C.c_int64), ("host_values", C.c_int64), ("slices", C.c_int32), ("reserved", C.c_int32), ("read_ms", C.c_double),
+                ("kernel_ms", C.c_double)]
+
+
 # every symbol include/dge.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int
 _P = C.POINTER
@@ -80,6 +87,9 @@ SIGNATURES = {
     "dge_graph_get_alias": (_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i32, _P(_i32), _P(_dbl)]),
     "dge_graph_get_source_alias": (_int, [_vp, _vp, _vp, _vp, _i32, _P(_i32), _P(_dbl)]),
     "dge_graph_sample_next": (_int, [_vp, _i32, _dbl, _P(_i32)]),
+    "dge_graph_add_od_files": (_int, [_vp, _vp, _i32, _vp, _P(OdInfo)]),
+    "dge_graph_add_od_texts": (_int, [_vp, _vp, _vp, _i32, _vp, _P(OdInfo)]),
+    "dge_graph_regions": (_int, [_vp, _vp, _i64, _P(_i64)]),
     "dge_sample_walks": (_int, [_vp, _i64, _i32, _i64, _int, _i64, _vp, _P(_i64)]),
     "dge_sample_walks_device": (_int, [_vp, _i64, _i32, _i64, _int, _i64, _P(_vp), _P(_i64)]),
     "dge_sample_walks_into": (_int, [_vp, _vp, _i64, _i64, _i64, _i64]),

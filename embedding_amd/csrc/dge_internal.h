@@ -106,6 +106,8 @@ struct dge_graph {
     double* d_src_prob = nullptr;
     int32_t* d_src_alias = nullptr;
     dge_slot* d_src_slots = nullptr;
+    // the region ids of a graph made from .od text (od_read.hip), ascending: vertex h*R + i is region od_regions[i] in slice h
+    std::vector<int64_t> od_regions;
 };
 
 struct dge_walks {

@@ -1,0 +1,396 @@
+// od_read.hip — .od flow text in, a layered graph out (include/dge.h: dge_graph_add_od_files / _texts, dge_graph_regions).
+//
+// One "src dst w" line per flow, one piece (a file or a text) per time slice; the rule of the graph is that of embedding_amd/io.py: read_od_slices
+// (J/CrossTimeGraph.java:25-52,68-95).  The host only moves bytes, finishes the few weight tokens the device routine hands back, formats the vertex names
+// and hands the layer-0 vertices to dge_graph_set_sources; the edges never visit it.  Outside the build stamp: nothing here is read or written by a
+// training launch.
+//
+// The passes, on the one buffer of seq_tokens.h (every piece with its pad byte):
+//   seq_tokenise               token t's first byte and line, the rows (rowx, row_first) — the .seq reader's kernels and chunk transport, unchanged
+//   k_od_ragged                every row must have 3 tokens
+//   k_od_parse                 a lane per row: its piece (= slice), od_parse.h's integer routines -> src id, dst id, the weight's bits; "not mine" weights flagged
+//   host path                  the flagged tokens' bytes in one blob, strtod in the "C" locale, k_od_scatter puts the bits in place
+//   k_od_keep                  a weight that is not finite is a bad token; keep[r] = w > 0
+//   scan of keep               a stable compaction: kept flow r is edge keepx[r], edges stand in text order
+//   k_od_endpoints, radix sort, k_od_unique around a scan
+//                              the kept endpoints' ids sorted as signed 64-bit integers, each distinct one once: the R regions, ascending
+//   k_od_edges                 rank by binary search -> d_coo_src / d_coo_dst / d_coo_w of the graph, edge h*R + rank(src) -> ((h+1) % T)*R + rank(dst);
+//                              marks the layer-0 endpoints
+//   k_od_sources around a scan the marked layer-0 vertices, ascending
+// Every error is the LEAST position of its kind, found with atomicMin on a row or a byte offset: which lane gets there first does not matter.
+//
+// Coherence: no protocol.  Every array is written by one kernel and read by later ones on the same stream; the only words several lanes write are the error
+// minima (atomicMin), the host-token counter (atomicAdd) and mark[] (every writer stores 1).
+//
+// What bounds the per-row kernel: a row is three tokens, known from the ragged pass, so a lane touches exactly its own three tokens' bytes.  A token ends at a
+// whitespace byte and the buffer ends in SEQ_TAIL blanks, so the byte loops stop inside the allocation; their length is the token's.  Lanes of a wave hold
+// adjacent lines (~20 bytes each), so their reads fall into the same few cache lines; divergence is over the digits of a token (ids 5-6, weights 1-4 in
+// the reference's files), and the division loop of od_parse_f64 has a fixed trip count.
+#include <locale.h>
+#include <stdlib.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "od_parse.h"
+#include "seq_tokens.h"
+
+// ------------------------------------------------------------------------------------------ kernels
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_ragged(const int64_t* row_first, int64_t rows, unsigned long long* ragged) {
+    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (r >= rows) return;
+    if (row_first[r + 1] - row_first[r] != 3) atomicMin(ragged, (unsigned long long)r);
+}
+
+// row r = tokens row_first[r] .. + 2 (the ragged pass has run).  status[r]: 1 = the host finishes the weight.  bad_at: least offset of a malformed token
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_parse(const uint8_t* buf, const int64_t* tok_start, const int64_t* row_first, int64_t rows, const int64_t* piece_off,
+                                                        int64_t n_pieces, int64_t* src_id, int64_t* dst_id, uint64_t* w_bits, int32_t* slice, uint8_t* status,
+                                                        unsigned long long* bad_at, unsigned long long* n_host) {
+    typedef hipcub::BlockReduce<unsigned long long, SEQ_BLOCK> Reduce;
+    __shared__ typename Reduce::TempStorage tmp;
+    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    unsigned long long for_host = 0;
+    if (r < rows) {
+        const int64_t t = row_first[r];
+        const int64_t at[3] = {tok_start[t], tok_start[t + 1], tok_start[t + 2]};
+        int64_t id[2] = {0, 0};
+        for (int i = 0; i < 2; i++) {
+            const uint8_t* p = buf + at[i];
+            if (!od_parse_id(p, seq_tok_len(p), &id[i])) atomicMin(bad_at, (unsigned long long)at[i]);
+        }
+        const uint8_t* p = buf + at[2];
+        uint64_t bits = 0;
+        const int rc = od_parse_f64(p, seq_tok_len(p), &bits);
+        if (rc == VEC_PARSE_BAD) atomicMin(bad_at, (unsigned long long)at[2]);
+        for_host = rc == VEC_PARSE_HOST ? 1 : 0;
+        src_id[r] = id[0]; dst_id[r] = id[1]; w_bits[r] = bits;
+        slice[r] = (int32_t)seq_piece_of(piece_off, n_pieces, at[0]);
+        status[r] = (uint8_t)for_host;
+    }
+    const unsigned long long sum = Reduce(tmp).Sum(for_host);
+    if (threadIdx.x == 0 && sum) atomicAdd(n_host, sum);
+}
+
+struct OdHostFlag { const uint8_t* status; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n ? status[i] : 0; } };
+struct OdHostLen {       // bytes of host token k (the weight of row host_row[k]) in the blob, its NUL included
+    const uint8_t* buf; const int64_t* tok_start; const int64_t* row_first; const int64_t* host_row; int64_t n;
+    __device__ int64_t operator()(int64_t k) const { return k < n ? seq_tok_len(buf + tok_start[row_first[host_row[k]] + 2]) + 1 : 0; }
+};
+
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_host_bytes(const uint8_t* buf, const int64_t* tok_start, const int64_t* row_first, const int64_t* host_row, const int64_t* host_off,
+                                                             int64_t n, uint8_t* blob) {
+    const int64_t k = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const uint8_t* src = buf + tok_start[row_first[host_row[k]] + 2];
+    const int64_t len = host_off[k + 1] - host_off[k] - 1;
+    uint8_t* dst = blob + host_off[k];
+    for (int64_t i = 0; i < len; i++) dst[i] = src[i];
+    dst[len] = 0;
+}
+
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_scatter(const int64_t* host_row, const uint64_t* host_bits, int64_t n, uint64_t* w_bits) {
+    const int64_t k = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (k < n) w_bits[host_row[k]] = host_bits[k];
+}
+
+// a weight that is not finite (inf, nan, overflow — decided here or by strtod) is a bad token; a flow is kept when its weight is > 0
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_keep(const uint64_t* w_bits, const int64_t* tok_start, const int64_t* row_first, int64_t rows, uint8_t* keep,
+                                                       unsigned long long* bad_at) {
+    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (r >= rows) return;
+    const uint64_t b = w_bits[r], mag = b & 0x7FFFFFFFFFFFFFFFull;
+    if (mag >= 0x7FF0000000000000ull) atomicMin(bad_at, (unsigned long long)tok_start[row_first[r] + 2]);
+    keep[r] = (b >> 63) == 0 && mag != 0 ? 1 : 0;
+}
+
+struct OdKeepFlag { const uint8_t* keep; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n ? keep[i] : 0; } };
+
+// the ids of the kept flows' endpoints: edge e's at [2e], [2e + 1]
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_endpoints(const int64_t* src_id, const int64_t* dst_id, const int64_t* keepx, int64_t rows, int64_t* ends) {
+    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (r >= rows || keepx[r + 1] == keepx[r]) return;
+    const int64_t e = keepx[r];
+    ends[2 * e] = src_id[r]; ends[2 * e + 1] = dst_id[r];
+}
+
+struct OdNewFlag { const int64_t* sorted; int64_t n; __device__ int64_t operator()(int64_t i) const { return (i < n && (i == 0 || sorted[i] != sorted[i - 1])) ? 1 : 0; } };
+
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_unique(const int64_t* sorted, const int64_t* newx, int64_t n, int64_t* regions) {
+    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (i < n && newx[i + 1] != newx[i]) regions[newx[i]] = sorted[i];
+}
+
+__device__ __forceinline__ int64_t od_rank(const int64_t* regions, int64_t R, int64_t id) {      // id is among the regions
+    int64_t lo = 0, hi = R;
+    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (regions[mid] <= id) lo = mid; else hi = mid; }
+    return lo;
+}
+
+// kept flow r of slice h -> edge keepx[r]: h*R + rank(src) -> ((h + 1) % T)*R + rank(dst); mark[i] = 1 for every layer-0 vertex i that is an endpoint
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_edges(const int64_t* src_id, const int64_t* dst_id, const uint64_t* w_bits, const int32_t* slice, const int64_t* keepx,
+                                                        int64_t rows, const int64_t* regions, int64_t R, int64_t T, int32_t* coo_src, int32_t* coo_dst, double* coo_w,
+                                                        uint8_t* mark) {
+    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (r >= rows || keepx[r + 1] == keepx[r]) return;
+    const int64_t e = keepx[r], h = slice[r], h1 = h + 1 == T ? 0 : h + 1;
+    const int64_t rs = od_rank(regions, R, src_id[r]), rd = od_rank(regions, R, dst_id[r]);
+    coo_src[e] = (int32_t)(h * R + rs);
+    coo_dst[e] = (int32_t)(h1 * R + rd);
+    coo_w[e] = __longlong_as_double((long long)w_bits[r]);
+    if (h == 0) mark[rs] = 1;
+    if (h1 == 0) mark[rd] = 1;
+}
+
+__global__ void __launch_bounds__(SEQ_BLOCK) k_od_sources(const int64_t* markx, int64_t R, int32_t* srcv) {
+    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (i < R && markx[i + 1] != markx[i]) srcv[markx[i]] = (int32_t)i;
+}
+
+// ------------------------------------------------------------------------------------------ host side of one read
+namespace {
+
+bool od_fresh(const dge_graph* g) { return g->n_coo == 0 && g->max_id < 0 && g->S == 0 && !g->d_srcv && g->od_regions.empty(); }
+
+// back to what dge_graph_create left: everything this call put into g goes
+void od_reset(dge_graph* g) {
+    void* mine[] = {g->d_coo_src, g->d_coo_dst, g->d_coo_w, g->d_row_ptr, g->d_nbr, g->d_w, g->d_outdeg, g->d_prob, g->d_alias, g->d_slots,
+                    g->d_srcv, g->d_src_w, g->d_src_prob, g->d_src_alias, g->d_src_slots};
+    for (void* p : mine) dge_dev_free(p);
+    g->d_coo_src = g->d_coo_dst = nullptr; g->d_coo_w = nullptr; g->n_coo = g->cap_coo = 0; g->max_id = -1;
+    g->d_row_ptr = nullptr; g->d_nbr = nullptr; g->d_w = nullptr; g->d_outdeg = nullptr; g->d_prob = nullptr; g->d_alias = nullptr; g->d_slots = nullptr;
+    g->csr_built = g->alias_built = false; g->V = 0; g->E = 0;
+    g->d_srcv = nullptr; g->d_src_w = nullptr; g->d_src_prob = nullptr; g->d_src_alias = nullptr; g->d_src_slots = nullptr;
+    g->S = 0; g->src_weight_sum = 0.0; g->src_stream_sum = 0; g->src_sum_fixed = false;
+    g->od_regions.clear();
+}
+
+int od_read(SeqRun& R, dge_graph* g, dge_names* names, dge_od_info* info, const char* who) {
+    R.what = "od read";
+    SEQ_TRY(seq_tokenise(R, nullptr, who));
+    const int64_t rows = R.rows, T = (int64_t)R.pieces.size();
+    // words: [0] ragged row, [1] malformed token (offset), [2] host tokens
+    dge_tmp<unsigned long long> words;
+    unsigned long long w[3] = {~0ull, ~0ull, 0ull};
+    SEQ_TRY(seq_alloc(R, words, 3, "the counters"));
+    DGE_HIP(hipMemcpyAsync(words.p, w, sizeof(w), hipMemcpyHostToDevice, R.stream));
+    SEQ_TRY(seq_kernels_begin(R));
+    if (rows) hipLaunchKernelGGL(k_od_ragged, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, R.row_first.p, rows, words.p);
+    SEQ_TRY(seq_kernels_end(R));
+    SEQ_TRY(seq_read_back(R, w, words.p, 8));
+    if (w[0] != ~0ull) {
+        int64_t f[2], at = 0;
+        SEQ_TRY(seq_read_back(R, f, R.row_first.p + (int64_t)w[0], 16));
+        SEQ_TRY(seq_read_back(R, &at, R.tok_start.p + f[0], 8));
+        DGE_FAIL(DGE_ERR_IO, "%s: the line at %s has %lld token%s where 3 are expected: src dst w", who, seq_where(R, at).c_str(), (long long)(f[1] - f[0]), f[1] - f[0] == 1 ? "" : "s");
+    }
+
+    // ---- the flows: two ids, a weight, the slice
+    dge_tmp<int64_t> piece_off, src_id, dst_id, keepx;
+    dge_tmp<uint64_t> w_bits;
+    dge_tmp<int32_t> slice;
+    dge_tmp<uint8_t> status, keep;
+    SEQ_TRY(seq_alloc(R, piece_off, T, "the pieces"));
+    SEQ_TRY(seq_alloc(R, src_id, rows, "the flows' sources"));
+    SEQ_TRY(seq_alloc(R, dst_id, rows, "the flows' destinations"));
+    SEQ_TRY(seq_alloc(R, w_bits, rows, "the flows' weights"));
+    SEQ_TRY(seq_alloc(R, slice, rows, "the flows' slices"));
+    SEQ_TRY(seq_alloc(R, status, rows, "the weights' states"));
+    SEQ_TRY(seq_alloc(R, keep, rows, "the kept flows"));
+    SEQ_TRY(seq_alloc(R, keepx, rows + 1, "the kept flows' numbers"));
+    DGE_HIP(hipMemcpyAsync(piece_off.p, R.L.offset.data(), (size_t)T * 8, hipMemcpyHostToDevice, R.stream));
+    SEQ_TRY(seq_kernels_begin(R));
+    if (rows) hipLaunchKernelGGL(k_od_parse, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.tok_start.p, R.row_first.p, rows, piece_off.p, T, src_id.p, dst_id.p,
+                                 w_bits.p, slice.p, status.p, words.p + 1, words.p + 2);
+    SEQ_TRY(seq_kernels_end(R));
+    SEQ_TRY(seq_read_back(R, w + 2, words.p + 2, 8));
+
+    // ---- the host path: the flagged weights' bytes in one blob, strtod, the bits back into place
+    const int64_t n_host = (int64_t)w[2];
+    if (n_host > 0) {
+        dge_tmp<int64_t> hostx, host_row, host_off;
+        dge_tmp<uint8_t> blob;
+        dge_tmp<uint64_t> host_bits;
+        SEQ_TRY(seq_alloc(R, hostx, rows + 1, "the host tokens' numbers"));
+        SEQ_TRY(seq_alloc(R, host_row, n_host, "the host tokens"));
+        SEQ_TRY(seq_alloc(R, host_off, n_host + 1, "the host tokens' offsets"));
+        SEQ_TRY(seq_alloc(R, host_bits, n_host, "the host tokens' values"));
+        SEQ_TRY(seq_kernels_begin(R));
+        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdHostFlag{status.p, rows}), hostx.p, rows + 1));
+        hipLaunchKernelGGL(k_seq_name_tok, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, hostx.p, (int64_t)0, rows, host_row.p);
+        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdHostLen{R.buf.p, R.tok_start.p, R.row_first.p, host_row.p, n_host}), host_off.p,
+                         n_host + 1));
+        std::vector<int64_t> off((size_t)n_host + 1);
+        SEQ_TRY(seq_read_back(R, off.data(), host_off.p, (size_t)(n_host + 1) * 8));
+        SEQ_TRY(seq_alloc(R, blob, off[(size_t)n_host], "the host tokens' bytes"));
+        hipLaunchKernelGGL(k_od_host_bytes, dim3(seq_grid(n_host)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.tok_start.p, R.row_first.p, host_row.p, host_off.p, n_host, blob.p);
+        SEQ_TRY(seq_kernels_end(R));
+        std::unique_ptr<char[]> text(new char[(size_t)off[(size_t)n_host]]);
+        SEQ_TRY(seq_read_back(R, text.get(), blob.p, (size_t)off[(size_t)n_host]));
+        std::vector<uint64_t> bits((size_t)n_host);
+        locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+        if (!c_locale) DGE_FAIL(DGE_ERR_STATE, "%s: the \"C\" locale is not available", who);
+        for (int64_t k = 0; k < n_host; k++) { const double d = strtod_l(text.get() + off[(size_t)k], nullptr, c_locale); memcpy(&bits[(size_t)k], &d, 8); }
+        freelocale(c_locale);
+        DGE_HIP(hipMemcpyAsync(host_bits.p, bits.data(), (size_t)n_host * 8, hipMemcpyHostToDevice, R.stream));
+        SEQ_TRY(seq_kernels_begin(R));
+        hipLaunchKernelGGL(k_od_scatter, dim3(seq_grid(n_host)), dim3(SEQ_BLOCK), 0, R.stream, host_row.p, host_bits.p, n_host, w_bits.p);
+        SEQ_TRY(seq_kernels_end(R));
+    }
+
+    // ---- the kept flows, numbered in text order
+    SEQ_TRY(seq_kernels_begin(R));
+    if (rows) hipLaunchKernelGGL(k_od_keep, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, w_bits.p, R.tok_start.p, R.row_first.p, rows, keep.p, words.p + 1);
+    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdKeepFlag{keep.p, rows}), keepx.p, rows + 1));
+    SEQ_TRY(seq_kernels_end(R));
+    SEQ_TRY(seq_read_back(R, w + 1, words.p + 1, 8));
+    if (w[1] != ~0ull)
+        DGE_FAIL(DGE_ERR_IO, "%s: the token at %s is not a region id ([+-] digits, an int64) or not a weight (a finite decimal number)", who, seq_where(R, (int64_t)w[1]).c_str());
+    int64_t E = 0;
+    SEQ_TRY(seq_read_back(R, &E, keepx.p + rows, 8));
+    seq_release(R, status, rows);
+    seq_release(R, keep, rows);
+
+    // ---- the regions: the kept endpoints' ids, sorted, each once
+    int64_t n_regions = 0;
+    dge_tmp<int64_t> regions;
+    {
+        dge_tmp<int64_t> ends, sorted, newx;
+        dge_tmp<uint8_t> tmp;
+        SEQ_TRY(seq_alloc(R, ends, 2 * E, "the endpoints"));
+        SEQ_TRY(seq_alloc(R, sorted, 2 * E, "the sorted endpoints"));
+        SEQ_TRY(seq_alloc(R, newx, 2 * E + 1, "the regions' numbers"));
+        size_t bytes = 0;
+        if (E) DGE_HIP(rocprim::radix_sort_keys(nullptr, bytes, ends.p, sorted.p, (size_t)(2 * E), 0, 64, R.stream));
+        SEQ_TRY(seq_alloc(R, tmp, (int64_t)bytes, "the sort's scratch"));
+        SEQ_TRY(seq_kernels_begin(R));
+        if (E) {
+            hipLaunchKernelGGL(k_od_endpoints, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, src_id.p, dst_id.p, keepx.p, rows, ends.p);
+            DGE_HIP(rocprim::radix_sort_keys((void*)tmp.p, bytes, ends.p, sorted.p, (size_t)(2 * E), 0, 64, R.stream));
+        }
+        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdNewFlag{sorted.p, 2 * E}), newx.p, 2 * E + 1));
+        SEQ_TRY(seq_kernels_end(R));
+        SEQ_TRY(seq_read_back(R, &n_regions, newx.p + 2 * E, 8));
+        if (T * n_regions > 0x7fffffffLL)
+            DGE_FAIL(DGE_ERR_RANGE, "%s: %lld slices of %lld regions are %lld vertices, which do not fit int32 ids", who, (long long)T, (long long)n_regions, (long long)(T * n_regions));
+        SEQ_TRY(seq_alloc(R, regions, n_regions, "the regions"));
+        SEQ_TRY(seq_kernels_begin(R));
+        if (E) hipLaunchKernelGGL(k_od_unique, dim3(seq_grid(2 * E)), dim3(SEQ_BLOCK), 0, R.stream, sorted.p, newx.p, 2 * E, regions.p);
+        SEQ_TRY(seq_kernels_end(R));
+        seq_release(R, ends, 2 * E); seq_release(R, sorted, 2 * E); seq_release(R, newx, 2 * E + 1); seq_release(R, tmp, (int64_t)bytes);
+    }
+    const int64_t Rn = n_regions;
+
+    // ---- the edges into the graph's own staging, the layer-0 endpoints
+    dge_tmp<int32_t> coo_src, coo_dst, srcv;
+    dge_tmp<double> coo_w;
+    dge_tmp<uint8_t> mark;
+    dge_tmp<int64_t> markx;
+    SEQ_TRY(seq_alloc(R, coo_src, E, "the edges' sources"));
+    SEQ_TRY(seq_alloc(R, coo_dst, E, "the edges' destinations"));
+    SEQ_TRY(seq_alloc(R, coo_w, E, "the edges' weights"));
+    SEQ_TRY(seq_alloc(R, mark, Rn, "the layer-0 vertices"));
+    SEQ_TRY(seq_alloc(R, markx, Rn + 1, "the layer-0 vertices' numbers"));
+    SEQ_TRY(seq_kernels_begin(R));
+    DGE_HIP(hipMemsetAsync(mark.p, 0, (size_t)std::max<int64_t>(Rn, 1), R.stream));
+    if (E) hipLaunchKernelGGL(k_od_edges, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, src_id.p, dst_id.p, w_bits.p, slice.p, keepx.p, rows, regions.p, Rn, T, coo_src.p, coo_dst.p,
+                              coo_w.p, mark.p);
+    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdKeepFlag{mark.p, Rn}), markx.p, Rn + 1));
+    SEQ_TRY(seq_kernels_end(R));
+    int64_t S = 0;
+    SEQ_TRY(seq_read_back(R, &S, markx.p + Rn, 8));
+    SEQ_TRY(seq_alloc(R, srcv, S, "the sources"));
+    SEQ_TRY(seq_kernels_begin(R));
+    if (Rn) hipLaunchKernelGGL(k_od_sources, dim3(seq_grid(Rn)), dim3(SEQ_BLOCK), 0, R.stream, markx.p, Rn, srcv.p);
+    SEQ_TRY(seq_kernels_end(R));
+    std::vector<int64_t> host_regions((size_t)Rn);
+    std::vector<int32_t> host_srcv((size_t)S);
+    if (Rn) SEQ_TRY(seq_read_back(R, host_regions.data(), regions.p, (size_t)Rn * 8));
+    if (S) SEQ_TRY(seq_read_back(R, host_srcv.data(), srcv.p, (size_t)S * 4));
+    DGE_HIP(hipStreamSynchronize(R.stream));
+    DGE_HIP(hipGetLastError());
+
+    // ---- the names "<h>-<region id>" in vertex-id order: the host formats them, R is small against E
+    std::vector<int64_t> off;
+    std::unique_ptr<char[]> name_blob;
+    if (names) {
+        std::string all;
+        off.reserve((size_t)(T * Rn) + 1);
+        char one[48];
+        for (int64_t h = 0; h < T; h++)
+            for (int64_t i = 0; i < Rn; i++) {
+                off.push_back((int64_t)all.size());
+                const int len = snprintf(one, sizeof(one), "%lld-%lld", (long long)h, (long long)host_regions[(size_t)i]);
+                all.append(one, (size_t)len + 1);
+            }
+        off.push_back((int64_t)all.size());
+        name_blob.reset(new char[all.size() + 1]);
+        memcpy(name_blob.get(), all.data(), all.size());
+    }
+
+    // ---- the graph takes the edges over, then stands where a host stands after add_edges, reserve_vertices and set_sources
+    od_reset(g);                                   // (a fresh graph may hold an empty CSR from a read-back: set_sources must build the real one)
+    g->d_coo_src = coo_src.release(); g->d_coo_dst = coo_dst.release(); g->d_coo_w = coo_w.release();
+    g->n_coo = E; g->cap_coo = std::max<int64_t>(E, 1);
+    g->max_id = (int32_t)(T * Rn) - 1;
+    const int rc = dge_graph_set_sources(g, host_srcv.data(), S, 0);
+    if (rc) { od_reset(g); return rc; }
+    // nothing can fail from here on
+    g->od_regions = std::move(host_regions);
+    if (names && T * Rn > 0) names_append(names, std::move(name_blob), off.data(), T * Rn);
+    if (info) {
+        info->bytes = R.L.text_bytes; info->lines = R.lines; info->flows = rows; info->edges = E; info->dropped = rows - E; info->regions = Rn; info->sources = S;
+        info->host_values = n_host; info->slices = (int32_t)T; info->reserved = 0; info->read_ms = R.read_ms; info->kernel_ms = R.kernel_ms;
+    }
+    return DGE_OK;
+}
+
+// what both entries check before a device is looked for (the pieces' own arguments are the caller's)
+int od_check(const dge_graph* g, const dge_names* names, const char* who) {
+    if (names && !names->ptr.empty()) DGE_FAIL(DGE_ERR_ARG, "%s: names must be empty: it receives the vertex names, it holds %lld", who, (long long)names->ptr.size());
+    if (!od_fresh(g)) DGE_FAIL(DGE_ERR_STATE, "%s: the graph must be fresh: it already holds edges, sources or reserved vertices", who);
+    return DGE_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------ entries
+extern "C" int dge_graph_add_od_texts(dge_graph* g, const char* const* texts, const int64_t* n_bytes, int32_t n_slices, dge_names* names, dge_od_info* info) {
+    if (!g || !texts || !n_bytes || n_slices < 1) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_od_texts: null or negative argument, or fewer than 1 slice");
+    for (int32_t k = 0; k < n_slices; k++)
+        if (n_bytes[k] < 0 || (n_bytes[k] > 0 && !texts[k])) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_od_texts: text %d is null or of negative size", k);
+    SEQ_TRY(od_check(g, names, "dge_graph_add_od_texts"));
+    SEQ_TRY(dge_require_device(g->device));
+    SeqRun R;
+    R.device = g->device;
+    for (int32_t k = 0; k < n_slices; k++) {
+        SeqPiece p; p.mem = reinterpret_cast<const uint8_t*>(texts[k]); p.size = n_bytes[k];
+        R.pieces.push_back(p);
+    }
+    return od_read(R, g, names, info, "dge_graph_add_od_texts");
+}
+
+extern "C" int dge_graph_add_od_files(dge_graph* g, const char* const* paths, int32_t n_slices, dge_names* names, dge_od_info* info) {
+    if (!g || !paths || n_slices < 1) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_od_files: null or negative argument, or fewer than 1 slice");
+    for (int32_t k = 0; k < n_slices; k++) if (!paths[k]) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_od_files: path %d is null", k);
+    SEQ_TRY(od_check(g, names, "dge_graph_add_od_files"));
+    SEQ_TRY(dge_require_device(g->device));
+    SeqRun R;
+    R.device = g->device;
+    for (int32_t k = 0; k < n_slices; k++) {
+        SeqPiece p; p.path = paths[k];
+        p.fd = open(paths[k], O_RDONLY | O_CLOEXEC);
+        if (p.fd < 0) DGE_FAIL(DGE_ERR_IO, "cannot open %s: %s", paths[k], strerror(errno));
+        R.pieces.push_back(p);                     // (the run closes it)
+        struct stat st;
+        if (fstat(p.fd, &st) != 0 || !S_ISREG(st.st_mode)) DGE_FAIL(DGE_ERR_IO, "cannot read %s: not a regular file", paths[k]);
+        R.pieces.back().size = (int64_t)st.st_size;
+    }
+    return od_read(R, g, names, info, "dge_graph_add_od_files");
+}
+
+extern "C" int dge_graph_regions(const dge_graph* g, int64_t* regions, int64_t cap, int64_t* n) {
+    if (!g || !n || cap < 0 || (cap > 0 && !regions)) DGE_FAIL(DGE_ERR_ARG, "dge_graph_regions: null or negative argument");
+    *n = (int64_t)g->od_regions.size();
+    if (cap < *n) DGE_FAIL(DGE_ERR_CAP, "dge_graph_regions: %lld regions exceed cap %lld", (long long)*n, (long long)cap);
+    if (*n) memcpy(regions, g->od_regions.data(), (size_t)*n * 8);
+    return DGE_OK;
+}

@@ -1,6 +1,6 @@
-// seq_tokens.h — the tokeniser, the name table and the byte transport that the two text readers share: seq_ingest.hip (.seq walks) and vec_read.hip (.vec
-// vectors) both include it, so every kernel and host routine below exists once in source.  Everything is static: each translation unit gets its own copy of
-// the code and the library exports nothing from here.  Outside the build stamp, like both readers.
+// seq_tokens.h — the tokeniser, the name table and the byte transport that the text readers share: seq_ingest.hip (.seq walks), vec_read.hip (.vec vectors) and
+// od_read.hip (.od flows; it interns nothing) all include it, so every kernel and host routine below exists once in source.  Everything is static: each
+// translation unit gets its own copy of the code and the library exports nothing from here.  Outside the build stamp, like the readers.
 //
 // One buffer holds everything the kernels read (seq_plan.h: seq_layout): the names the caller's dge_names already holds, one per line, then every file
 // (or the caller's text) with one pad byte behind it, then blanks up to whole chunks.  The prior names are thereby the first tokens of the buffer and take
@@ -126,6 +126,23 @@ __device__ __forceinline__ int seq_run(uint64_t w) {
 }
 __device__ __forceinline__ uint64_t seq_keep(uint64_t w, int n) { return n >= 8 ? w : (n == 0 ? 0ull : (w & (~0ull >> (64 - 8 * n)))); }
 
+// bytes of the token that starts at p (the buffer ends in SEQ_TAIL blanks)
+__device__ __forceinline__ int64_t seq_tok_len(const uint8_t* p) {
+    int64_t len = 0;
+    for (;;) {
+        const int n = seq_run(seq_ld8(p + len));
+        len += n;
+        if (n < 8) return len;
+    }
+}
+
+// the piece a buffer offset lies in: the last k with piece_off[k] <= at (at is never in front of piece 0)
+__device__ __forceinline__ int64_t seq_piece_of(const int64_t* piece_off, int64_t n_pieces, int64_t at) {
+    int64_t lo = 0, hi = n_pieces;
+    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (piece_off[mid] <= at) lo = mid; else hi = mid; }
+    return lo;
+}
+
 // The buffer ends in SEQ_TAIL blanks: the 8-byte reads stop at a whitespace byte inside the allocation.
 static __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_hash(const uint8_t* buf, const int64_t* tok_start, int64_t T, int32_t hash_bits, int64_t* tok_len, uint64_t* tok_hash) {
     const int64_t t = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
@@ -247,6 +264,28 @@ static __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_name_bytes(const uint8
     uint8_t* dst = blob + name_off[k];
     for (int64_t i = 0; i < len; i++) dst[i] = src[i];
     dst[len] = 0;
+}
+
+// one lane: where[0] = newlines in [lo, at), where[1] = bytes between the start of at's line (or lo) and at.  The lane walks inside three chunks at the most,
+// however long the line is: the chunks of lo and of at for the counts, and the chunk that holds the last newline in front of at, which the scanned
+// per-chunk counts give by bisection (the last chunk with fewer newlines in front of it than at has).
+[[maybe_unused]] static __global__ void k_seq_locate(const uint8_t* buf, const int64_t* chunk_nlx, int64_t lo, int64_t at, int64_t* where) {
+    int64_t nl[2];
+    const int64_t pos[2] = {lo, at};
+    for (int i = 0; i < 2; i++) {
+        const int64_t c = pos[i] / SEQ_CHUNK;
+        nl[i] = chunk_nlx[c];
+        for (int64_t b = c * SEQ_CHUNK; b < pos[i]; b++) nl[i] += buf[b] == '\n';
+    }
+    int64_t b = lo;                                      // no newline in [lo, at): the line starts with the piece
+    if (nl[1] > nl[0]) {
+        int64_t c = 0, hi = at / SEQ_CHUNK + 1;          // chunk_nlx[0] = 0 < nl[1]; the newline sought lies in front of at
+        while (hi - c > 1) { const int64_t mid = (c + hi) >> 1; if (chunk_nlx[mid] < nl[1]) c = mid; else hi = mid; }
+        b = at < (c + 1) * SEQ_CHUNK ? at : (c + 1) * SEQ_CHUNK;
+        while (b > c * SEQ_CHUNK && buf[b - 1] != '\n') b--;
+    }
+    where[0] = nl[1] - nl[0];
+    where[1] = at - b;
 }
 
 // ------------------------------------------------------------------------------------------ host side of one ingest
@@ -377,6 +416,22 @@ int64_t seq_text_offset(const SeqRun& R, int64_t at, size_t* piece) {
     return at;
 }
 
+// "offset O of the text (piece K[, path]), line L, column C" for a buffer offset; line and column count from 1 inside the piece
+[[maybe_unused]] std::string seq_where(SeqRun& R, int64_t at) {
+    size_t piece = 0;
+    const int64_t off = seq_text_offset(R, at, &piece);
+    int64_t where[2] = {0, 0};
+    dge_tmp<int64_t> d;
+    if (seq_alloc(R, d, 2, "a position") == DGE_OK) {
+        hipLaunchKernelGGL(k_seq_locate, dim3(1), dim3(1), 0, R.stream, R.buf.p, R.chunk_nlx.p, R.L.offset[piece], at, d.p);
+        (void)seq_read_back(R, where, d.p, sizeof(where));
+    }
+    char msg[512];
+    snprintf(msg, sizeof(msg), "offset %lld of the text (piece %lld%s%s), line %lld, column %lld", (long long)off, (long long)piece, R.pieces[piece].path ? ", " : "",
+             R.pieces[piece].path ? R.pieces[piece].path : "", (long long)where[0] + 1, (long long)where[1] + 1);
+    return msg;
+}
+
 struct SeqOptions { int32_t hash_bits = 64; int64_t initial_slots = 0; int intern = 1; };
 
 // bytes to the device, tokens (first byte, line), rows (rowx, row_first, max_len)
@@ -483,7 +538,7 @@ int seq_tokenise(SeqRun& R, const dge_names* names, const char* who) {
 
 // Entries e = 0 .. N-1, entry e the token whose first byte is starts[e] (device), the first P of them the prior names: length, hash, name table, ids in
 // first-appearance order.  The kernels are the same whatever the entries are; the .seq reader interns every token (starts = tok_start, N = T).
-int seq_intern(SeqRun& R, const int64_t* starts, int64_t N, const SeqOptions& opt, const char* who) {
+[[maybe_unused]] int seq_intern(SeqRun& R, const int64_t* starts, int64_t N, const SeqOptions& opt, const char* who) {
     const int64_t T = N, P = R.P;
     dge_tmp<unsigned long long>& words = R.words;
     const int64_t n_words = 4 + (int64_t)SEQ_SHARDS * SEQ_SHARD_STRIDE;
@@ -534,7 +589,7 @@ int seq_intern(SeqRun& R, const int64_t* starts, int64_t N, const SeqOptions& op
 }
 
 // the bytes of the n_new names behind the prior ones (entries as in seq_intern), NUL-terminated, in ONE blob for the host: string k at off[k]
-int seq_new_names(SeqRun& R, const int64_t* starts, int64_t n_new, std::vector<int64_t>& off, std::unique_ptr<char[]>& host_blob) {
+[[maybe_unused]] int seq_new_names(SeqRun& R, const int64_t* starts, int64_t n_new, std::vector<int64_t>& off, std::unique_ptr<char[]>& host_blob) {
     const int64_t T = R.N, P = R.P;
     off.assign((size_t)std::max<int64_t>(n_new, 0) + 1, 0);
     if (n_new <= 0) return DGE_OK;

@@ -28,25 +28,9 @@
 #include "vec_parse.h"
 
 // ------------------------------------------------------------------------------------------ kernels
-__device__ __forceinline__ int64_t vec_tok_len(const uint8_t* p) {      // (the buffer ends in SEQ_TAIL blanks)
-    int64_t len = 0;
-    for (;;) {
-        const int n = seq_run(seq_ld8(p + len));
-        len += n;
-        if (n < 8) return len;
-    }
-}
-
-// the piece a buffer offset lies in: the last k with piece_off[k] <= at (at is never in front of piece 0)
-__device__ __forceinline__ int64_t vec_piece_of(const int64_t* piece_off, int64_t n_pieces, int64_t at) {
-    int64_t lo = 0, hi = n_pieces;
-    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (piece_off[mid] <= at) lo = mid; else hi = mid; }
-    return lo;
-}
-
 // an unsigned decimal integer of up to 18 digits (more: INT64_MAX, which equals no count); -1: not one
 __device__ __forceinline__ int64_t vec_uint(const uint8_t* p) {
-    const int64_t len = vec_tok_len(p);
+    const int64_t len = seq_tok_len(p);
     int64_t v = 0;
     for (int64_t i = 0; i < len; i++) {
         const uint32_t d = (uint32_t)p[i] - '0';
@@ -62,8 +46,8 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_vec_mark(const uint8_t* buf, cons
     const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
     if (r >= rows) return;
     const int64_t t = row_first[r];
-    const int64_t k = vec_piece_of(piece_off, n_pieces, tok_start[t]);
-    const bool hdr = header && (r == 0 || vec_piece_of(piece_off, n_pieces, tok_start[row_first[r - 1]]) != k);
+    const int64_t k = seq_piece_of(piece_off, n_pieces, tok_start[t]);
+    const bool hdr = header && (r == 0 || seq_piece_of(piece_off, n_pieces, tok_start[row_first[r - 1]]) != k);
     is_hdr[r] = hdr ? 1 : 0;
     if (!hdr) { atomicMin(first_data, (unsigned long long)r); return; }
     piece_first[k] = r;
@@ -109,7 +93,7 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_vec_parse(const uint8_t* buf, con
             else if (col < dim) {
                 const uint8_t* p = buf + tok_start[t];
                 uint32_t bits = 0;
-                const int rc = vec_parse_f32(p, vec_tok_len(p), &bits);
+                const int rc = vec_parse_f32(p, seq_tok_len(p), &bits);
                 if (rc == VEC_PARSE_BAD) atomicMin(bad_at, (unsigned long long)tok_start[t]);
                 else if (id >= 0) {
                     if (rc == VEC_PARSE_OK) out[id * dim + col] = bits;
@@ -145,7 +129,7 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_vec_dups(const unsigned long long
 struct VecHostFlag { const uint8_t* status; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n ? status[i] : 0; } };
 struct VecHostLen {      // bytes of host token k in the blob, its NUL included
     const uint8_t* buf; const int64_t* tok_start; const int64_t* host_tok; int64_t P, n;
-    __device__ int64_t operator()(int64_t k) const { return k < n ? vec_tok_len(buf + tok_start[P + host_tok[k]]) + 1 : 0; }
+    __device__ int64_t operator()(int64_t k) const { return k < n ? seq_tok_len(buf + tok_start[P + host_tok[k]]) + 1 : 0; }
 };
 
 __global__ void __launch_bounds__(SEQ_BLOCK) k_vec_host_bytes(const uint8_t* buf, const int64_t* tok_start, const int64_t* host_tok, const int64_t* host_off, int64_t P, int64_t n,
@@ -167,46 +151,8 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_vec_scatter(const int64_t* host_t
     out[(int64_t)ent_id[P + r - hdrx[r]] * dim + (t - row_first[r] - 1)] = host_bits[k];
 }
 
-// one lane: where[0] = newlines in [lo, at), where[1] = bytes between the start of at's line (or lo) and at.  The lane walks inside three chunks at the most,
-// however long the line is: the chunks of lo and of at for the counts, and the chunk that holds the last newline in front of at, which the scanned
-// per-chunk counts give by bisection (the last chunk with fewer newlines in front of it than at has).
-__global__ void k_vec_locate(const uint8_t* buf, const int64_t* chunk_nlx, int64_t lo, int64_t at, int64_t* where) {
-    int64_t nl[2];
-    const int64_t pos[2] = {lo, at};
-    for (int i = 0; i < 2; i++) {
-        const int64_t c = pos[i] / SEQ_CHUNK;
-        nl[i] = chunk_nlx[c];
-        for (int64_t b = c * SEQ_CHUNK; b < pos[i]; b++) nl[i] += buf[b] == '\n';
-    }
-    int64_t b = lo;                                      // no newline in [lo, at): the line starts with the piece
-    if (nl[1] > nl[0]) {
-        int64_t c = 0, hi = at / SEQ_CHUNK + 1;          // chunk_nlx[0] = 0 < nl[1]; the newline sought lies in front of at
-        while (hi - c > 1) { const int64_t mid = (c + hi) >> 1; if (chunk_nlx[mid] < nl[1]) c = mid; else hi = mid; }
-        b = at < (c + 1) * SEQ_CHUNK ? at : (c + 1) * SEQ_CHUNK;
-        while (b > c * SEQ_CHUNK && buf[b - 1] != '\n') b--;
-    }
-    where[0] = nl[1] - nl[0];
-    where[1] = at - b;
-}
-
 // ------------------------------------------------------------------------------------------ host side of one read
 namespace {
-
-// "offset O of the text (piece K[, path]), line L, column C" for a buffer offset; line and column count from 1 inside the piece
-std::string vec_where(SeqRun& R, int64_t at) {
-    size_t piece = 0;
-    const int64_t off = seq_text_offset(R, at, &piece);
-    int64_t where[2] = {0, 0};
-    dge_tmp<int64_t> d;
-    if (seq_alloc(R, d, 2, "a position") == DGE_OK) {
-        hipLaunchKernelGGL(k_vec_locate, dim3(1), dim3(1), 0, R.stream, R.buf.p, R.chunk_nlx.p, R.L.offset[piece], at, d.p);
-        (void)seq_read_back(R, where, d.p, sizeof(where));
-    }
-    char msg[512];
-    snprintf(msg, sizeof(msg), "offset %lld of the text (piece %lld%s%s), line %lld, column %lld", (long long)off, (long long)piece, R.pieces[piece].path ? ", " : "",
-             R.pieces[piece].path ? R.pieces[piece].path : "", (long long)where[0] + 1, (long long)where[1] + 1);
-    return msg;
-}
 
 int vec_token_offset(SeqRun& R, int64_t t, int64_t* at) { return seq_read_back(R, at, R.tok_start.p + t, 8); }
 
@@ -252,7 +198,7 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
     if (w[0] != ~0ull) {
         int64_t at = 0, count = 0;
         SEQ_TRY(row_offset((int64_t)w[0], &at, &count));
-        DGE_FAIL(DGE_ERR_IO, "%s: the header line at %s is not two unsigned decimal integers \"V D\" (it has %lld tokens)", who, vec_where(R, at).c_str(), (long long)count);
+        DGE_FAIL(DGE_ERR_IO, "%s: the header line at %s is not two unsigned decimal integers \"V D\" (it has %lld tokens)", who, seq_where(R, at).c_str(), (long long)count);
     }
     // ---- dim: the first row's token count less the name
     const int64_t n_data = rows - n_hdr;
@@ -261,7 +207,7 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
         int64_t at = 0, count = 0;
         SEQ_TRY(row_offset((int64_t)w[1], &at, &count));
         dim = count - 1;
-        if (dim < 1) DGE_FAIL(DGE_ERR_IO, "%s: the row at %s has 1 token where at least 2 are expected: a name and its values", who, vec_where(R, at).c_str());
+        if (dim < 1) DGE_FAIL(DGE_ERR_IO, "%s: the row at %s has 1 token where at least 2 are expected: a name and its values", who, seq_where(R, at).c_str());
         if (dim > 0x7fffffffLL) DGE_FAIL(DGE_ERR_RANGE, "%s: %lld values a row do not fit an int32 dim", who, (long long)dim);
         SEQ_TRY(seq_kernels_begin(R));
         hipLaunchKernelGGL(k_vec_ragged, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, R.row_first.p, is_hdr.p, rows, dim + 1, words.p + 2);
@@ -269,7 +215,7 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
         SEQ_TRY(seq_read_back(R, w + 2, words.p + 2, 8));
         if (w[2] != ~0ull) {
             SEQ_TRY(row_offset((int64_t)w[2], &at, &count));
-            DGE_FAIL(DGE_ERR_IO, "%s: the row at %s has %lld tokens where %lld are expected (a name and %lld values, as on the first row)", who, vec_where(R, at).c_str(),
+            DGE_FAIL(DGE_ERR_IO, "%s: the row at %s has %lld tokens where %lld are expected (a name and %lld values, as on the first row)", who, seq_where(R, at).c_str(),
                      (long long)count, (long long)(dim + 1), (long long)dim);
         }
     } else if (header) {
@@ -308,12 +254,12 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
     }
     SEQ_TRY(seq_kernels_end(R));
     SEQ_TRY(seq_read_back(R, w + 3, words.p + 3, 24));
-    if (w[3] != ~0ull) DGE_FAIL(DGE_ERR_IO, "%s: the value token at %s is not a decimal number, inf or nan", who, vec_where(R, (int64_t)w[3]).c_str());
+    if (w[3] != ~0ull) DGE_FAIL(DGE_ERR_IO, "%s: the value token at %s is not a decimal number, inf or nan", who, seq_where(R, (int64_t)w[3]).c_str());
     if (w[4] != ~0ull) {
         int64_t t = 0, at = 0;
         SEQ_TRY(seq_read_back(R, &t, ent_tok.p + (int64_t)w[4], 8));
         SEQ_TRY(vec_token_offset(R, t, &at));
-        DGE_FAIL(DGE_ERR_IO, "%s: the name of the row at %s occurred on an earlier row: a name may have one vector", who, vec_where(R, at).c_str());
+        DGE_FAIL(DGE_ERR_IO, "%s: the name of the row at %s occurred on an earlier row: a name may have one vector", who, seq_where(R, at).c_str());
     }
     if (header) {
         int64_t next = rows;

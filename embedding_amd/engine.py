@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import EvalResult, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, EvalResult, OdInfo, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -35,6 +35,46 @@ class DeviceGraph:
             self._h = None
 
     __del__ = close
+
+    @classmethod
+    def from_od(cls, paths_or_list_of_bytes, names=True, device=0):
+        """.od flow text -> (graph, names, info): one "src dst w" line per flow, one piece per time slice, parsed and turned into the layered graph on the
+        device (include/dge.h: dge_graph_add_od_files / dge_graph_add_od_texts) under the rule of io.read_od_slices; the edges never visit the host.
+        paths_or_list_of_bytes: a path (one slice: the static graph), a sequence of paths, or a sequence of texts as bytes / bytearray / memoryview — slice h
+        is entry h.  names=True: a new Names receives the T*R vertex names "<h>-<region id>" in vertex-id order; an empty Names of the caller's is filled
+        instead; False / None: no names (None is returned in their place).  The graph has its edges, its reserved vertices and its sources: build_alias
+        is next.  info: the fields of struct dge_od_info."""
+        if names is True:
+            names = Names()
+        elif not names and not isinstance(names, Names):
+            names = None
+        g = cls(device)
+        inf = OdInfo()
+        nh = names._h if names is not None else None
+        pieces = paths_or_list_of_bytes
+        if isinstance(pieces, (str, os.PathLike)):
+            pieces = [pieces]
+        pieces = list(pieces)
+        if pieces and all(isinstance(p, (bytes, bytearray, memoryview)) for p in pieces):
+            views = [np.frombuffer(p, np.uint8) for p in pieces]
+            ptrs = (C.c_void_p * len(views))(*[v.ctypes.data if v.size else None for v in views])
+            sizes = (C.c_int64 * len(views))(*[v.size for v in views])
+            check(lib.dge_graph_add_od_texts(g._h, ptrs, sizes, len(views), nh, C.byref(inf)))
+        else:
+            arr = (C.c_char_p * len(pieces))(*[os.fsencode(p) for p in pieces])
+            check(lib.dge_graph_add_od_files(g._h, arr, len(pieces), nh, C.byref(inf)))
+        return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
+
+    def regions(self):
+        """The R region ids of a graph made by from_od, ascending int64 (vertex h*R + i is region regions()[i] in slice h); empty for any other graph."""
+        n = C.c_int64(0)
+        rc = lib.dge_graph_regions(self._h, None, 0, C.byref(n))          # a size query: DGE_ERR_CAP with n set when there are regions
+        if rc not in (0, DGE_ERR_CAP):
+            check(rc)
+        out = np.empty(n.value, np.int64)
+        if n.value:
+            check(lib.dge_graph_regions(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     def set_stream(self, stream_ptr):
         check(lib.dge_graph_set_stream(self._h, C.c_void_p(int(stream_ptr))))

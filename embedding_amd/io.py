@@ -4,6 +4,7 @@
 .vec  "name v1 .. vD" per vocabulary row, no header              J/DeepWalk.java:82, P/embeddingEvaluation_tract.py:298-300
       LINE-style variant with a "V D" first line                 miscs/taxi_all.txt:1, P/embeddingEvaluation_tract.py:113-117
 .od   "src dst w" per line, one file per time slice              J/Tracts.java:236-264, J/CommunityAreas.java:171-186
+      (on the device: engine.DeviceGraph.from_od; read_od_slices below is the host-side second reading)
 """
 import numpy as np
 

@@ -110,6 +110,52 @@ int  dge_graph_get_source_alias(const dge_graph* g, double* prob, int32_t* alias
 /* Vertex.sampleNextVertex(double x)  J/LayeredGraph.java:123-132 (test overload); *next = -1 when the
  * vertex has no out-edges.  Runs the device sampler for one explicit x. */
 int  dge_graph_sample_next(const dge_graph* g, int32_t v, double x, int32_t* next);
+/* ---- .od flow text in (new; additions only, DGE_VERSION unchanged): the files at the front of the pipeline, one "src dst w" line per flow and one file per
+ * time slice (written J/Tracts.java:236-264, J/CommunityAreas.java:127-146,171-186), become the layered graph on the device (csrc/od_read.hip).  The rule is
+ * that of embedding_amd/io.py: read_od_slices (J/CrossTimeGraph.java:25-52,68-95):
+ *   - Piece h of n_slices = T pieces (a file, or a text) is slice h.  A line with a token is a FLOW "src dst w": two region ids and a weight.  A flow with w > 0
+ *     is an edge; every other flow — w == 0 (J/CommunityAreas.java:178 writes them), -0, a negative weight — is dropped and counted (info.dropped).
+ *   - REGIONS are the distinct region ids that occur in a kept flow of any slice, ascending as signed 64-bit integers: R of them, rank(r) the index of r.
+ *   - A kept flow of slice h is the edge  h*R + rank(src)  ->  ((h + 1) % T)*R + rank(dst)  of weight w.  Edges stand in the order of the text, piece after piece,
+ *     line after line; duplicates are kept (the per-vertex edge order, and with it the alias tables, follow from that order).  T*R vertices are reserved;
+ *     T*R > 2^31 - 1: DGE_ERR_RANGE.  T == 1 gives the static graph of one file (taxi-all.od): its edges stay inside the layer.
+ *   - SOURCES: every layer-0 vertex that is an endpoint of some edge, ascending, set as dge_graph_set_sources(.., stream_sum = 0) sets them — a region that
+ *     is only a destination of slice T-1 is a source of weight 0.
+ *   - The text is BYTES; whitespace, lines, pieces and NUL are what they are to the .seq and .vec readers: whitespace is 0x09-0x0D and 0x20, the last line may
+ *     lack its '\n', no token and no line crosses a piece, a line without a token is skipped, a NUL byte is DGE_ERR_IO naming its offset.
+ *   - Errors of the text, the first applicable wins: a NUL byte; a RAGGED LINE — a token count that is neither 0 nor 3: DGE_ERR_IO naming the least such
+ *     (piece, line), the count found and the count expected; a BAD TOKEN: DGE_ERR_IO naming the least byte offset of one, with its piece, line and column.
+ *     An id token is [+-] digits with a value in the int64 range (leading zeros allowed: 007 is region 7).  A weight token is a value token of the .vec grammar
+ *     below; its value is the binary64 nearest the exact decimal value, ties to even — what glibc's strtod returns in the "C" locale, for tokens of any length
+ *     (csrc/od_parse.h decides every integer of up to 19 digits and most else on the device; the few tokens it hands back are finished by the host with strtod
+ *     and counted in info.host_values).  A weight that is not finite — inf, nan, overflow — is a bad token; underflow to 0 is w == 0, so the flow is dropped.
+ *   - g must be fresh: one that already holds edges, sources or reserved vertices is DGE_ERR_STATE.  On success g stands where a host stands after
+ *     dge_graph_add_edges, dge_graph_reserve_vertices and dge_graph_set_sources; dge_graph_build_alias is next.
+ *   - names (may be NULL) must be empty, else DGE_ERR_ARG; it receives the T*R vertex names "<h>-<region id in decimal>" in vertex-id order — what
+ *     dge_walks_write_seq and dge_write_vec take.
+ *   - Null / negative arguments, n_slices < 1, names not empty: DGE_ERR_ARG before a device is looked for.  A file that is missing or unreadable: DGE_ERR_IO with
+ *     its path.  A working set beyond device memory: DGE_ERR_CAP.  On any error g and names are as they were.
+ *   - The result is a pure function of the bytes: nothing depends on timing or launch geometry. */
+struct dge_names;
+typedef struct dge_od_info {
+    int64_t bytes;        /* bytes of text taken (the pieces' sizes added up)                            */
+    int64_t lines;        /* lines, a last one without '\n' included                                      */
+    int64_t flows;        /* lines with a token                                                           */
+    int64_t edges;        /* flows kept: w > 0                                                            */
+    int64_t dropped;      /* flows - edges: w <= 0                                                        */
+    int64_t regions;      /* R                                                                            */
+    int64_t sources;      /* layer-0 vertices that are an endpoint of an edge                             */
+    int64_t host_values;  /* weight tokens the host finished with strtod                                  */
+    int32_t slices;       /* T                                                                            */
+    int32_t reserved;
+    double  read_ms;      /* bytes to the device (file reads included)                                    */
+    double  kernel_ms;    /* the device passes                                                            */
+} dge_od_info;            /* 88 bytes */
+int  dge_graph_add_od_files(dge_graph* g, const char* const* paths, int32_t n_slices, struct dge_names* names /* may be NULL */, dge_od_info* info /* may be NULL */);
+int  dge_graph_add_od_texts(dge_graph* g, const char* const* texts, const int64_t* n_bytes, int32_t n_slices, struct dge_names* names, dge_od_info* info);
+/* the R region ids of a graph made by the two entries above, ascending (vertex h*R + i is region regions[i] in slice h); *n = 0 for a graph not made this way;
+ * cap too small: DGE_ERR_CAP with *n set.  A host read: no device involved. */
+int  dge_graph_regions(const dge_graph* g, int64_t* regions, int64_t cap, int64_t* n);
 
 /* ------------------------------------------------------------------------------------------------
  * Walk sampler — replaces sampleVertexSequence() J/LayeredGraph.java:232-252 and the writer loops
