@@ -62,6 +62,26 @@ class OdInfo(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class RegionsInfo(C.Structure):
+    """struct dge_regions_info (include/dge.h)."""
+    _fields_ = [("regions", C.c_int64), ("rings", C.c_int64), ("segments", C.c_int64), ("max_cell_candidates", C.c_int64), ("grid", C.c_int32),
+                ("tile_segments", C.c_int32), ("x0", C.c_double), ("y0", C.c_double), ("x1", C.c_double), ("y1", C.c_double)]
+
+
+class LocateInfo(C.Structure):
+    """struct dge_locate_info (include/dge.h) — what dge_regions_locate / dge_regions_locate_device report."""
+    _fields_ = [("points", C.c_int64), ("located", C.c_int64), ("on_boundary", C.c_int64), ("multi", C.c_int64), ("outside", C.c_int64), ("exact", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
+class FlowsInfo(C.Structure):
+    """struct dge_flows_info (include/dge.h) — accumulated over the calls that added trips."""
+    _fields_ = [("trips", C.c_int64), ("mapped", C.c_int64), ("bad", C.c_int64), ("no_start", C.c_int64), ("no_end", C.c_int64), ("entries", C.c_int64),
+                ("located", C.c_int64), ("on_boundary", C.c_int64), ("multi", C.c_int64), ("outside", C.c_int64), ("exact", C.c_int64), ("kernel_ms", C.c_double)]
+
+
+DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
+
 # every symbol include/dge.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int
 _P = C.POINTER
@@ -90,6 +110,19 @@ SIGNATURES = {
     "dge_graph_add_od_files": (_int, [_vp, _vp, _i32, _vp, _P(OdInfo)]),
     "dge_graph_add_od_texts": (_int, [_vp, _vp, _vp, _i32, _vp, _P(OdInfo)]),
     "dge_graph_regions": (_int, [_vp, _vp, _i64, _P(_i64)]),
+    "dge_regions_create": (_int, [_int, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _P(_vp)]),
+    "dge_regions_info": (_int, [_vp, _P(RegionsInfo)]),
+    "dge_regions_locate": (_int, [_vp, _vp, _i64, _vp, _P(LocateInfo)]),
+    "dge_regions_locate_device": (_int, [_vp, _vp, _i64, _vp, _P(LocateInfo)]),
+    "dge_regions_free": (None, [_vp]),
+    "dge_flows_create": (_int, [_vp, _P(_vp)]),
+    "dge_flows_add_trips": (_int, [_vp, _vp, _vp, _vp, _i64]),
+    "dge_flows_add_trips_device": (_int, [_vp, _vp, _vp, _vp, _i64]),
+    "dge_flows_info": (_int, [_vp, _P(FlowsInfo)]),
+    "dge_flows_to_host": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
+    "dge_flows_slot_edges": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
+    "dge_flows_free": (None, [_vp]),
+    "dge_graph_add_flows": (_int, [_vp, _vp, _i32, _i32, _vp, _P(OdInfo)]),
     "dge_sample_walks": (_int, [_vp, _i64, _i32, _i64, _int, _i64, _vp, _P(_i64)]),
     "dge_sample_walks_device": (_int, [_vp, _i64, _i32, _i64, _int, _i64, _P(_vp), _P(_i64)]),
     "dge_sample_walks_into": (_int, [_vp, _vp, _i64, _i64, _i64, _i64]),

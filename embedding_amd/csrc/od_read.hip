@@ -12,6 +12,7 @@
 //   host path                  the flagged tokens' bytes in one blob, strtod in the "C" locale, k_od_scatter puts the bits in place
 //   k_od_keep                  a weight that is not finite is a bad token; keep[r] = w > 0
 //   scan of keep               a stable compaction: kept flow r is edge keepx[r], edges stand in text order
+//   od_commit.h, which dge_graph_add_flows (trip_map.hip) runs too:
 //   k_od_endpoints, radix sort, k_od_unique around a scan
 //                              the kept endpoints' ids sorted as signed 64-bit integers, each distinct one once: the R regions, ascending
 //   k_od_edges                 rank by binary search -> d_coo_src / d_coo_dst / d_coo_w of the graph, edge h*R + rank(src) -> ((h+1) % T)*R + rank(dst);
@@ -29,8 +30,7 @@
 #include <locale.h>
 #include <stdlib.h>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
+#include "od_commit.h"
 #include "od_parse.h"
 #include "seq_tokens.h"
 
@@ -102,66 +102,8 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_od_keep(const uint64_t* w_bits, c
     keep[r] = (b >> 63) == 0 && mag != 0 ? 1 : 0;
 }
 
-struct OdKeepFlag { const uint8_t* keep; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n ? keep[i] : 0; } };
-
-// the ids of the kept flows' endpoints: edge e's at [2e], [2e + 1]
-__global__ void __launch_bounds__(SEQ_BLOCK) k_od_endpoints(const int64_t* src_id, const int64_t* dst_id, const int64_t* keepx, int64_t rows, int64_t* ends) {
-    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (r >= rows || keepx[r + 1] == keepx[r]) return;
-    const int64_t e = keepx[r];
-    ends[2 * e] = src_id[r]; ends[2 * e + 1] = dst_id[r];
-}
-
-struct OdNewFlag { const int64_t* sorted; int64_t n; __device__ int64_t operator()(int64_t i) const { return (i < n && (i == 0 || sorted[i] != sorted[i - 1])) ? 1 : 0; } };
-
-__global__ void __launch_bounds__(SEQ_BLOCK) k_od_unique(const int64_t* sorted, const int64_t* newx, int64_t n, int64_t* regions) {
-    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (i < n && newx[i + 1] != newx[i]) regions[newx[i]] = sorted[i];
-}
-
-__device__ __forceinline__ int64_t od_rank(const int64_t* regions, int64_t R, int64_t id) {      // id is among the regions
-    int64_t lo = 0, hi = R;
-    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (regions[mid] <= id) lo = mid; else hi = mid; }
-    return lo;
-}
-
-// kept flow r of slice h -> edge keepx[r]: h*R + rank(src) -> ((h + 1) % T)*R + rank(dst); mark[i] = 1 for every layer-0 vertex i that is an endpoint
-__global__ void __launch_bounds__(SEQ_BLOCK) k_od_edges(const int64_t* src_id, const int64_t* dst_id, const uint64_t* w_bits, const int32_t* slice, const int64_t* keepx,
-                                                        int64_t rows, const int64_t* regions, int64_t R, int64_t T, int32_t* coo_src, int32_t* coo_dst, double* coo_w,
-                                                        uint8_t* mark) {
-    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (r >= rows || keepx[r + 1] == keepx[r]) return;
-    const int64_t e = keepx[r], h = slice[r], h1 = h + 1 == T ? 0 : h + 1;
-    const int64_t rs = od_rank(regions, R, src_id[r]), rd = od_rank(regions, R, dst_id[r]);
-    coo_src[e] = (int32_t)(h * R + rs);
-    coo_dst[e] = (int32_t)(h1 * R + rd);
-    coo_w[e] = __longlong_as_double((long long)w_bits[r]);
-    if (h == 0) mark[rs] = 1;
-    if (h1 == 0) mark[rd] = 1;
-}
-
-__global__ void __launch_bounds__(SEQ_BLOCK) k_od_sources(const int64_t* markx, int64_t R, int32_t* srcv) {
-    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (i < R && markx[i + 1] != markx[i]) srcv[markx[i]] = (int32_t)i;
-}
-
 // ------------------------------------------------------------------------------------------ host side of one read
 namespace {
-
-bool od_fresh(const dge_graph* g) { return g->n_coo == 0 && g->max_id < 0 && g->S == 0 && !g->d_srcv && g->od_regions.empty(); }
-
-// back to what dge_graph_create left: everything this call put into g goes
-void od_reset(dge_graph* g) {
-    void* mine[] = {g->d_coo_src, g->d_coo_dst, g->d_coo_w, g->d_row_ptr, g->d_nbr, g->d_w, g->d_outdeg, g->d_prob, g->d_alias, g->d_slots,
-                    g->d_srcv, g->d_src_w, g->d_src_prob, g->d_src_alias, g->d_src_slots};
-    for (void* p : mine) dge_dev_free(p);
-    g->d_coo_src = g->d_coo_dst = nullptr; g->d_coo_w = nullptr; g->n_coo = g->cap_coo = 0; g->max_id = -1;
-    g->d_row_ptr = nullptr; g->d_nbr = nullptr; g->d_w = nullptr; g->d_outdeg = nullptr; g->d_prob = nullptr; g->d_alias = nullptr; g->d_slots = nullptr;
-    g->csr_built = g->alias_built = false; g->V = 0; g->E = 0;
-    g->d_srcv = nullptr; g->d_src_w = nullptr; g->d_src_prob = nullptr; g->d_src_alias = nullptr; g->d_src_slots = nullptr;
-    g->S = 0; g->src_weight_sum = 0.0; g->src_stream_sum = 0; g->src_sum_fixed = false;
-    g->od_regions.clear();
-}
 
 int od_read(SeqRun& R, dge_graph* g, dge_names* names, dge_od_info* info, const char* who) {
     R.what = "od read";
@@ -249,104 +191,12 @@ int od_read(SeqRun& R, dge_graph* g, dge_names* names, dge_od_info* info, const 
     seq_release(R, status, rows);
     seq_release(R, keep, rows);
 
-    // ---- the regions: the kept endpoints' ids, sorted, each once
-    int64_t n_regions = 0;
-    dge_tmp<int64_t> regions;
-    {
-        dge_tmp<int64_t> ends, sorted, newx;
-        dge_tmp<uint8_t> tmp;
-        SEQ_TRY(seq_alloc(R, ends, 2 * E, "the endpoints"));
-        SEQ_TRY(seq_alloc(R, sorted, 2 * E, "the sorted endpoints"));
-        SEQ_TRY(seq_alloc(R, newx, 2 * E + 1, "the regions' numbers"));
-        size_t bytes = 0;
-        if (E) DGE_HIP(rocprim::radix_sort_keys(nullptr, bytes, ends.p, sorted.p, (size_t)(2 * E), 0, 64, R.stream));
-        SEQ_TRY(seq_alloc(R, tmp, (int64_t)bytes, "the sort's scratch"));
-        SEQ_TRY(seq_kernels_begin(R));
-        if (E) {
-            hipLaunchKernelGGL(k_od_endpoints, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, src_id.p, dst_id.p, keepx.p, rows, ends.p);
-            DGE_HIP(rocprim::radix_sort_keys((void*)tmp.p, bytes, ends.p, sorted.p, (size_t)(2 * E), 0, 64, R.stream));
-        }
-        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdNewFlag{sorted.p, 2 * E}), newx.p, 2 * E + 1));
-        SEQ_TRY(seq_kernels_end(R));
-        SEQ_TRY(seq_read_back(R, &n_regions, newx.p + 2 * E, 8));
-        if (T * n_regions > 0x7fffffffLL)
-            DGE_FAIL(DGE_ERR_RANGE, "%s: %lld slices of %lld regions are %lld vertices, which do not fit int32 ids", who, (long long)T, (long long)n_regions, (long long)(T * n_regions));
-        SEQ_TRY(seq_alloc(R, regions, n_regions, "the regions"));
-        SEQ_TRY(seq_kernels_begin(R));
-        if (E) hipLaunchKernelGGL(k_od_unique, dim3(seq_grid(2 * E)), dim3(SEQ_BLOCK), 0, R.stream, sorted.p, newx.p, 2 * E, regions.p);
-        SEQ_TRY(seq_kernels_end(R));
-        seq_release(R, ends, 2 * E); seq_release(R, sorted, 2 * E); seq_release(R, newx, 2 * E + 1); seq_release(R, tmp, (int64_t)bytes);
-    }
-    const int64_t Rn = n_regions;
-
-    // ---- the edges into the graph's own staging, the layer-0 endpoints
-    dge_tmp<int32_t> coo_src, coo_dst, srcv;
-    dge_tmp<double> coo_w;
-    dge_tmp<uint8_t> mark;
-    dge_tmp<int64_t> markx;
-    SEQ_TRY(seq_alloc(R, coo_src, E, "the edges' sources"));
-    SEQ_TRY(seq_alloc(R, coo_dst, E, "the edges' destinations"));
-    SEQ_TRY(seq_alloc(R, coo_w, E, "the edges' weights"));
-    SEQ_TRY(seq_alloc(R, mark, Rn, "the layer-0 vertices"));
-    SEQ_TRY(seq_alloc(R, markx, Rn + 1, "the layer-0 vertices' numbers"));
-    SEQ_TRY(seq_kernels_begin(R));
-    DGE_HIP(hipMemsetAsync(mark.p, 0, (size_t)std::max<int64_t>(Rn, 1), R.stream));
-    if (E) hipLaunchKernelGGL(k_od_edges, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, src_id.p, dst_id.p, w_bits.p, slice.p, keepx.p, rows, regions.p, Rn, T, coo_src.p, coo_dst.p,
-                              coo_w.p, mark.p);
-    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdKeepFlag{mark.p, Rn}), markx.p, Rn + 1));
-    SEQ_TRY(seq_kernels_end(R));
-    int64_t S = 0;
-    SEQ_TRY(seq_read_back(R, &S, markx.p + Rn, 8));
-    SEQ_TRY(seq_alloc(R, srcv, S, "the sources"));
-    SEQ_TRY(seq_kernels_begin(R));
-    if (Rn) hipLaunchKernelGGL(k_od_sources, dim3(seq_grid(Rn)), dim3(SEQ_BLOCK), 0, R.stream, markx.p, Rn, srcv.p);
-    SEQ_TRY(seq_kernels_end(R));
-    std::vector<int64_t> host_regions((size_t)Rn);
-    std::vector<int32_t> host_srcv((size_t)S);
-    if (Rn) SEQ_TRY(seq_read_back(R, host_regions.data(), regions.p, (size_t)Rn * 8));
-    if (S) SEQ_TRY(seq_read_back(R, host_srcv.data(), srcv.p, (size_t)S * 4));
-    DGE_HIP(hipStreamSynchronize(R.stream));
-    DGE_HIP(hipGetLastError());
-
-    // ---- the names "<h>-<region id>" in vertex-id order: the host formats them, R is small against E
-    std::vector<int64_t> off;
-    std::unique_ptr<char[]> name_blob;
-    if (names) {
-        std::string all;
-        off.reserve((size_t)(T * Rn) + 1);
-        char one[48];
-        for (int64_t h = 0; h < T; h++)
-            for (int64_t i = 0; i < Rn; i++) {
-                off.push_back((int64_t)all.size());
-                const int len = snprintf(one, sizeof(one), "%lld-%lld", (long long)h, (long long)host_regions[(size_t)i]);
-                all.append(one, (size_t)len + 1);
-            }
-        off.push_back((int64_t)all.size());
-        name_blob.reset(new char[all.size() + 1]);
-        memcpy(name_blob.get(), all.data(), all.size());
-    }
-
-    // ---- the graph takes the edges over, then stands where a host stands after add_edges, reserve_vertices and set_sources
-    od_reset(g);                                   // (a fresh graph may hold an empty CSR from a read-back: set_sources must build the real one)
-    g->d_coo_src = coo_src.release(); g->d_coo_dst = coo_dst.release(); g->d_coo_w = coo_w.release();
-    g->n_coo = E; g->cap_coo = std::max<int64_t>(E, 1);
-    g->max_id = (int32_t)(T * Rn) - 1;
-    const int rc = dge_graph_set_sources(g, host_srcv.data(), S, 0);
-    if (rc) { od_reset(g); return rc; }
-    // nothing can fail from here on
-    g->od_regions = std::move(host_regions);
-    if (names && T * Rn > 0) names_append(names, std::move(name_blob), off.data(), T * Rn);
+    int64_t Rn = 0, S = 0;
+    SEQ_TRY(od_commit(R, g, names, rows, E, T, src_id.p, dst_id.p, w_bits.p, slice.p, keepx.p, who, &Rn, &S));
     if (info) {
         info->bytes = R.L.text_bytes; info->lines = R.lines; info->flows = rows; info->edges = E; info->dropped = rows - E; info->regions = Rn; info->sources = S;
         info->host_values = n_host; info->slices = (int32_t)T; info->reserved = 0; info->read_ms = R.read_ms; info->kernel_ms = R.kernel_ms;
     }
-    return DGE_OK;
-}
-
-// what both entries check before a device is looked for (the pieces' own arguments are the caller's)
-int od_check(const dge_graph* g, const dge_names* names, const char* who) {
-    if (names && !names->ptr.empty()) DGE_FAIL(DGE_ERR_ARG, "%s: names must be empty: it receives the vertex names, it holds %lld", who, (long long)names->ptr.size());
-    if (!od_fresh(g)) DGE_FAIL(DGE_ERR_STATE, "%s: the graph must be fresh: it already holds edges, sources or reserved vertices", who);
     return DGE_OK;
 }
 

@@ -435,7 +435,7 @@ int64_t seq_text_offset(const SeqRun& R, int64_t at, size_t* piece) {
 struct SeqOptions { int32_t hash_bits = 64; int64_t initial_slots = 0; int intern = 1; };
 
 // bytes to the device, tokens (first byte, line), rows (rowx, row_first, max_len)
-int seq_tokenise(SeqRun& R, const dge_names* names, const char* who) {
+[[maybe_unused]] int seq_tokenise(SeqRun& R, const dge_names* names, const char* who) {
     using clock = std::chrono::steady_clock;
     // ---- layout
     std::string prefix;

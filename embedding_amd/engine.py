@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, EvalResult, OdInfo, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -63,6 +63,19 @@ class DeviceGraph:
         else:
             arr = (C.c_char_p * len(pieces))(*[os.fsencode(p) for p in pieces])
             check(lib.dge_graph_add_od_files(g._h, arr, len(pieces), nh, C.byref(inf)))
+        return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
+
+    @classmethod
+    def from_flows(cls, flows, T, mode=DGE_SLOTS_EVEN, names=True):
+        """A Flows table -> (graph, names, info): the slot edges of (T, mode) become the layered graph on the device (include/dge.h: dge_graph_add_flows), exactly
+        the graph from_od gives for flows.to_od_bytes(T, mode), with no text in between.  names as in from_od."""
+        if names is True:
+            names = Names()
+        elif not names and not isinstance(names, Names):
+            names = None
+        g = cls(flows.regions.device)
+        inf = OdInfo()
+        check(lib.dge_graph_add_flows(g._h, flows._h, int(T), int(mode), names._h if names is not None else None, C.byref(inf)))
         return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
 
     def regions(self):
@@ -172,6 +185,130 @@ class DeviceGraph:
 
     def sample_walks_into(self, corpus, row0, n_walks, seed, first_index):
         check(lib.dge_sample_walks_into(self._h, corpus._h, int(row0), int(n_walks), int(seed), int(first_index)))
+
+
+def _info_dict(inf):
+    return {f[0]: getattr(inf, f[0]) for f in inf._fields_}
+
+
+class Regions:
+    """Region rings with their cell index in HBM (struct dge_regions, include/dge.h): what Tracts / CommunityAreas hold as JTS MultiPolygons
+    (J/Tracts.java:26-43).  Points are located by the exact ray-crossing rule of csrc/pip_exact.h."""
+
+    def __init__(self, handle, device):
+        self._h = handle
+        self.device = int(device)
+
+    @classmethod
+    def from_arrays(cls, ids, ring_first, vert_first, xy, grid=0, device=0):
+        """ids int64 [R]; ring_first int64 [R + 1]; vert_first int64 [rings + 1]; xy float64 [verts, 2] (x = longitude, y = latitude).  grid: 0 = the library's
+        rule, n > 0 = n x n cells; the result does not depend on it."""
+        ids = np.ascontiguousarray(ids, np.int64); ring_first = np.ascontiguousarray(ring_first, np.int64)
+        vert_first = np.ascontiguousarray(vert_first, np.int64); xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        if len(ring_first) != len(ids) + 1 or len(vert_first) < 1:
+            raise ValueError("ring_first has R + 1 entries, vert_first rings + 1")
+        h = C.c_void_p(0)
+        check(lib.dge_regions_create(int(device), _ptr(ids), len(ids), _ptr(ring_first), _ptr(vert_first), _ptr(xy), len(vert_first) - 1, len(xy), int(grid), C.byref(h)))
+        return cls(h, device)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.dge_regions_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def info(self):
+        inf = RegionsInfo()
+        check(lib.dge_regions_info(self._h, C.byref(inf)))
+        return _info_dict(inf)
+
+    def locate(self, xy, return_info=False):
+        """xy: numpy float64 [n, 2] -> numpy int32 [n]; or a torch float64 tensor on this device -> a torch int32 tensor there.  -1: in no region."""
+        inf = LocateInfo()
+        if isinstance(xy, np.ndarray) or not hasattr(xy, "data_ptr"):
+            xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+            out = np.empty(len(xy), np.int32)
+            check(lib.dge_regions_locate(self._h, _ptr(xy), len(xy), _ptr(out), C.byref(inf)))
+        else:
+            import torch
+            xy = xy.contiguous()
+            if xy.dtype != torch.float64 or not xy.is_cuda:
+                raise ValueError("a device tensor of float64 is expected")
+            out = torch.empty(xy.numel() // 2, dtype=torch.int32, device=xy.device)
+            torch.cuda.synchronize(xy.device)
+            check(lib.dge_regions_locate_device(self._h, _dev_ptr(xy), xy.numel() // 2, _dev_ptr(out), C.byref(inf)))
+        return (out, _info_dict(inf)) if return_info else out
+
+
+class Flows:
+    """The table (hour, s, e) -> count in HBM (struct dge_flows, include/dge.h): what Tract.taxiFlows holds after Tracts.mapTripsIntoTracts
+    (J/Tracts.java:71-102)."""
+    EVEN, AS_TRACTS = DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS
+
+    def __init__(self, regions):
+        h = C.c_void_p(0)
+        check(lib.dge_flows_create(regions._h, C.byref(h)))
+        self._h = h
+        self.regions = regions
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.dge_flows_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add_trips(self, start_xy, end_xy, hour):
+        """numpy arrays (float64 [n, 2] twice, int32 [n]) or torch tensors of those types on the regions' device; may be called any number of times."""
+        if hasattr(start_xy, "data_ptr") and not isinstance(start_xy, np.ndarray):
+            import torch
+            s, e, h = start_xy.contiguous(), end_xy.contiguous(), hour.contiguous()
+            if s.dtype != torch.float64 or e.dtype != torch.float64 or h.dtype != torch.int32 or not (s.is_cuda and e.is_cuda and h.is_cuda):
+                raise ValueError("device tensors of float64, float64 and int32 are expected")
+            if not (s.numel() == e.numel() == 2 * h.numel()):
+                raise ValueError("start / end / hour lengths differ")
+            torch.cuda.synchronize(s.device)
+            check(lib.dge_flows_add_trips_device(self._h, _dev_ptr(s), _dev_ptr(e), _dev_ptr(h), h.numel()))
+            return
+        s = np.ascontiguousarray(start_xy, np.float64).reshape(-1, 2); e = np.ascontiguousarray(end_xy, np.float64).reshape(-1, 2)
+        h = np.ascontiguousarray(hour, np.int32)
+        if not (len(s) == len(e) == len(h)):
+            raise ValueError("start / end / hour lengths differ")
+        check(lib.dge_flows_add_trips(self._h, _ptr(s), _ptr(e), _ptr(h), len(h)))
+
+    def info(self):
+        inf = FlowsInfo()
+        check(lib.dge_flows_info(self._h, C.byref(inf)))
+        return _info_dict(inf)
+
+    def to_host(self):
+        """-> hour int32, src int32, dst int32 (region indices), count int64: ascending by (hour, src, dst)."""
+        n = self.info()["entries"]
+        hour = np.empty(n, np.int32); src = np.empty(n, np.int32); dst = np.empty(n, np.int32); count = np.empty(n, np.int64)
+        got = C.c_int64(0)
+        check(lib.dge_flows_to_host(self._h, _ptr(hour), _ptr(src), _ptr(dst), _ptr(count), n, C.byref(got)))
+        return hour, src, dst, count
+
+    def slot_edges(self, T, mode=DGE_SLOTS_EVEN):
+        """-> slot int32, src id int64, dst id int64, w int64: ascending by (slot, src id, dst id)."""
+        n = C.c_int64(0)
+        rc = lib.dge_flows_slot_edges(self._h, int(T), int(mode), None, None, None, None, 0, C.byref(n))          # a size query
+        if rc not in (0, DGE_ERR_CAP):
+            check(rc)
+        m = n.value
+        slot = np.empty(m, np.int32); src = np.empty(m, np.int64); dst = np.empty(m, np.int64); w = np.empty(m, np.int64)
+        if m:
+            check(lib.dge_flows_slot_edges(self._h, int(T), int(mode), _ptr(slot), _ptr(src), _ptr(dst), _ptr(w), m, C.byref(n)))
+        return slot, src, dst, w
+
+    def to_od_bytes(self, T, mode=DGE_SLOTS_EVEN):
+        """The T .od texts (J/Tracts.java:236-260), formatted on the host from slot_edges: the tables are small."""
+        slot, src, dst, w = self.slot_edges(T, mode)
+        out = [[] for _ in range(int(T))]
+        for k, s, d, x in zip(slot.tolist(), src.tolist(), dst.tolist(), w.tolist()):
+            out[k].append(b"%d %d %d\n" % (s, d, x))
+        return [b"".join(lines) for lines in out]
 
 
 class Names:

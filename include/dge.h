@@ -157,6 +157,96 @@ int  dge_graph_add_od_texts(dge_graph* g, const char* const* texts, const int64_
  * cap too small: DGE_ERR_CAP with *n set.  A host read: no device involved. */
 int  dge_graph_regions(const dge_graph* g, int64_t* regions, int64_t cap, int64_t* n);
 
+/* ---- trips into regions, regions into flows (new; additions only, DGE_VERSION unchanged): the stage in front of the .od files — Tracts.mapTripsIntoTracts
+ * (J/Tracts.java:71-102) and CommunityAreas.mapTripsIntoCommunities (J/CommunityAreas.java:55-103), which test every trip's pickup and drop-off point with JTS
+ * MultiPolygon.contains against every region and count taxiFlows[hour][dst] — on the device (csrc/trip_map.hip, csrc/pip_exact.h).  Arrays in, flows and a
+ * graph out: parsing trip CSVs and reading shapefiles stay with the host.  The rule; the result is a pure function of the inputs, nothing depends on timing,
+ * launch geometry or the index's cell count:
+ *   - REGIONS: region r has the id ids[r] (distinct) and the rings ring_first[r] .. ring_first[r+1]-1; ring q has the vertices vert_first[q] .. vert_first[q+1]-1
+ *     of xy (binary64, x = longitude, y = latitude, interleaved).  A ring is closed: at least 4 vertices, the last equal to the first bit for bit.  Shells and
+ *     holes are not told apart.
+ *   - LOCATION of a point p in region r: BOUNDARY when p lies on a segment of a ring of r, its vertices included; INTERIOR when not boundary and the ray from p
+ *     towards +x crosses the rings of r an odd number of times, a segment (a, b) being crossed when exactly one of a.y, b.y is > p.y and p lies strictly on the
+ *     ray's side of the line through a and b — what JTS's RayCrossingCounter decides, and on a valid MultiPolygon what contains() decides.
+ *   - The side test is the sign of (b.x-a.x)(p.y-a.y) - (b.y-a.y)(p.x-a.x) in EXACT arithmetic over the binary64 inputs (a filtered floating-point evaluation,
+ *     then error-free transformations: csrc/pip_exact.h).  DOMAIN: every coordinate is finite and either 0 or of magnitude in [2^-450, 2^500].  A ring vertex
+ *     outside the domain: DGE_ERR_ARG.  A trip point outside it: its region is -1 and the trip is bad.
+ *   - The REGION of a point is the least index r whose location is interior, else -1 (a point on a shared edge of a tiling belongs to no region, as in the
+ *     reference).
+ *   - FLOWS: trip i has a start point, an end point and an hour.  It is BAD when its hour is outside 0 .. 23 or a coordinate is outside the domain: dropped and
+ *     counted.  Otherwise, with s and e the regions of its points, it adds 1 to c(hour, s, e) when both are >= 0.  The table is the triples with c > 0,
+ *     ascending by (hour, s, e), counts int64; adding trips in several calls gives the same table, bit for bit, as adding them in one.
+ *   - SLOTS, T time slices out of the 24 hours.  DGE_SLOTS_EVEN: T divides 24, hour h belongs to slot h / (24/T); T = 1 is the static graph (taxi-all.od,
+ *     J/Tracts.java:251-260).  DGE_SLOTS_AS_TRACTS is Tracts.outputEdgeFile as written (J/Tracts.java:236-249): 1 <= T <= 24, step = 24 / T (integer division),
+ *     slot k holds for every (s, e) with c(k, s, e) > 0 the weight c(k, s, e) + .. + c(k+step-1, s, e) — the windows overlap, start at hour k, and only
+ *     destinations seen in hour k itself appear.  With T = 24 the modes agree.  A slot edge is (slot, ids[s], ids[e], w), w > 0; slot edges stand ascending by
+ *     (slot, src id, dst id).
+ *   - dge_graph_add_flows leaves g exactly where dge_graph_add_od_texts leaves it when slice k's text is the lines "%d %d %d\n" % (src id, dst id, w) of slot k
+ *     in that order: same fresh-graph and names-empty rules, same statuses, the same commit path (csrc/od_commit.h); info: bytes = lines = 0, flows = edges = the
+ *     slot edges, dropped = host_values = 0.  On error g and names are as they were.
+ *   - Null / negative arguments, an unclosed or short ring, duplicate ids, a vertex outside the domain (the message names region, ring and vertex), a T the mode
+ *     refuses: DGE_ERR_ARG before a device is looked for.  cap too small: DGE_ERR_CAP with *n set.  T*R' > 2^31-1: DGE_ERR_RANGE.  Out of device memory:
+ *     DGE_ERR_CAP.  R = 0, n = 0 and an empty table are fine.
+ * (dge_regions_info and dge_flows_info name a struct and a function each: write `struct dge_regions_info`, as C requires.) */
+typedef struct dge_regions dge_regions;   /* rings + cell index, resident in HBM */
+typedef struct dge_flows   dge_flows;     /* sorted (hour, s, e, count) table, resident in HBM; holds a reference to its regions */
+enum { DGE_SLOTS_EVEN = 0, DGE_SLOTS_AS_TRACTS = 1 };
+struct dge_regions_info {
+    int64_t regions;              /* R                                                                  */
+    int64_t rings;
+    int64_t segments;             /* ring vertices minus rings                                          */
+    int64_t max_cell_candidates;  /* the longest list of candidate regions a cell has                   */
+    int32_t grid;                 /* the index has grid x grid cells                                    */
+    int32_t tile_segments;        /* segments one LDS tile holds                                        */
+    double  x0;                   /* the bounding box of all rings: x0 <= x <= x1, y0 <= y <= y1        */
+    double  y0;
+    double  x1;
+    double  y1;
+};                                /* 72 bytes */
+typedef struct dge_locate_info {
+    int64_t points;
+    int64_t located;              /* region >= 0                                                        */
+    int64_t on_boundary;          /* region -1 and on some ring                                         */
+    int64_t multi;                /* interior to more than one region                                   */
+    int64_t outside;              /* outside every region's bounding box (out-of-domain points included) */
+    int64_t exact;                /* side tests that went past the floating-point filter                */
+    double  kernel_ms;
+} dge_locate_info;                /* 56 bytes */
+struct dge_flows_info {           /* everything accumulates over the calls that added trips             */
+    int64_t trips;
+    int64_t mapped;               /* both regions found                                                 */
+    int64_t bad;                  /* hour outside 0 .. 23 or a coordinate outside the domain            */
+    int64_t no_start;             /* not bad, no region for the start point                             */
+    int64_t no_end;               /* start found, end not                                               */
+    int64_t entries;              /* triples in the table                                               */
+    int64_t located;              /* the two points' locate counters, summed                            */
+    int64_t on_boundary;
+    int64_t multi;
+    int64_t outside;
+    int64_t exact;
+    double  kernel_ms;
+};                                /* 96 bytes */
+/* replaces the map of Tract(id, MultiPolygon boundary) the constructor fills (J/Tracts.java:26-43); grid 0: the library's rule, n > 0: n x n cells */
+int  dge_regions_create(int device, const int64_t* ids, int64_t R, const int64_t* ring_first, const int64_t* vert_first, const double* xy, int64_t n_rings, int64_t n_verts,
+                        int32_t grid, dge_regions** out);
+int  dge_regions_info(const dge_regions* r, struct dge_regions_info* out);
+/* replaces the boundary.contains loop (J/Tracts.java:82-86) for n points; region: host int32[n] */
+int  dge_regions_locate(const dge_regions* r, const double* xy, int64_t n, int32_t* region, dge_locate_info* info /* may be NULL */);
+int  dge_regions_locate_device(const dge_regions* r, const double* d_xy, int64_t n, int32_t* d_region, dge_locate_info* info /* may be NULL */);
+void dge_regions_free(dge_regions* r);
+/* replaces Tract.taxiFlows / CommunityArea.taxiFlows and Tracts.mapTripsIntoTracts (J/Tracts.java:71-102), J/CommunityAreas.java:55-103 */
+int  dge_flows_create(const dge_regions* r, dge_flows** out);
+int  dge_flows_add_trips(dge_flows* f, const double* start_xy, const double* end_xy, const int32_t* hour, int64_t n);              /* host arrays */
+int  dge_flows_add_trips_device(dge_flows* f, const double* d_start_xy, const double* d_end_xy, const int32_t* d_hour, int64_t n);
+int  dge_flows_info(const dge_flows* f, struct dge_flows_info* out);
+/* the table, region INDICES; replaces Tracts.serializeTracts (J/Tracts.java:104) as the way to keep the result */
+int  dge_flows_to_host(const dge_flows* f, int32_t* hour, int32_t* src, int32_t* dst, int64_t* count, int64_t cap, int64_t* n);
+/* replaces Tracts.outputEdgeFile / outputStaticEdgeFile (J/Tracts.java:236-260): the lines of the T files as arrays */
+int  dge_flows_slot_edges(const dge_flows* f, int32_t T, int32_t mode, int32_t* slot, int64_t* src_id, int64_t* dst_id, int64_t* w, int64_t cap, int64_t* n);
+void dge_flows_free(dge_flows* f);
+/* replaces outputEdgeFile followed by CrossTimeGraph.constructGraphFromOD (J/CrossTimeGraph.java:25-52): no text in between */
+int  dge_graph_add_flows(dge_graph* g, const dge_flows* f, int32_t T, int32_t mode, struct dge_names* names /* may be NULL */, dge_od_info* info /* may be NULL */);
+
 /* ------------------------------------------------------------------------------------------------
  * Walk sampler — replaces sampleVertexSequence() J/LayeredGraph.java:232-252 and the writer loops
  * J/CrossTimeGraph.java:134-140, J/SpatialGraph.java:103-113.
