@@ -80,7 +80,19 @@ class FlowsInfo(C.Structure):
                 ("located", C.c_int64), ("on_boundary", C.c_int64), ("multi", C.c_int64), ("outside", C.c_int64), ("exact", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class TripTextOptions(C.Structure):
+    """struct dge_trip_text_options (include/dge.h)."""
+    _fields_ = [("format", C.c_int32), ("header", C.c_int32), ("slab_bytes", C.c_int64)]
+
+
+class TripTextInfo(C.Structure):
+    """struct dge_trip_text_info (include/dge.h) — what dge_trips_parse_texts / dge_flows_add_trip_texts / dge_flows_add_trip_files report."""
+    _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("header_lines", C.c_int64), ("ok", C.c_int64), ("bad_fields", C.c_int64), ("bad_parse", C.c_int64),
+                ("too_long", C.c_int64), ("host_values", C.c_int64), ("slabs", C.c_int64), ("read_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
+DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
 
 # every symbol include/dge.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _dbl, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_double, C.c_int
@@ -123,6 +135,9 @@ SIGNATURES = {
     "dge_flows_slot_edges": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "dge_flows_free": (None, [_vp]),
     "dge_graph_add_flows": (_int, [_vp, _vp, _i32, _i32, _vp, _P(OdInfo)]),
+    "dge_trips_parse_texts": (_int, [_int, _vp, _vp, _i32, _P(TripTextOptions), _vp, _vp, _vp, _vp, _i64, _P(_i64), _P(TripTextInfo)]),
+    "dge_flows_add_trip_texts": (_int, [_vp, _vp, _vp, _i32, _P(TripTextOptions), _P(TripTextInfo)]),
+    "dge_flows_add_trip_files": (_int, [_vp, _vp, _i32, _P(TripTextOptions), _P(TripTextInfo)]),
     "dge_sample_walks": (_int, [_vp, _i64, _i32, _i64, _int, _i64, _vp, _P(_i64)]),
     "dge_sample_walks_device": (_int, [_vp, _i64, _i32, _i64, _int, _i64, _P(_vp), _P(_i64)]),
     "dge_sample_walks_into": (_int, [_vp, _vp, _i64, _i64, _i64, _i64]),

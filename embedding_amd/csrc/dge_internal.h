@@ -139,6 +139,11 @@ struct dge_vectors {
     int64_t n_present = 0;
 };
 
+// the flow table of trip_map.hip as trip_text.hip needs it: the trips of a text gather in a table of their own over the same regions, merged at the end
+int dge_flows_device(const dge_flows* f);
+int dge_flows_like(const dge_flows* f, dge_flows** out);          // an empty table over f's regions
+int dge_flows_merge(dge_flows* f, const dge_flows* part);          // part's table and counters into f; on error f is as it was
+
 int dge_graph_ensure_csr(dge_graph* g);
 // launches the strided walk kernel on `stream`; rows [row0,row0+n) of out (row length L)
 int dge_launch_walks_strided(const dge_graph* g, hipStream_t stream, int32_t* d_out, int64_t n, int32_t L,

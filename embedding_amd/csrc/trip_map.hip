@@ -617,6 +617,47 @@ extern "C" int dge_flows_add_trips_device(dge_flows* f, const double* d_start_xy
     return flows_add(f, d_start_xy, d_end_xy, d_hour, n, true, "dge_flows_add_trips_device");
 }
 
+int dge_flows_device(const dge_flows* f) { return f->regions->device; }
+int dge_flows_like(const dge_flows* f, dge_flows** out) { return dge_flows_create(f->regions, out); }
+
+// The tables are sorted sets of (key, count): concatenated, sorted and reduced by key they are the table the trips of both give in any order of adding.
+int dge_flows_merge(dge_flows* f, const dge_flows* part) {
+    const char* who = "dge_flows_merge";
+    if (f->regions != part->regions) DGE_FAIL(DGE_ERR_ARG, "%s: the tables are over different regions", who);
+    SeqRun R;
+    if (part->n > 0) {
+        SEQ_TRY(dge_require_device(f->regions->device));
+        SEQ_TRY(trip_open(R, f->regions->device, who));
+        const int64_t tn = f->n, u = part->n;
+        const uint64_t Ru = (uint64_t)std::max<int64_t>(f->regions->R, 1);
+        dge_tmp<uint64_t> ckey, cskey, nkey;
+        dge_tmp<int64_t> ccnt, cscnt, ncnt;
+        int64_t nn = 0;
+        SEQ_TRY(seq_alloc(R, ckey, tn + u, "the joined tables"));
+        SEQ_TRY(seq_alloc(R, ccnt, tn + u, "the joined tables' counts"));
+        SEQ_TRY(seq_alloc(R, cskey, tn + u, "the joined tables, sorted"));
+        SEQ_TRY(seq_alloc(R, cscnt, tn + u, "the joined tables' counts, sorted"));
+        if (tn) {
+            DGE_HIP(hipMemcpyAsync(ckey.p, f->d_key, (size_t)tn * 8, hipMemcpyDeviceToDevice, R.stream));
+            DGE_HIP(hipMemcpyAsync(ccnt.p, f->d_cnt, (size_t)tn * 8, hipMemcpyDeviceToDevice, R.stream));
+        }
+        DGE_HIP(hipMemcpyAsync(ckey.p + tn, part->d_key, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
+        DGE_HIP(hipMemcpyAsync(ccnt.p + tn, part->d_cnt, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
+        SEQ_TRY(trip_sort_pairs(R, ckey.p, cskey.p, ccnt.p, cscnt.p, tn + u, bits_of(24 * Ru * Ru)));
+        SEQ_TRY(trip_reduce(R, cskey.p, cscnt.p, tn + u, nkey, ncnt, &nn));
+        DGE_HIP(hipStreamSynchronize(R.stream));
+        // nothing can fail from here on
+        dge_dev_free(f->d_key); dge_dev_free(f->d_cnt);
+        f->d_key = nkey.release(); f->d_cnt = ncnt.release(); f->n = nn;
+    }
+    struct dge_flows_info& I = f->info;
+    const struct dge_flows_info& P = part->info;
+    I.trips += P.trips; I.mapped += P.mapped; I.bad += P.bad; I.no_start += P.no_start; I.no_end += P.no_end; I.entries = f->n;
+    I.located += P.located; I.on_boundary += P.on_boundary; I.multi += P.multi; I.outside += P.outside; I.exact += P.exact;
+    I.kernel_ms += P.kernel_ms + R.kernel_ms;
+    return DGE_OK;
+}
+
 extern "C" int dge_flows_info(const dge_flows* f, struct dge_flows_info* out) {
     if (!f || !out) DGE_FAIL(DGE_ERR_ARG, "dge_flows_info: null argument");
     *out = f->info;

@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, TripTextInfo, TripTextOptions, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -191,6 +191,34 @@ def _info_dict(inf):
     return {f[0]: getattr(inf, f[0]) for f in inf._fields_}
 
 
+def _text_args(texts):
+    """bytes-like pieces -> (the arrays kept alive, pointer array, size array, count)"""
+    if isinstance(texts, (bytes, bytearray, memoryview)):
+        texts = [texts]
+    views = [np.frombuffer(t, np.uint8) for t in texts]
+    ptrs = (C.c_void_p * max(len(views), 1))(*[v.ctypes.data if v.size else None for v in views])
+    sizes = (C.c_int64 * max(len(views), 1))(*[v.size for v in views])
+    return views, ptrs, sizes, len(views)
+
+
+def parse_trips(texts, fmt, header=True, slab_bytes=0, device=0):
+    """Taxi trip text -> a dict of arrays, one record per non-header line in text order (include/dge.h: dge_trips_parse_texts): status uint8 (0 ok, 1 wrong
+    piece count, 2 a field did not parse, 3 too long), hour int32, start_xy and end_xy float64 [n, 2] (x, y), and info, the fields of struct
+    dge_trip_text_info.  texts: one text or a sequence of texts as bytes / bytearray / memoryview, each a piece (a file's bytes); fmt: 1, 2 or 3."""
+    views, ptrs, sizes, n = _text_args(texts)
+    opt = TripTextOptions(int(fmt), 1 if header else 0, int(slab_bytes))
+    inf = TripTextInfo()
+    got = C.c_int64(0)
+    rc = lib.dge_trips_parse_texts(int(device), ptrs, sizes, n, C.byref(opt), None, None, None, None, 0, C.byref(got), C.byref(inf))          # a size query
+    if rc not in (0, DGE_ERR_CAP):
+        check(rc)
+    m = got.value
+    status = np.zeros(m, np.uint8); hour = np.zeros(m, np.int32); s = np.zeros((m, 2), np.float64); e = np.zeros((m, 2), np.float64)
+    if m:
+        check(lib.dge_trips_parse_texts(int(device), ptrs, sizes, n, C.byref(opt), _ptr(status), _ptr(hour), _ptr(s), _ptr(e), m, C.byref(got), C.byref(inf)))
+    return dict(status=status, hour=hour, start_xy=s, end_xy=e, info=_info_dict(inf))
+
+
 class Regions:
     """Region rings with their cell index in HBM (struct dge_regions, include/dge.h): what Tracts / CommunityAreas hold as JTS MultiPolygons
     (J/Tracts.java:26-43).  Points are located by the exact ray-crossing rule of csrc/pip_exact.h."""
@@ -276,6 +304,26 @@ class Flows:
         if not (len(s) == len(e) == len(h)):
             raise ValueError("start / end / hour lengths differ")
         check(lib.dge_flows_add_trips(self._h, _ptr(s), _ptr(e), _ptr(h), len(h)))
+
+    def add_trip_text(self, texts, fmt, header=True, slab_bytes=0):
+        """Taxi trip text (one text or a sequence of texts, bytes-like, each a piece) parsed and added on the device (include/dge.h: dge_flows_add_trip_texts):
+        the table stands where add_trips leaves it on the status-0 records of the text.  -> the fields of struct dge_trip_text_info"""
+        views, ptrs, sizes, n = _text_args(texts)
+        opt = TripTextOptions(int(fmt), 1 if header else 0, int(slab_bytes))
+        inf = TripTextInfo()
+        check(lib.dge_flows_add_trip_texts(self._h, ptrs, sizes, n, C.byref(opt), C.byref(inf)))
+        return _info_dict(inf)
+
+    def add_trip_files(self, paths, fmt, header=True, slab_bytes=0):
+        """The same for trip files (one path or a sequence), streamed from disk: dge_flows_add_trip_files."""
+        if isinstance(paths, (str, os.PathLike)):
+            paths = [paths]
+        paths = list(paths)
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        opt = TripTextOptions(int(fmt), 1 if header else 0, int(slab_bytes))
+        inf = TripTextInfo()
+        check(lib.dge_flows_add_trip_files(self._h, arr, len(paths), C.byref(opt), C.byref(inf)))
+        return _info_dict(inf)
 
     def info(self):
         inf = FlowsInfo()

@@ -160,7 +160,7 @@ int  dge_graph_regions(const dge_graph* g, int64_t* regions, int64_t cap, int64_
 /* ---- trips into regions, regions into flows (new; additions only, DGE_VERSION unchanged): the stage in front of the .od files — Tracts.mapTripsIntoTracts
  * (J/Tracts.java:71-102) and CommunityAreas.mapTripsIntoCommunities (J/CommunityAreas.java:55-103), which test every trip's pickup and drop-off point with JTS
  * MultiPolygon.contains against every region and count taxiFlows[hour][dst] — on the device (csrc/trip_map.hip, csrc/pip_exact.h).  Arrays in, flows and a
- * graph out: parsing trip CSVs and reading shapefiles stay with the host.  The rule; the result is a pure function of the inputs, nothing depends on timing,
+ * graph out: reading shapefiles stays with the host (the trip files themselves: the next section).  The rule; the result is a pure function of the inputs, nothing depends on timing,
  * launch geometry or the index's cell count:
  *   - REGIONS: region r has the id ids[r] (distinct) and the rings ring_first[r] .. ring_first[r+1]-1; ring q has the vertices vert_first[q] .. vert_first[q+1]-1
  *     of xy (binary64, x = longitude, y = latitude, interleaved).  A ring is closed: at least 4 vertices, the last equal to the first bit for bit.  Shells and
@@ -246,6 +246,68 @@ int  dge_flows_slot_edges(const dge_flows* f, int32_t T, int32_t mode, int32_t* 
 void dge_flows_free(dge_flows* f);
 /* replaces outputEdgeFile followed by CrossTimeGraph.constructGraphFromOD (J/CrossTimeGraph.java:25-52): no text in between */
 int  dge_graph_add_flows(dge_graph* g, const dge_flows* f, int32_t T, int32_t mode, struct dge_names* names /* may be NULL */, dge_od_info* info /* may be NULL */);
+
+/* ---- taxi trip text in (new; additions only, DGE_VERSION unchanged): the lines the reference reads in TaxiTrip(String line) and ShortDate
+ * (J/TaxiTrip.java:39-78,199-223; the loops J/TaxiTrip.java:123-143 and J/TaxiTripIterator.java:32-62) are parsed on the device (csrc/trip_text.hip, csrc/trip_parse.h)
+ * and go into a flow table without per-trip work on the host.  The rule; the result is a pure function of the bytes, the format and the header flag — nothing
+ * depends on timing, launch geometry or slab_bytes:
+ *   - LINES.  The text is BYTES in pieces (a file, or a text).  A line ends at "\n", "\r\n" or a lone "\r" (BufferedReader.readLine); a last line without a
+ *     terminator counts; nothing follows a final terminator.  No line crosses a piece: a "\r" that ends piece A and a "\n" that opens piece B are two terminators,
+ *     and B begins with an empty line.  header != 0: the first line of every piece is skipped and counted in header_lines (J/TaxiTrip.java:128); header == 0: it is
+ *     parsed like any other (TaxiTripIterator).  No byte is an error, NUL included: text is never refused, lines are good or bad.
+ *     DEVIATION: a line longer than 65 535 bytes is status 3 whatever it holds (the reference would parse it).
+ *   - SPLIT(s, set) cuts at every byte of set; empty pieces are kept, except that all trailing empty pieces go; an empty s is one empty piece, an s of only
+ *     separators is no piece.  SPLIT+ treats a run of separators as one; a leading separator still leaves a leading empty piece.  SPLIT2(s) cuts at the first blank
+ *     only: one or two pieces, the second may be empty.  (Java 8 String.split for ",", "\t", "\t+", "[/ :]", "/" and (" ", 2).)
+ *   - INT(s, lo, hi): [+-] digits, at least one digit, ASCII digits only, leading zeros allowed, the value in [lo, hi]; else the parse fails.  BYTE is INT with
+ *     -128 .. 127, INT32 with the int32 range.
+ *   - COORD(s): bytes <= 0x20 go at both ends; then the value grammar of the .od weights above without its inf / nan words; the value is the binary64 nearest the
+ *     exact decimal, ties to even (csrc/od_parse.h; the few tokens it hands back are finished by the host with strtod and counted in host_values).  A result that
+ *     is not finite fails.  DEVIATION: so do hex floats and the f / d suffixes, which Double.parseDouble takes; NaN and Infinity, which it takes too, fail here —
+ *     the flow table is the same either way, because a point that is not finite lies in no region.
+ *   - DATE1(s): f = SPLIT(s, "/ :"), at least 5 pieces; BYTE(f0), BYTE(f1), BYTE(f4) must parse; hour = BYTE(f3), as it stands.
+ *   - DATE2(date, time): d = SPLIT(date, "/"), at least 2 pieces, BYTE(d0) and BYTE(d1) must parse; t = SPLIT(time, " :"), at least 4 pieces, BYTE(t1) must parse;
+ *     h = BYTE(t0); hour = h % 12 + 12 when t3 is exactly "PM", else h % 12 — the remainder truncating, as Java's.
+ *   - DGE_TRIPS_TYPE1: p = SPLIT+(line, "\t"), exactly 13 pieces.  DATE1(p7) gives the hour, DATE1(p8) must parse.  A GPS piece g has length >= 2; its first and
+ *     last byte go, then q = SPLIT(., ","), at least 2 pieces, y = COORD(q0), x = COORD(q1).  Start point p9, end point p10.  INT32(p2) must parse.
+ *   - DGE_TRIPS_TYPE2: p = SPLIT(line, "\t"), exactly 17 pieces.  DATE2(p0, p1) gives the hour, DATE1(p2) must parse.  start = (COORD(p9), COORD(p10)),
+ *     end = (COORD(p11), COORD(p12)), each (x, y).  INT32(p15) must parse.
+ *   - DGE_TRIPS_TYPE3: p = SPLIT(line, ","), exactly 21 pieces; there is no quoting.  a = SPLIT2(p0), b = SPLIT2(p1), 2 pieces each.  DATE2(a0, a1) gives the hour,
+ *     DATE2(b0, b1) must parse.  start = (COORD(p16), COORD(p15)), end = (COORD(p19), COORD(p18)).  INT32(p2) must parse.
+ *   - STATUS of a line: 0 ok; 1 the line's piece count is wrong (the reference's badTrip; an empty line is status 1); 2 anything else failed; 3 too long.  An hour
+ *     outside 0 .. 23 does not make a line bad: dge_flows drops and counts such trips.
+ *   - dge_trips_parse_texts returns one record per non-header line, in text order, in host arrays (start_xy / end_xy: x, y interleaved); a record of status != 0
+ *     has hour -1 and zeros.  cap too small: DGE_ERR_CAP with *n_lines set.
+ *   - dge_flows_add_trip_texts / _files leave f exactly where dge_flows_add_trips leaves it when given the status-0 records of the same text, bit for bit, the
+ *     counters of dge_flows_info included.  The trips gather in a table of their own that is merged into f at the end: on any error f is as it was.  All files are
+ *     opened before anything runs; a missing or unreadable file: DGE_ERR_IO with its path.  Out of device memory: DGE_ERR_CAP.
+ *   - The text streams through the device in slabs of slab_bytes (0: the library's rule, 16 MiB; else at least 131072; above 2^30 is taken as 2^30): device memory
+ *     does not grow with the text.
+ *   - Null / negative arguments, an unknown format, slab_bytes in 1 .. 131071: DGE_ERR_ARG before a device is looked for. */
+enum { DGE_TRIPS_TYPE1 = 1, DGE_TRIPS_TYPE2 = 2, DGE_TRIPS_TYPE3 = 3 };
+struct dge_trip_text_options {
+    int32_t format;       /* DGE_TRIPS_TYPE1 .. DGE_TRIPS_TYPE3                                           */
+    int32_t header;       /* != 0: the first line of every piece is a header                              */
+    int64_t slab_bytes;   /* 0: the library's rule; else >= 131072                                        */
+};                        /* 16 bytes */
+typedef struct dge_trip_text_info {
+    int64_t bytes;        /* bytes of text taken (the pieces' sizes added up)                             */
+    int64_t lines;        /* lines, headers and a last one without a terminator included                  */
+    int64_t header_lines; /* lines skipped as headers                                                     */
+    int64_t ok;           /* records of status 0                                                          */
+    int64_t bad_fields;   /* status 1                                                                     */
+    int64_t bad_parse;    /* status 2                                                                     */
+    int64_t too_long;     /* status 3                                                                     */
+    int64_t host_values;  /* coordinates the host finished with strtod                                    */
+    int64_t slabs;        /* slabs the text went through the device in                                    */
+    double  read_ms;      /* filling the pinned buffers (file reads included)                             */
+    double  kernel_ms;    /* the text's device passes (the flow table's are in dge_flows_info)            */
+} dge_trip_text_info;     /* 88 bytes */
+int  dge_trips_parse_texts(int device, const char* const* texts, const int64_t* n_bytes, int32_t n, const struct dge_trip_text_options* opt, uint8_t* status, int32_t* hour,
+                           double* start_xy, double* end_xy, int64_t cap, int64_t* n_lines, dge_trip_text_info* info /* may be NULL */);
+/* replace the loops over TaxiTrip lines in front of Tracts.mapTripsIntoTracts (J/TaxiTrip.java:123-143, J/TaxiTripIterator.java:32-62) */
+int  dge_flows_add_trip_texts(dge_flows* f, const char* const* texts, const int64_t* n_bytes, int32_t n, const struct dge_trip_text_options* opt, dge_trip_text_info* info /* may be NULL */);
+int  dge_flows_add_trip_files(dge_flows* f, const char* const* paths, int32_t n, const struct dge_trip_text_options* opt, dge_trip_text_info* info /* may be NULL */);
 
 /* ------------------------------------------------------------------------------------------------
  * Walk sampler — replaces sampleVertexSequence() J/LayeredGraph.java:232-252 and the writer loops
