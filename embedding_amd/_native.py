@@ -91,6 +91,11 @@ class TripTextInfo(C.Structure):
                 ("too_long", C.c_int64), ("host_values", C.c_int64), ("slabs", C.c_int64), ("read_ms", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class SpatialInfo(C.Structure):
+    """struct dge_spatial_info (include/dge.h) — what dge_graph_add_spatial / dge_graph_add_spatial_points report."""
+    _fields_ = [("regions", C.c_int64), ("edges", C.c_int64), ("weights", C.c_int64), ("zero_weights", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
 DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
 
@@ -135,6 +140,9 @@ SIGNATURES = {
     "dge_flows_slot_edges": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "dge_flows_free": (None, [_vp]),
     "dge_graph_add_flows": (_int, [_vp, _vp, _i32, _i32, _vp, _P(OdInfo)]),
+    "dge_regions_centroids": (_int, [_vp, _vp, _i64, _P(_i64)]),
+    "dge_graph_add_spatial": (_int, [_vp, _vp, _i32, _dbl, _vp, _P(SpatialInfo)]),
+    "dge_graph_add_spatial_points": (_int, [_vp, _vp, _vp, _i64, _i32, _dbl, _vp, _P(SpatialInfo)]),
     "dge_trips_parse_texts": (_int, [_int, _vp, _vp, _i32, _P(TripTextOptions), _vp, _vp, _vp, _vp, _i64, _P(_i64), _P(TripTextInfo)]),
     "dge_flows_add_trip_texts": (_int, [_vp, _vp, _vp, _i32, _P(TripTextOptions), _P(TripTextInfo)]),
     "dge_flows_add_trip_files": (_int, [_vp, _vp, _i32, _P(TripTextOptions), _P(TripTextInfo)]),

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <atomic>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <string_view>
 #include <unordered_set>
@@ -139,12 +140,39 @@ struct dge_vectors {
     int64_t n_present = 0;
 };
 
+// region rings with their cell index (trip_map.hip makes and reads it; spatial.hip reads the segments and keeps the centroids)
+struct dge_regions {
+    int device = 0;
+    std::atomic<int> refs{1};
+    int64_t R = 0, n_rings = 0, n_segs = 0, max_cand = 0;
+    int32_t grid = 1;
+    double box[4] = {0, 0, 0, 0};                // x0, y0, x1, y1
+    double invx = 0, invy = 0;
+    std::vector<int64_t> ids;
+    double* d_seg = nullptr;                     // [n_segs][4]: ax ay bx by
+    int64_t* d_seg_first = nullptr;              // [R + 1]
+    double* d_box = nullptr;                     // [R][4]
+    int64_t* d_cell_first = nullptr;             // [G*G + 1]
+    int32_t* d_cand = nullptr;
+    int32_t* d_idrank = nullptr;                 // region -> rank of its id
+    int64_t* d_id_by_rank = nullptr;             // rank -> id
+    // the regions' centroids (spatial.hip): computed on the device on first use and kept, on the device and on the host
+    mutable std::mutex cent_mutex;               // the first use may come from several threads at once: the fill happens under it, once
+    mutable bool cent_done = false;
+    mutable double* d_cent = nullptr;            // [R][2]
+    mutable std::vector<double> cent;
+    ~dge_regions() { for (void* p : {(void*)d_seg, (void*)d_seg_first, (void*)d_box, (void*)d_cell_first, (void*)d_cand, (void*)d_idrank, (void*)d_id_by_rank, (void*)d_cent}) dge_dev_free(p); }
+};
+
 // the flow table of trip_map.hip as trip_text.hip needs it: the trips of a text gather in a table of their own over the same regions, merged at the end
 int dge_flows_device(const dge_flows* f);
 int dge_flows_like(const dge_flows* f, dge_flows** out);          // an empty table over f's regions
 int dge_flows_merge(dge_flows* f, const dge_flows* part);          // part's table and counters into f; on error f is as it was
 
 int dge_graph_ensure_csr(dge_graph* g);
+// the end state of keepNearestKVertices (graph.hip): the store becomes the given CSR of n_edges edges (device arrays, taken over; g->d_outdeg already holds the
+// recomputed outDegree), the tables are void, the sources' weights are refreshed.  dge_graph_keep_top_k ends in it; spatial.hip hands its edges over through it.
+int dge_graph_adopt_pruned(dge_graph* g, int64_t* d_row_ptr, double* d_w, int32_t* d_nbr, int64_t n_edges);
 // launches the strided walk kernel on `stream`; rows [row0,row0+n) of out (row length L)
 int dge_launch_walks_strided(const dge_graph* g, hipStream_t stream, int32_t* d_out, int64_t n, int32_t L,
                              int64_t seed, int64_t first_index, int32_t* d_deadend_count);

@@ -689,13 +689,18 @@ extern "C" int dge_graph_keep_top_k(dge_graph* g, int32_t k) {
                        nrp.p, nw.p, nn.p, g->d_outdeg);
     DGE_HIP(hipStreamSynchronize(g->stream));
     DGE_HIP(hipGetLastError());
+    return dge_graph_adopt_pruned(g, nrp.release(), nw.release(), nn.release(), NE);
+}
+
+int dge_graph_adopt_pruned(dge_graph* g, int64_t* d_row_ptr, double* d_w, int32_t* d_nbr, int64_t n_edges) {
     dge_dev_free(g->d_row_ptr); dge_dev_free(g->d_w); dge_dev_free(g->d_nbr);
     dge_dev_free(g->d_prob); dge_dev_free(g->d_alias); dge_dev_free(g->d_slots);
     g->d_prob = nullptr; g->d_alias = nullptr; g->d_slots = nullptr;
-    g->d_row_ptr = nrp.release(); g->d_w = nw.release(); g->d_nbr = nn.release(); g->E = NE;
+    g->d_row_ptr = d_row_ptr; g->d_w = d_w; g->d_nbr = d_nbr; g->E = n_edges;
     g->alias_built = false;
     // source weights depend on outDegree: refresh them if sources were already set
     if (g->S > 0) {
+        int rc;
         dge_tmp<double> d_sum;
         if ((rc = d_sum.alloc(1))) return rc;
         launch_sources(g->stream, g->d_srcv, g->S, g->d_outdeg, g->d_src_w, 1, d_sum.p);

@@ -38,24 +38,6 @@ constexpr int64_t TRIP_CHUNK = (int64_t)1 << 24; // points (or trips) taken at a
 constexpr int32_t TRIP_MAX_GRID = 4096;
 enum { TC_LOCATED = 0, TC_BOUNDARY, TC_MULTI, TC_OUTSIDE, TC_EXACT, TC_MAPPED, TC_BAD, TC_NO_START, TC_NO_END, TC_VALID, TC_N };
 
-struct dge_regions {
-    int device = 0;
-    std::atomic<int> refs{1};
-    int64_t R = 0, n_rings = 0, n_segs = 0, max_cand = 0;
-    int32_t grid = 1;
-    double box[4] = {0, 0, 0, 0};                // x0, y0, x1, y1
-    double invx = 0, invy = 0;
-    std::vector<int64_t> ids;
-    double* d_seg = nullptr;                     // [n_segs][4]: ax ay bx by
-    int64_t* d_seg_first = nullptr;              // [R + 1]
-    double* d_box = nullptr;                     // [R][4]
-    int64_t* d_cell_first = nullptr;             // [G*G + 1]
-    int32_t* d_cand = nullptr;
-    int32_t* d_idrank = nullptr;                 // region -> rank of its id
-    int64_t* d_id_by_rank = nullptr;             // rank -> id
-    ~dge_regions() { for (void* p : {(void*)d_seg, (void*)d_seg_first, (void*)d_box, (void*)d_cell_first, (void*)d_cand, (void*)d_idrank, (void*)d_id_by_rank}) dge_dev_free(p); }
-};
-
 struct dge_flows {
     dge_regions* regions = nullptr;
     uint64_t* d_key = nullptr;                   // ascending

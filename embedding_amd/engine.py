@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, TrainConfig, TrainStats, TripTextInfo, TripTextOptions, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TripTextInfo, TripTextOptions, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -77,6 +77,30 @@ class DeviceGraph:
         inf = OdInfo()
         check(lib.dge_graph_add_flows(g._h, flows._h, int(T), int(mode), names._h if names is not None else None, C.byref(inf)))
         return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
+
+    @classmethod
+    def from_spatial(cls, regions_or_ids_xy, k=10, scale=100.0, names=True, device=0):
+        """Regions, or (ids, xy) host arrays of centroids -> (graph, names, info): the spatial graph of SpatialGraph.constructGraph_tract / _CA
+        (J/SpatialGraph.java:37-88) built on the device (include/dge.h: dge_graph_add_spatial / dge_graph_add_spatial_points): vertex i is region i, its edges
+        the first k candidates under (w descending, j ascending) with w = E(-d * scale) between centroids, all vertices sources.  No R x R matrix exists
+        anywhere.  names as in from_od: the decimal region ids in vertex order.  build_alias is next.  info: the fields of struct dge_spatial_info."""
+        if names is True:
+            names = Names()
+        elif not names and not isinstance(names, Names):
+            names = None
+        nh = names._h if names is not None else None
+        inf = SpatialInfo()
+        if isinstance(regions_or_ids_xy, Regions):
+            g = cls(regions_or_ids_xy.device)
+            check(lib.dge_graph_add_spatial(g._h, regions_or_ids_xy._h, int(k), float(scale), nh, C.byref(inf)))
+        else:
+            ids, xy = regions_or_ids_xy
+            ids = np.ascontiguousarray(ids, np.int64); xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+            if len(ids) != len(xy):
+                raise ValueError("ids has R entries, xy R x 2")
+            g = cls(device)
+            check(lib.dge_graph_add_spatial_points(g._h, _ptr(ids), _ptr(xy), len(ids), int(k), float(scale), nh, C.byref(inf)))
+        return g, names, _info_dict(inf)
 
     def regions(self):
         """The R region ids of a graph made by from_od, ascending int64 (vertex h*R + i is region regions()[i] in slice h); empty for any other graph."""
@@ -250,6 +274,18 @@ class Regions:
         inf = RegionsInfo()
         check(lib.dge_regions_info(self._h, C.byref(inf)))
         return _info_dict(inf)
+
+    def centroids(self):
+        """The regions' centroids, float64 [R, 2] (x, y): JTS's area-weighted centroid of the rings under the rule of include/dge.h, computed on the device on
+        first use and kept with the handle (dge_regions_centroids).  A region whose rings have no area: DgeError (DGE_ERR_ARG) naming it."""
+        n = C.c_int64(0)
+        rc = lib.dge_regions_centroids(self._h, None, 0, C.byref(n))         # a size query: DGE_ERR_CAP with n set when there are regions
+        if rc not in (0, DGE_ERR_CAP):
+            check(rc)
+        out = np.empty((n.value, 2), np.float64)
+        if n.value:
+            check(lib.dge_regions_centroids(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     def locate(self, xy, return_info=False):
         """xy: numpy float64 [n, 2] -> numpy int32 [n]; or a torch float64 tensor on this device -> a torch int32 tensor there.  -1: in no region."""

@@ -374,6 +374,38 @@ class SpatialGraph : public LayeredGraph {
         g.sourceWeightSum = java8StreamSum(od);
         g.initiateAliasTables(true);
     }
+    // The same graph from the regions' centroids, built on the device (dge_graph_add_spatial_points; include/dge.h, "the spatial graph"): no n x n matrix
+    // exists on either side.  Vertex names are the decimal ids, in the order of `ids`.  edgesOut, outDegree, sourceVertices and sourceWeightSum are filled
+    // from the read-back; allEdges stays empty (the reference's holds the n^2 edges it added, nothing reads it).  k > n: std::out_of_range, as above.
+    static void constructGraph(SpatialGraph& g, const std::vector<int64_t>& ids, const std::vector<double>& xy /* n x 2 */, int k = 10, double scale = 100.0) {
+        const size_t n = ids.size();
+        if (xy.size() != 2 * n) throw std::invalid_argument("constructGraph: xy holds n x 2 values");
+        if (!g.allVertices.empty()) throw std::runtime_error("constructGraph: the graph already has vertices");
+        dge_graph* h = nullptr;
+        dge_check(dge_graph_create(&h, device));
+        std::vector<int64_t> rp(n + 1);
+        std::vector<int32_t> nbr(n * (size_t)std::max(k, 0) + 1);
+        std::vector<double> w(nbr.size()), od(n + 1);
+        int32_t ns = 0;
+        double sum = 0.0;
+        int rc = dge_graph_add_spatial_points(h, ids.data(), xy.data(), (int64_t)n, k, scale, nullptr, nullptr);
+        if (!rc) rc = dge_graph_get_csr(h, rp.data(), nbr.data(), w.data(), nullptr, nullptr, od.data(), (int32_t)n, (int64_t)nbr.size());
+        if (!rc) rc = dge_graph_get_source_alias(h, nullptr, nullptr, nullptr, 0, &ns, &sum);
+        dge_graph_free(h);
+        if (rc == DGE_ERR_TOPK) throw std::out_of_range(dge_last_error());
+        dge_check(rc);
+        std::vector<Vertex*> vs;
+        for (int64_t id : ids) vs.push_back(g.intern(std::to_string(id)));
+        for (size_t i = 0; i < n; i++) {
+            vs[i]->edgesOut.clear();
+            for (int64_t e = rp[i]; e < rp[i + 1]; e++) vs[i]->edgesOut.emplace_back(vs[i], vs[(size_t)nbr[(size_t)e]], w[(size_t)e]);
+            vs[i]->outDegree = od[i];
+        }
+        g.sourceVertices = vs;
+        g.sourceWeightSum = sum;
+        g.built_ = false;
+        g.initiateAliasTables(true);
+    }
     static void outputSampleSequence(SpatialGraph& g, const std::string& path) {
         LayeredGraph::numLayer = SpatialGraph::numLayer;              // J/SpatialGraph.java:92
         CrossTimeGraph::write_seq(g, path, numSamples, true);

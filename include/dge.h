@@ -309,6 +309,63 @@ int  dge_trips_parse_texts(int device, const char* const* texts, const int64_t* 
 int  dge_flows_add_trip_texts(dge_flows* f, const char* const* texts, const int64_t* n_bytes, int32_t n, const struct dge_trip_text_options* opt, dge_trip_text_info* info /* may be NULL */);
 int  dge_flows_add_trip_files(dge_flows* f, const char* const* paths, int32_t n, const struct dge_trip_text_options* opt, dge_trip_text_info* info /* may be NULL */);
 
+/* ---- the spatial graph (new; additions only, DGE_VERSION unchanged): SpatialGraph.constructGraph_tract / constructGraph_CA (J/SpatialGraph.java:37-88) take the
+ * centroid of every region's MultiPolygon (J/Tracts.java:484-497), form all R^2 weights exp(-d * 100), call addEdge R^2 times and keep the 10 heaviest edges of every
+ * vertex.  Here the centroids, the weights and the selection happen on the device next to the resident rings (csrc/spatial.hip, csrc/spatial_weight.h), fused:
+ * nothing of size R^2 ever exists.  The rule; the result is a pure function of the inputs, nothing depends on timing, launch geometry or tile sizes:
+ *   - CENTROID of region r: the area-weighted centroid that JTS's Geometry.getCentroid() returns for a MultiPolygon (as recalled: its source was not consulted;
+ *     what follows is the rule).  The base point b is the first vertex of the region's first ring.  Over the rings in order and the segments (p, q) of each
+ *     ring in order:  a2 = (p.x-b.x)*(q.y-b.y) - (q.x-b.x)*(p.y-b.y);  cx += a2*(b.x+p.x+q.x);  cy += a2*(b.y+p.y+q.y);  A += a2.  The centroid is
+ *     (cx/3/A, cy/3/A).  Every operation is a rounded binary64 operation in exactly that order, operands left to right, nothing fused.
+ *   - Rings contribute with their own orientation: dge_regions does not tell shells from holes.  With the shapefile convention (shells clockwise, holes
+ *     counter-clockwise) this is JTS's sum term for term.  Reversing every ring of a region negates every a2 exactly, and the sign cancels in cx/A: the
+ *     centroid is the same point — the same bits where the sums are exact (dyadic coordinates of a few bits); with rounded coordinates the reversed rings are
+ *     summed in another order and the result agrees to rounding.
+ *   - A == 0 (a region without a ring included) or a centroid that is not finite: DGE_ERR_ARG naming the region.  DEVIATION: JTS falls back to the centroid of
+ *     the lines.
+ *   - DISTANCE: d(i,j) = sqrt(dx*dx + dy*dy), dx = ci.x - cj.x, dy = ci.y - cj.y (Coordinate.distance); sqrt correctly rounded.  d may be +inf (finite
+ *     centroids can overflow dx*dx): the weight is then 0, not an error.
+ *   - WEIGHT: w(i,j) = E((-d) * scale); the reference's scale is 100 (J/SpatialGraph.java:46,74).  E is one fixed sequence of rounded binary64 + - * /,
+ *     shaped like fdlibm's e_exp (the algorithm java.lang.StrictMath.exp is defined by) and written once in csrc/spatial_weight.h.  For x <= 0:
+ *       x < -0x1.74910d52d3051p+9: 0 (E(-inf) = 0; underflow goes to 0);  x >= -0x1p-28: 1 + x (E(-0.0) = E(0) = 1);
+ *       x >= -0x1.62e42fefa39efp-2: k = 0, hi = x, lo = 0;  else x > -0x1.0a2b23f3bab73p+0: k = -1, hi = x + ln2HI, lo = -ln2LO;
+ *       else k = (int)(invln2*x - 0.5), truncated, hi = x - k*ln2HI, lo = k*ln2LO;
+ *       r = hi - lo;  t = r*r;  c = r - t*(P1 + t*(P2 + t*(P3 + t*(P4 + t*P5))));
+ *       k == 0: 1 - ((r*c)/(c - 2) - r);  else y = 1 - ((lo - (r*c)/(2 - c)) - hi), scaled by 2^k exactly: y*2^k for k >= -1021, else (y*2^(k+1000))*2^-1000;
+ *       ln2HI = 0x1.62e42feep-1, ln2LO = 0x1.a39ef35793c76p-33, invln2 = 0x1.71547652b82fep+0, P1 = 0x1.555555555553ep-3, P2 = -0x1.6c16c16bebd93p-9,
+ *       P3 = 0x1.1566aaf25de2cp-14, P4 = -0x1.bbd41c5d26bf1p-20, P5 = 0x1.6376972bea4d0p-25.
+ *     E meets what Java asks of Math.exp: within 1 ulp of the true value, and never increasing as d grows (tests/test_spatial_host.py).
+ *   - SELECTION: for source i the candidates are j = 0 .. R-1 in region order, i itself included (w = 1).  The edges of vertex i are the first k candidates
+ *     under (w descending, j ascending), in that order — what the stable sort and subList(0, k) of keepNearestKVertices leave (J/SpatialGraph.java:29-35) when
+ *     addEdge ran in region order.  The order is by w, not by d: two distinct distances that round to one weight are ordered by index.  outDegree is
+ *     dge_java8_stream_sum (DoubleStream.sum()) of the k kept weights in that order.  1 <= k <= 32; k > R: DGE_ERR_TOPK, as the reference throws.
+ *   - GRAPH: vertex i is region i, in the order of ids; R*k edges; the sources are all vertices in order, set as dge_graph_set_sources(.., stream_sum = 1) sets
+ *     them (J/SpatialGraph.java:56-57).  g then stands bit for bit where a host stands after dge_graph_add_edges of all R^2 (i, j, w(i,j)) in row-major order,
+ *     dge_graph_keep_top_k(k) and dge_graph_set_sources(0 .. R-1, 1) — the "pruned" state that refuses later dge_graph_add_edges included (for k == R too,
+ *     where the three calls would leave a store that still takes edges).  dge_graph_build_alias is next.  R*k must stay below 2^32: DGE_ERR_RANGE.
+ *   - g must be fresh (DGE_ERR_STATE).  names (may be NULL) must be empty; it receives the decimal region ids in vertex order (the "j-" position prefix is the
+ *     walk writer's: dge_walks_write_seq).  On any error g and names are as they were.
+ *   - DGE_ERR_ARG before a device is looked for: null or negative arguments, scale not finite or <= 0, k outside 1 .. 32, duplicate ids, a point that is not
+ *     finite, names not empty.  R = 0 is fine and leaves an empty graph.
+ *   - Selection is brute force: R^2 squared distances, of which only those that can still enter a row's list get an E (info.weights): a candidate scanned in
+ *     ascending j whose dx*dx + dy*dy is >= that of the row's current k-th entry is left out without one.  That is the rule above only because E never rises as
+ *     d grows: whoever refits E's constants must pass the monotonicity test (tests/test_spatial_host.py) again, or drop that saving in csrc/spatial.hip.
+ *   - A dge_regions may be shared by threads: the first use of its centroids is serialised inside the handle. */
+typedef struct dge_spatial_info {
+    int64_t regions;      /* R                                                                            */
+    int64_t edges;        /* R * k                                                                        */
+    int64_t weights;      /* how many times E was evaluated: at most R^2 (a work counter, not part of the rule) */
+    int64_t zero_weights; /* kept edges with w == 0                                                       */
+    double  kernel_ms;    /* HIP-event time of the fused weight-and-selection kernel                      */
+} dge_spatial_info;       /* 40 bytes */
+/* the R centroids, x y interleaved, host double[2R]; computed on the device on first use and kept with the handle.  cap (in regions) too small: DGE_ERR_CAP with *n set */
+int  dge_regions_centroids(const dge_regions* r, double* xy, int64_t cap, int64_t* n);
+/* replaces constructGraph_tract (J/SpatialGraph.java:37-60): from the resident rings to the spatial graph in one call */
+int  dge_graph_add_spatial(dge_graph* g, const dge_regions* r, int32_t k, double scale, struct dge_names* names /* may be NULL */, dge_spatial_info* info /* may be NULL */);
+/* the same from host arrays of centroids that come from anywhere (community areas, J/SpatialGraph.java:63-88; another tool): ids int64[R], xy double[2R] */
+int  dge_graph_add_spatial_points(dge_graph* g, const int64_t* ids, const double* xy, int64_t R, int32_t k, double scale, struct dge_names* names /* may be NULL */,
+                                  dge_spatial_info* info /* may be NULL */);
+
 /* ------------------------------------------------------------------------------------------------
  * Walk sampler — replaces sampleVertexSequence() J/LayeredGraph.java:232-252 and the writer loops
  * J/CrossTimeGraph.java:134-140, J/SpatialGraph.java:103-113.
