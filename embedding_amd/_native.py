@@ -96,6 +96,17 @@ class SpatialInfo(C.Structure):
     _fields_ = [("regions", C.c_int64), ("edges", C.c_int64), ("weights", C.c_int64), ("zero_weights", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class KmeansCfg(C.Structure):
+    """struct dge_kmeans_cfg (include/dge.h)."""
+    _fields_ = [("k", C.c_int32), ("n_init", C.c_int32), ("max_iter", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class KmeansInfo(C.Structure):
+    """struct dge_kmeans_info (include/dge.h) — what dge_kmeans_vectors / dge_kmeans report."""
+    _fields_ = [("rows", C.c_int64), ("best_restart", C.c_int32), ("iterations", C.c_int32), ("total_iterations", C.c_int64), ("scale_bits", C.c_int32),
+                ("empty", C.c_int32), ("inertia", C.c_double), ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
 DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
 
@@ -222,6 +233,9 @@ SIGNATURES = {
     "dge_model_load_vectors": (_int, [_vp, _vp, _P(_i64)]),
     "dge_knn_cosine_vectors": (_int, [_vp, _i32, _vp, _vp, _P(_dbl)]),
     "dge_ndcg_at_k_vectors": (_int, [_vp, _vp, _i32, _P(_dbl), _P(_dbl)]),
+    "dge_kmeans_vectors": (_int, [_vp, _vp, _P(KmeansCfg), _vp, _vp, _vp, _P(KmeansInfo)]),
+    "dge_kmeans": (_int, [_int, _vp, _i64, _i32, _vp, _P(KmeansCfg), _vp, _vp, _vp, _P(KmeansInfo)]),
+    "dge_cluster_accuracy": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _P(_dbl)]),
     "dge_selftest_locked_rows": (_int, [_int, _i32, _i64, _i32, C.c_uint64, _i32, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave": (_int, [_int, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),

@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TripTextInfo, TripTextOptions, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TripTextInfo, TripTextOptions, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -621,6 +621,25 @@ class Vectors:
         out = C.c_double(0); ms = C.c_double(0)
         check(lib.dge_ndcg_at_k_vectors(self._h, gnd._h, int(k), C.byref(out), C.byref(ms)))
         return out.value, ms.value
+
+    def kmeans(self, k, seed=1, n_init=10, max_iter=300, select=None, init=None):
+        """k-means on these rows as the rule of include/dge.h (dge_kmeans_vectors): the same bits for the same rows, k, seed, n_init and max_iter.
+        select: one entry per row, non-zero = take the row (default: every present row).  init: [k x dim] initial centres instead of k-means++ seeding
+        (n_init is then 1).  -> (labels int32 [rows], -1 on rows not selected; centres float32 [k x dim]; info: the fields of struct dge_kmeans_info)."""
+        n, dim = self.shape
+        k = int(k)
+        if select is not None:
+            select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+            if select.shape != (n,):
+                raise ValueError("select must hold one entry per row")
+        if init is not None:
+            init = np.ascontiguousarray(init, np.float32)
+            if init.shape != (k, dim):
+                raise ValueError("init must be [k x dim] = [%d x %d], not %s" % (k, dim, list(init.shape)))
+        cfg = KmeansCfg(k, int(n_init), int(max_iter), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        labels = np.empty(n, np.int32); centres = np.empty((max(k, 0), dim), np.float32); inf = KmeansInfo()
+        check(lib.dge_kmeans_vectors(self._h, _ptr(select), C.byref(cfg), _ptr(init), _ptr(labels), _ptr(centres), C.byref(inf)))
+        return labels, centres, {f[0]: getattr(inf, f[0]) for f in KmeansInfo._fields_}
 
 
 def make_config(dim, window, n_vertices, negative=5, min_count=2, epochs=1, workers=0, alpha=0.025, min_alpha=1e-4,

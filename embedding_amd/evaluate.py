@@ -1,6 +1,7 @@
 """Quality metric of the reference's evaluation scripts on the device (P/embeddingEvaluation_tract.py:169-196 pairwiseEstimator, :249-260
 ndcg_atK): ctypes views of dge_knn_cosine / dge_ndcg_at_k.  Used as the statistical parity check between training schedules (in-order /
-Hogwild / multi-GPU) on one slice.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
+Hogwild / multi-GPU) on one slice; and the reference's second figure, clusteringAccuracy (:539-571), on a k-means that is a fully specified rule
+(include/dge.h: dge_kmeans_vectors, dge_cluster_accuracy) instead of scikit-learn's randomised one.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
 import numpy as np
 
 
@@ -39,3 +40,50 @@ def knn_cosine_vectors(vectors, k):
 def ndcg_vectors(vectors, gnd_vectors, k=10):
     """ndcg_against_gpu on two resident row sets aligned by name (engine.Vectors): dge_ndcg_at_k_vectors."""
     return vectors.ndcg_against(gnd_vectors, k)
+
+
+def kmeans_gpu(features, k, seed=1, n_init=10, max_iter=300, select=None, init=None, device=0):
+    """k-means of host rows [n x dim] on the device as the rule of include/dge.h (dge_kmeans).  -> (labels int32 [n], -1 on rows select leaves out;
+    centres float32 [k x dim]; info: the fields of struct dge_kmeans_info)."""
+    import ctypes as C
+    from ._native import KmeansCfg, KmeansInfo, check, lib
+    f = np.ascontiguousarray(features, np.float32)
+    n, dim = f.shape
+    k = int(k)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    if select is not None:
+        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+        if select.shape != (n,):
+            raise ValueError("select must hold one entry per row")
+    if init is not None:
+        init = np.ascontiguousarray(init, np.float32)
+        if init.shape != (k, dim):
+            raise ValueError("init must be [k x dim] = [%d x %d], not %s" % (k, dim, list(init.shape)))
+    cfg = KmeansCfg(k, int(n_init), int(max_iter), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+    labels = np.empty(n, np.int32); centres = np.empty((max(k, 0), dim), np.float32); inf = KmeansInfo()
+    check(lib.dge_kmeans(int(device), p(f), n, dim, p(select), C.byref(cfg), p(init), p(labels), p(centres), C.byref(inf)))
+    return labels, centres, {fl[0]: getattr(inf, fl[0]) for fl in KmeansInfo._fields_}
+
+
+def clustering_accuracy(labels, gnd, k):
+    """clusteringAccuracy of the reference (P/embeddingEvaluation_tract.py:544-571) from cluster labels and ground labels, both in [0, k) or -1
+    (dge_cluster_accuracy; a host computation).  -> (accuracy, cnt int64 [k x k], map int32 [k])."""
+    import ctypes as C
+    from ._native import check, lib
+    a = np.ascontiguousarray(labels, np.int32); g = np.ascontiguousarray(gnd, np.int32)
+    if a.shape != g.shape or a.ndim != 1:
+        raise ValueError("labels and gnd must be one-dimensional and of one length")
+    k = int(k)
+    cnt = np.zeros((max(k, 0), max(k, 0)), np.int64); m = np.full(max(k, 0), -1, np.int32); acc = C.c_double(0)
+    check(lib.dge_cluster_accuracy(a.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p), len(a), k, cnt.ctypes.data_as(C.c_void_p),
+                                   m.ctypes.data_as(C.c_void_p), C.byref(acc)))
+    return acc.value, cnt, m
+
+
+def clustering_accuracy_vectors(vectors, gnd_labels, k, seed=1, n_init=10, max_iter=300, select=None):
+    """The reference's clusteringAccuracy on resident rows (an engine.Vectors): k-means by rule, then the accuracy of its labels against gnd_labels
+    (one per row, -1 = no ground label).  Rows the embedding lacks count in the denominator, as in the reference.  -> (accuracy, labels, info)."""
+    labels, _, info = vectors.kmeans(k, seed=seed, n_init=n_init, max_iter=max_iter, select=select)
+    acc, cnt, m = clustering_accuracy(labels, gnd_labels, k)
+    info = dict(info, cnt=cnt, map=m)
+    return acc, labels, info

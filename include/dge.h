@@ -804,6 +804,73 @@ int  dge_knn_cosine_vectors(const dge_vectors* v, int32_t k, int32_t* out_idx, f
 int  dge_ndcg_at_k_vectors(const dge_vectors* f, const dge_vectors* gnd, int32_t k, double* ndcg, double* ms_kernels);         /* equal row counts, every row present in both: else DGE_ERR_ARG */
 
 /* ------------------------------------------------------------------------------------------------
+ * k-means and clustering accuracy (new; additions only, DGE_VERSION unchanged): the reference's second figure of merit, clusteringAccuracy
+ * (P/embeddingEvaluation_tract.py:539-571, driven by evaluate_by_clustering, :574-631): k-means on the embedding's rows, the contingency table against ground
+ * labels, a greedy map of clusters to labels, the share of regions that land on their label.  The reference takes scikit-learn's KMeans, which draws its own
+ * random numbers: two of its runs do not agree.  Here k-means is a RULE (csrc/kmeans.hip; the per-element pieces: csrc/kmeans_rule.h); the result is a pure
+ * function of the rows, k, the seed, n_init and max_iter.  Nothing depends on timing, launch geometry or tile sizes: every sum that decides anything is an
+ * integer sum or a binary64 sum in an order fixed below.  tests/kmeans_ref.py is this text in Python.
+ *   - INPUTS.  Resident float32 rows [rows x dim] with one present byte per row, and an optional host array `select`, one byte per row (NULL: every present
+ *     row).  The SELECTED rows are the present rows with a non-zero select byte, in ascending row order; n is their count and "row i" below is the i-th of
+ *     them.  Limits: 1 <= k <= 64, 1 <= dim <= 256, k <= n <= 2^31 - 1, n_init >= 1, max_iter >= 1; anything outside: DGE_ERR_ARG with the reason.  A value
+ *     that is not finite in a selected row: DGE_ERR_ARG naming the least such row (by its number among all rows); rows that are not selected are never
+ *     read.  Null arguments and the limits on k, n_init, max_iter and dim: DGE_ERR_ARG before a device is looked for.  On any error the outputs are untouched.
+ *   - DISTANCE.  d(i, c) is a binary64 accumulator that starts at +0.0; for j = 0 .. dim-1 ascending: t = (double)x[i][j] - (double)centre[c][j] (one rounded
+ *     subtraction), acc = fma(t, t, acc) (one rounding).  The label of a row is the LEAST c with minimal d.
+ *   - FIXED-POINT ROW SUMS.  M = max |x| over the selected rows; e is the integer with M = m * 2^e, 0.5 <= m < 1 (e = 0 if M = 0); b is the bit length of n;
+ *     s = 62 - b - e, which may be negative; q[i][j] = (double)x[i][j] * 2^s (exact) rounded to the nearest integer, ties to even.  S[c][j] is the int64 sum
+ *     of q over the members of c: |q| < 2^(62-b) and n < 2^b, so it cannot overflow, and being an integer sum it is the same in any order.
+ *   - CENTRE UPDATE.  centre[c][j] = (float) ldexp((double)S[c][j] / (double)count[c], -s): int64 to binary64 rounded to nearest even, one division, an exact
+ *     scaling, one rounding to binary32.  A centre without a member keeps its position; info.empty counts those of the final state.
+ *   - BLOCKED SUM.  Every binary64 sum over rows has this one shape: the selected rows, in order, are cut into blocks of 256; each block's values are added
+ *     sequentially from +0.0; the block sums are added sequentially, from +0.0, in block order.  It is used for the inertia and for the seeding totals.
+ *   - SEEDING (k-means++), once per restart r = 0 .. n_init-1.  dge_mix64 is the splitmix64 of csrc/dge_algos.h; the arithmetic is unsigned 64-bit and wraps.
+ *     Centre 0 is row dge_mix64(seed + r*k) % n.  dmin[i] is the least d of row i to the centres chosen so far.  For c = 1 .. k-1:
+ *     u = (dge_mix64(seed + r*k + c) >> 11) * 2^-53;  target = u * total, total being the blocked sum of dmin.  Walk the block sums in order, from +0.0, to
+ *     the first block after which the running total exceeds target; then, starting again from the total in front of that block, add that block's dmin row by
+ *     row: the pick is the first row after which this running sum exceeds target (should rounding let none of the block's rows do so, its last row).  If no
+ *     block exceeds the target (total = 0, or u * total rounding to total), the pick is the row with the greatest dmin, the least row among equals.
+ *     Caller-supplied initial centres (host [k x dim]) replace seeding; n_init is then taken as 1.
+ *   - ITERATION.  Assign labels and count the labels that changed (the first pass counts every row).  If none changed, stop; otherwise update the centres and
+ *     repeat, for at most max_iter assignment passes: after the max_iter-th pass the centres are not updated again.
+ *   - A RESTART gives the labels and d of its last assignment pass, the centres that pass used, and its inertia, the blocked sum of d(i, label_i).
+ *   - THE BEST RESTART is that of least inertia, the lower restart number among equals.  Its labels go to the host as int32[rows] (all rows; a row that is not
+ *     selected gets -1), its centres as float[k x dim].
+ *   - ACCURACY (dge_cluster_accuracy; clusteringAccuracy, :544-571).  labels[n_rows] and gnd[n_rows] hold values in [0, k) or -1 (anything else: DGE_ERR_ARG
+ *     naming the row).  cnt[a][g] counts the rows where labels = a and gnd = g, both >= 0.  Clusters are visited by row total of cnt, descending, the LARGER
+ *     index first among equal totals; for each cluster the ground labels by cnt[a][.], descending, the larger label first among equals; the cluster maps to
+ *     the first label not yet taken.  (That tie order is numpy's argsort(..)[::-1] under a stable sort, which is what numpy uses at these sizes.)
+ *     accuracy = sum of cnt[a][map[a]] / (number of rows with gnd >= 0): the denominator counts labelled regions the embedding lacks, as len(gndTid) does in
+ *     the reference.  A zero denominator gives NaN and DGE_OK.  A host computation: no device involved.
+ *   - NOT the reference's KMeans: no tol stop, no relocation of empty clusters, no greedy multi-trial seeding.  For the reference's per-slice loop a host passes
+ *     `select` masks built from the "h-rid" names.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_kmeans_cfg {
+    int32_t  k;
+    int32_t  n_init;       /* restarts (taken as 1 with initial centres)                                   */
+    int32_t  max_iter;     /* assignment passes of one restart, at most                                    */
+    int32_t  reserved;
+    uint64_t seed;
+} dge_kmeans_cfg;          /* 24 bytes */
+typedef struct dge_kmeans_info {
+    int64_t rows;              /* n: the selected rows                                                     */
+    int32_t best_restart;
+    int32_t iterations;        /* assignment passes of the best restart                                    */
+    int64_t total_iterations;  /* assignment passes of all restarts                                        */
+    int32_t scale_bits;        /* s                                                                        */
+    int32_t empty;             /* centres of the best restart without a member in its last pass            */
+    double  inertia;
+    double  kernel_ms;         /* HIP-event time from the first kernel of the call to its last             */
+} dge_kmeans_info;             /* 48 bytes */
+/* labels: host int32[rows]; centres: host float[k x dim]; select, init_centres and info may be NULL */
+int  dge_kmeans_vectors(const dge_vectors* v, const uint8_t* select, const dge_kmeans_cfg* cfg, const float* init_centres, int32_t* labels, float* centres, dge_kmeans_info* info);
+/* the same on host rows float32 [n_rows x dim], every row present (through dge_vectors_from_host) */
+int  dge_kmeans(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* select, const dge_kmeans_cfg* cfg, const float* init_centres, int32_t* labels,
+                float* centres, dge_kmeans_info* info);
+/* cnt: host int64[k x k], may be NULL; map: host int32[k], may be NULL */
+int  dge_cluster_accuracy(const int32_t* labels, const int32_t* gnd, int64_t n_rows, int32_t k, int64_t* cnt, int32_t* map, double* accuracy);
+
+/* ------------------------------------------------------------------------------------------------
  * Ablation / test knobs of the trainer (process-wide relaxed atomics; nothing in a normal run sets them).  value < 0 puts
  * a knob back to the library's own rule.
  * ---------------------------------------------------------------------------------------------- */
