@@ -20,20 +20,27 @@
 #define KNN_MAX_K 64
 #define KNN_MAX_D 256
 
-__global__ void k_row_norms(const float* __restrict__ x, int n, int D, float* __restrict__ inv_norm) {
+// inv_norm[r] = 1 / |x_r| in binary64, or 0 where the row counts as a zero vector (cosine undefined -> distance 2): an all-zero row, a row with a
+// NaN or an infinity (the sum of squares is then not finite; finite float32 entries cannot overflow it), a row the caller marks absent.  The strip
+// kernel and k_ndcg only ask "is it 0"; the value serves k_normalise, and as a double it holds the inverse of any float32 row's norm (2^-149 .. 2^132).
+__global__ void k_row_norms(const float* __restrict__ x, const uint8_t* __restrict__ present, int n, int D, double* __restrict__ inv_norm) {
     int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     double s = 0.0;
     for (int j = 0; j < D; j++) { double v = x[(size_t)r * D + j]; s += v * v; }
-    inv_norm[r] = s > 0.0 ? (float)(1.0 / sqrt(s)) : 0.0f;       // 0 marks a zero vector: cosine undefined -> distance 2
+    inv_norm[r] = s > 0.0 && s < (double)INFINITY && (!present || present[r]) ? 1.0 / sqrt(s) : 0.0;
 }
 
-// rows scaled to unit norm and zero-padded to Dp floats (a zero vector stays zero: inv_norm 0 marks it)
-__global__ void k_normalise(const float* __restrict__ x, const float* __restrict__ inv_norm, int n, int D, int Dp, float* __restrict__ xn) {
+// rows scaled to unit norm — x * inv in binary64, rounded once — and zero-padded to Dp floats; a zero-marked row is written as zeros whatever it holds.
+// mark[r] = inv_norm[r] != 0 as a float, the form the strip kernel and k_ndcg read.
+__global__ void k_normalise(const float* __restrict__ x, const double* __restrict__ inv_norm, int n, int D, int Dp, float* __restrict__ xn,
+                            float* __restrict__ mark) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)n * Dp) return;
     const int r = (int)(i / Dp), c = (int)(i % Dp);
-    xn[i] = c < D ? x[(size_t)r * D + c] * inv_norm[r] : 0.0f;
+    const double inv = inv_norm[r];
+    xn[i] = c < D && inv != 0.0 ? (float)((double)x[(size_t)r * D + c] * inv) : 0.0f;
+    if (c == 0) mark[r] = inv != 0.0 ? 1.0f : 0.0f;
 }
 
 // (d, col) < (d2, col2): distance ascending, smaller index first among equals
@@ -162,16 +169,20 @@ static int launch_knn(const float* xn, const float* inv, int n, int k, int32_t* 
     return 0;
 }
 
-// device form: x [n x D] in device memory -> lists in device memory
-static int knn_device(const float* d_x, int n, int D, int k, float* d_inv, float* d_xn, int32_t* d_oi, float* d_od, double* ms_kernel) {
+// device form: x [n x D] in device memory -> lists in device memory.  d_present (may be null: every row): one byte a row, 0 = the row counts as a zero
+// vector.  d_inv [n]: left holding 1.0 for a row with a direction, 0.0 for a zero vector (what k_ndcg asks of the ground rows).
+static int knn_device(const float* d_x, const uint8_t* d_present, int n, int D, int k, float* d_inv, float* d_xn, int32_t* d_oi, float* d_od,
+                      double* ms_kernel) {
     const int dh = (D + 1) / 2 <= 16 ? 16 : ((D + 1) / 2 <= 32 ? 32 : ((D + 1) / 2 <= 64 ? 64 : 128));
     const int Dp = 2 * dh;
-    hipLaunchKernelGGL(k_row_norms, dim3((n + 255) / 256), dim3(256), 0, 0, d_x, n, D, d_inv);
-    hipLaunchKernelGGL(k_normalise, dim3((unsigned)(((size_t)n * Dp + 255) / 256)), dim3(256), 0, 0, d_x, d_inv, n, D, Dp, d_xn);
+    dge_tmp<double> d_norm;                       // freed at return, after the hipDeviceSynchronize below (an error return: hipFree itself waits for the device)
+    int rc;
+    if ((rc = d_norm.alloc((size_t)n))) return rc;
+    hipLaunchKernelGGL(k_row_norms, dim3((n + 255) / 256), dim3(256), 0, 0, d_x, d_present, n, D, d_norm.p);
+    hipLaunchKernelGGL(k_normalise, dim3((unsigned)(((size_t)n * Dp + 255) / 256)), dim3(256), 0, 0, d_x, d_norm.p, n, D, Dp, d_xn, d_inv);
     hipEvent_t e0, e1;
     DGE_HIP(hipEventCreate(&e0)); DGE_HIP(hipEventCreate(&e1));
     DGE_HIP(hipEventRecord(e0, 0));
-    int rc;
     if (dh == 16) rc = launch_knn<16>(d_xn, d_inv, n, k, d_oi, d_od, 0);
     else if (dh == 32) rc = launch_knn<32>(d_xn, d_inv, n, k, d_oi, d_od, 0);
     else if (dh == 64) rc = launch_knn<64>(d_xn, d_inv, n, k, d_oi, d_od, 0);
@@ -203,7 +214,7 @@ extern "C" int dge_knn_cosine(int device, const float* features, int32_t n, int3
     if ((rc = d_od.alloc((size_t)n * k))) return rc;
     if ((rc = d_oi.alloc((size_t)n * k))) return rc;
     DGE_HIP(hipMemcpy(d_x.p, features, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice));
-    if ((rc = knn_device(d_x.p, n, D, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, ms_kernel))) return rc;
+    if ((rc = knn_device(d_x.p, nullptr, n, D, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, ms_kernel))) return rc;
     DGE_HIP(hipMemcpy(out_idx, d_oi.p, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost));
     DGE_HIP(hipMemcpy(out_dist, d_od.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost));
     return DGE_OK;
@@ -238,8 +249,8 @@ static int ndcg_device(const float* d_x, int32_t dim, const float* d_g, int32_t 
         (rc = d_xn.alloc((size_t)n * 256)) || (rc = d_gn.alloc((size_t)n * 256)) || (rc = d_od.alloc((size_t)n * k)) || (rc = d_god.alloc((size_t)n * k)) ||
         (rc = d_oi.alloc((size_t)n * k)) || (rc = d_goi.alloc((size_t)n * k)) || (rc = d_ratio.alloc(n))) return rc;
     double ms1 = 0, ms2 = 0;
-    if ((rc = knn_device(d_x, n, dim, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, &ms1))) return rc;
-    if ((rc = knn_device(d_g, n, gnd_dim, k, d_ginv.p, d_gn.p, d_goi.p, d_god.p, &ms2))) return rc;
+    if ((rc = knn_device(d_x, nullptr, n, dim, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, &ms1))) return rc;
+    if ((rc = knn_device(d_g, nullptr, n, gnd_dim, k, d_ginv.p, d_gn.p, d_goi.p, d_god.p, &ms2))) return rc;
     const int gdh = (gnd_dim + 1) / 2 <= 16 ? 16 : ((gnd_dim + 1) / 2 <= 32 ? 32 : ((gnd_dim + 1) / 2 <= 64 ? 64 : 128));
     hipLaunchKernelGGL(k_ndcg, dim3((n + 3) / 4), dim3(256), 0, 0, d_gn.p, d_ginv.p, 2 * gdh, n, k, d_oi.p, d_god.p, d_ratio.p);
     DGE_HIP(hipGetLastError());
@@ -283,7 +294,7 @@ extern "C" int dge_knn_cosine_vectors(const dge_vectors* v, int32_t k, int32_t* 
     const int n = (int)v->rows;
     dge_tmp<float> d_inv, d_od, d_xn; dge_tmp<int32_t> d_oi;
     if ((rc = d_xn.alloc((size_t)n * 256)) || (rc = d_inv.alloc((size_t)n)) || (rc = d_od.alloc((size_t)n * k)) || (rc = d_oi.alloc((size_t)n * k))) return rc;
-    if ((rc = knn_device(v->d, n, v->dim, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, ms_kernel))) return rc;
+    if ((rc = knn_device(v->d, v->d_present, n, v->dim, k, d_inv.p, d_xn.p, d_oi.p, d_od.p, ms_kernel))) return rc;
     DGE_HIP(hipMemcpy(out_idx, d_oi.p, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost));
     DGE_HIP(hipMemcpy(out_dist, d_od.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost));
     return DGE_OK;

@@ -727,13 +727,18 @@ int  dge_model_gather_table(dge_model* m, dge_comm* c, int table);
  * Quality metric ("next" row of the scope table): pairwiseEstimator of P/embeddingEvaluation_tract.py:169-196 — for every
  * row of features [n x dim] the k other rows nearest in cosine distance (1 - cos; a zero vector is at distance 2 from
  * everything), ascending, smaller index first among equals.  Exact-f32 MFMA tiles fused with the top-k selection.
- * dim <= 256, k <= 64.  Host buffers.
+ * dim <= 256, k <= 64.  Host buffers.  Slots beyond n-1 neighbours hold -1 / 3.0.
+ * RULE: a row with a non-finite entry (NaN, +-infinity) counts as a zero vector, as the reference's NaN -> 2 puts it at distance 2 from
+ * everything.  Every other non-zero row, of any float32 magnitude (all-subnormal entries included), is scaled to a unit row: x * (1 / |x|)
+ * formed in binary64 and rounded once.
  * ---------------------------------------------------------------------------------------------- */
 int  dge_knn_cosine(int device, const float* features, int32_t n, int32_t dim, int32_t k, int32_t* out_idx, float* out_dist,
                     double* ms_kernel);
 /* ndcg_atK of P/embeddingEvaluation_tract.py:249-260 wholly on the device: the k nearest neighbours of every region in `features`
  * [n x dim] are scored with relevance 1 - (cosine distance in gnd_features [n x gnd_dim]), DCG = sum_i relv_i / log2(i + 1), normalised
- * by the DCG of the ground features' own k nearest; *ndcg = mean over the n regions (rows of the two arrays are the same regions). */
+ * by the DCG of the ground features' own k nearest; *ndcg = mean over the n regions (rows of the two arrays are the same regions).
+ * RULE: a region whose ideal DCG is exactly 0 (e.g. every one of its k nearest ground neighbours orthogonal to it) contributes 0 to the
+ * mean, where the reference would divide by zero.  Zero and non-finite rows, of either array, are zero vectors as above. */
 int  dge_ndcg_at_k(int device, const float* features, int32_t dim, const float* gnd_features, int32_t gnd_dim, int32_t n, int32_t k,
                    double* ndcg, double* ms_kernels);
 
@@ -800,7 +805,7 @@ void dge_vectors_free(dge_vectors* v);
 int  dge_model_load_vectors(dge_model* m, const dge_vectors* v, int64_t* rows_set);
 
 /* the two quality entries above on resident rows: the same kernels, no host round trip of the features */
-int  dge_knn_cosine_vectors(const dge_vectors* v, int32_t k, int32_t* out_idx, float* out_dist, double* ms_kernel);           /* absent rows are zero vectors */
+int  dge_knn_cosine_vectors(const dge_vectors* v, int32_t k, int32_t* out_idx, float* out_dist, double* ms_kernel);           /* absent rows are zero vectors, whatever they hold */
 int  dge_ndcg_at_k_vectors(const dge_vectors* f, const dge_vectors* gnd, int32_t k, double* ndcg, double* ms_kernels);         /* equal row counts, every row present in both: else DGE_ERR_ARG */
 
 /* ------------------------------------------------------------------------------------------------

@@ -153,6 +153,9 @@ def test_quality_entries_on_resident_rows(dge):
     part = dge.Vectors.from_host(f, present)
     idx, dist, _ = part.knn(5)
     assert idx.shape == (n, 5)
+    f0 = f.copy(); f0[17] = 0
+    idx0, dist0, _ = evaluate.knn_cosine_gpu(f0, 5)                                           # (more absent rows, exactly: tests/test_gpu_knn_exact.py)
+    assert np.array_equal(idx, idx0) and np.array_equal(bits(dist), bits(dist0)) and (dist[17] == 2).all()
     for a, b in ((part, vg), (vg, part)):
         with pytest.raises(dge.DgeError) as ei:
             a.ndcg_against(b, 5)
