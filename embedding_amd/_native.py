@@ -107,7 +107,19 @@ class KmeansInfo(C.Structure):
                 ("empty", C.c_int32), ("inertia", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class NmfCfg(C.Structure):
+    """struct dge_nmf_cfg (include/dge.h)."""
+    _fields_ = [("rank", C.c_int32), ("max_iter", C.c_int32), ("update", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class NmfInfo(C.Structure):
+    """struct dge_nmf_info (include/dge.h) — what dge_nmf_coo / dge_nmf_flows report."""
+    _fields_ = [("rows", C.c_int64), ("cols", C.c_int64), ("entries", C.c_int64), ("zeros", C.c_int64), ("iterations", C.c_int32), ("reserved", C.c_int32),
+                ("vmax", C.c_double), ("objective", C.c_double), ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
+DGE_NMF_DIVERGENCE, DGE_NMF_EUCLIDEAN = 0, 1
 DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
 
 # every symbol include/dge.h declares: name -> (restype, argtypes)
@@ -236,6 +248,8 @@ SIGNATURES = {
     "dge_kmeans_vectors": (_int, [_vp, _vp, _P(KmeansCfg), _vp, _vp, _vp, _P(KmeansInfo)]),
     "dge_kmeans": (_int, [_int, _vp, _i64, _i32, _vp, _P(KmeansCfg), _vp, _vp, _vp, _P(KmeansInfo)]),
     "dge_cluster_accuracy": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _P(_dbl)]),
+    "dge_nmf_coo": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _P(NmfCfg), _vp, _vp, _vp, _vp, _P(NmfInfo)]),
+    "dge_nmf_flows": (_int, [_vp, _i32, _i32, _i32, _vp, _P(NmfCfg), _vp, _vp, _vp, _P(NmfInfo)]),
     "dge_selftest_locked_rows": (_int, [_int, _i32, _i64, _i32, C.c_uint64, _i32, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave": (_int, [_int, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),

@@ -169,6 +169,11 @@ int dge_flows_device(const dge_flows* f);
 int dge_flows_like(const dge_flows* f, dge_flows** out);          // an empty table over f's regions
 int dge_flows_merge(dge_flows* f, const dge_flows* part);          // part's table and counters into f; on error f is as it was
 
+// the edges dge_flows_slot_edges gives for `slot`, restricted to the regions with a non-zero select byte (NULL: all) and re-indexed in ascending region index, as
+// device entries (row = source, col = destination, val = weight) in no particular order; regions: the selected region indices, ascending (nmf.hip reads it)
+int dge_flows_slot_coo(const dge_flows* f, int32_t T, int32_t mode, int32_t slot, const uint8_t* select, const char* who, dge_tmp<int32_t>& row, dge_tmp<int32_t>& col,
+                       dge_tmp<double>& val, int64_t* n_entries, std::vector<int64_t>& regions);
+
 int dge_graph_ensure_csr(dge_graph* g);
 // the end state of keepNearestKVertices (graph.hip): the store becomes the given CSR of n_edges edges (device arrays, taken over; g->d_outdeg already holds the
 // recomputed outDegree), the tables are void, the sources' weights are refreshed.  dge_graph_keep_top_k ends in it; spatial.hip hands its edges over through it.

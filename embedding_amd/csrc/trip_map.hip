@@ -196,6 +196,20 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_slot_decode(const uint64_t* key, 
     iota[i] = i;
 }
 
+// the slot's edges inside a selection as matrix entries: map[rank] = the compact index of the region of that rank, or -1.  The positions come from a counter:
+// the order of the entries is of no account to their reader, which sorts them
+__global__ void __launch_bounds__(SEQ_BLOCK) k_slot_coo(const uint64_t* key, const int64_t* w, int64_t n, uint64_t R, int32_t slot, const int32_t* map, int32_t* row, int32_t* col,
+                                                        double* val, unsigned long long* count) {
+    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t k = key[i];
+    if ((int32_t)(k / R / R) != slot) return;
+    const int32_t a = map[(k / R) % R], b = map[k % R];
+    if (a < 0 || b < 0) return;
+    const unsigned long long at = atomicAdd(count, 1ULL);
+    row[at] = a; col[at] = b; val[at] = (double)w[i];
+}
+
 // ------------------------------------------------------------------------------------------ host side
 namespace {
 
@@ -683,6 +697,49 @@ extern "C" int dge_flows_slot_edges(const dge_flows* f, int32_t T, int32_t mode,
     SEQ_TRY(seq_read_back(R, src_id, A.src_id.p, (size_t)E * 8));
     SEQ_TRY(seq_read_back(R, dst_id, A.dst_id.p, (size_t)E * 8));
     return seq_read_back(R, w, ow.p, (size_t)E * 8);
+}
+
+int dge_flows_slot_coo(const dge_flows* f, int32_t T, int32_t mode, int32_t slot, const uint8_t* select, const char* who, dge_tmp<int32_t>& row, dge_tmp<int32_t>& col,
+                       dge_tmp<double>& val, int64_t* n_entries, std::vector<int64_t>& regions) {
+    *n_entries = 0;
+    SEQ_TRY(slot_check(T, mode, who));
+    if (slot < 0 || slot >= T) DGE_FAIL(DGE_ERR_ARG, "%s: slot = %d is outside 0 .. %d", who, slot, T - 1);
+    const dge_regions* rg = f->regions;
+    const int64_t Rn = rg->R;
+    regions.clear();
+    for (int64_t i = 0; i < Rn; i++) if (!select || select[i]) regions.push_back(i);
+    if (regions.empty()) DGE_FAIL(DGE_ERR_ARG, "%s: no region is selected", who);
+    if (f->n == 0) DGE_FAIL(DGE_ERR_ARG, "%s: slot %d holds no entry: the table is empty", who, slot);
+    SEQ_TRY(dge_require_device(rg->device));
+    SeqRun R;
+    SEQ_TRY(trip_open(R, rg->device, who));
+    // rank of a region's id -> its number among the selected regions
+    std::vector<int32_t> idrank((size_t)Rn), map((size_t)Rn, -1);
+    SEQ_TRY(seq_read_back(R, idrank.data(), rg->d_idrank, (size_t)Rn * 4));
+    for (size_t c = 0; c < regions.size(); c++) map[(size_t)idrank[(size_t)regions[c]]] = (int32_t)c;
+    dge_tmp<uint64_t> okey;
+    dge_tmp<int64_t> ow;
+    dge_tmp<int32_t> d_map;
+    dge_tmp<unsigned long long> count;
+    int64_t E = 0;
+    SEQ_TRY(trip_slot_edges(R, f, T, mode, okey, ow, &E));
+    unsigned long long got = 0;
+    if (E > 0) {
+        SEQ_TRY(seq_alloc(R, d_map, Rn, "the regions' numbers"));
+        SEQ_TRY(seq_alloc(R, count, 1, "the number of entries"));
+        SEQ_TRY(seq_alloc(R, row, E, "the entries' rows"));
+        SEQ_TRY(seq_alloc(R, col, E, "the entries' columns"));
+        SEQ_TRY(seq_alloc(R, val, E, "the entries' values"));
+        DGE_HIP(hipMemcpyAsync(d_map.p, map.data(), (size_t)Rn * 4, hipMemcpyHostToDevice, R.stream));
+        DGE_HIP(hipMemsetAsync(count.p, 0, 8, R.stream));
+        SEQ_TRY(seq_kernels_begin(R));
+        hipLaunchKernelGGL(k_slot_coo, dim3(seq_grid(E)), dim3(SEQ_BLOCK), 0, R.stream, okey.p, ow.p, E, (uint64_t)std::max<int64_t>(Rn, 1), slot, d_map.p, row.p, col.p, val.p, count.p);
+        SEQ_TRY(seq_kernels_end(R));
+        SEQ_TRY(seq_read_back(R, &got, count.p, 8));
+    }
+    if (got == 0) DGE_FAIL(DGE_ERR_ARG, "%s: slot %d holds no entry between the selected regions", who, slot);
+    *n_entries = (int64_t)got;
+    return DGE_OK;
 }
 
 extern "C" void dge_flows_free(dge_flows* f) {

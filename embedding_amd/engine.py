@@ -261,7 +261,9 @@ class Regions:
             raise ValueError("ring_first has R + 1 entries, vert_first rings + 1")
         h = C.c_void_p(0)
         check(lib.dge_regions_create(int(device), _ptr(ids), len(ids), _ptr(ring_first), _ptr(vert_first), _ptr(xy), len(vert_first) - 1, len(xy), int(grid), C.byref(h)))
-        return cls(h, device)
+        self = cls(h, device)
+        self.ids = ids.copy()              # region index -> id (Flows.nmf names its rows with it)
+        return self
 
     def close(self):
         if getattr(self, "_h", None):
@@ -385,6 +387,29 @@ class Flows:
         if m:
             check(lib.dge_flows_slot_edges(self._h, int(T), int(mode), _ptr(slot), _ptr(src), _ptr(dst), _ptr(w), m, C.byref(n)))
         return slot, src, dst, w
+
+    def nmf(self, slot, T=8, mode=DGE_SLOTS_EVEN, select=None, **kw):
+        """NMF of the flow matrix of one slot (dge_nmf_flows; the rule of include/dge.h): V[src][dst] = w over the edges slot_edges(T, mode) gives for `slot`,
+        restricted to the regions select marks (one entry per region, by region index; None: all) and re-indexed in ascending region index — what the reference
+        gets from outputAdjacencyMatrix, np.loadtxt and the idx sub-matrix (P/matrixFactorization_tract.py:32-38), built on the device from the resident table.
+        kw: rank, max_iter, update, seed as evaluate.nmf_gpu takes them.  nmf(0, T=1) factors taxi-all.matrix.
+        -> (W float64 [n x rank], H float64 [rank x n], region_ids int64 [n], info)"""
+        from ._native import NmfInfo
+        from .evaluate import nmf_config
+        cfg = nmf_config(**kw)
+        R = self.regions.info()["regions"]
+        if select is not None:
+            select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+            if select.shape != (R,):
+                raise ValueError("select must hold one entry per region")
+        n = R if select is None else int(select.sum())
+        rank = max(cfg.rank, 0)
+        W = np.empty((n, rank), np.float64); H = np.empty((rank, n), np.float64); index = np.empty(n, np.int64); inf = NmfInfo()
+        check(lib.dge_nmf_flows(self._h, int(T), int(mode), int(slot), _ptr(select), C.byref(cfg), _ptr(W), _ptr(H), _ptr(index), C.byref(inf)))
+        ids = getattr(self.regions, "ids", None)
+        info = {k: v for k, v in _info_dict(inf).items() if k != "reserved"}
+        info["region_index"] = index
+        return W, H, (ids[index] if ids is not None else index), info
 
     def to_od_bytes(self, T, mode=DGE_SLOTS_EVEN):
         """The T .od texts (J/Tracts.java:236-260), formatted on the host from slot_edges: the tables are small."""

@@ -1,7 +1,8 @@
 """Quality metric of the reference's evaluation scripts on the device (P/embeddingEvaluation_tract.py:169-196 pairwiseEstimator, :249-260
 ndcg_atK): ctypes views of dge_knn_cosine / dge_ndcg_at_k.  Used as the statistical parity check between training schedules (in-order /
 Hogwild / multi-GPU) on one slice; and the reference's second figure, clusteringAccuracy (:539-571), on a k-means that is a fully specified rule
-(include/dge.h: dge_kmeans_vectors, dge_cluster_accuracy) instead of scikit-learn's randomised one.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
+(include/dge.h: dge_kmeans_vectors, dge_cluster_accuracy) instead of scikit-learn's randomised one; and the figures' "MF" baseline, NMF of a slice's flow matrix
+(P/matrixFactorization_tract.py:26-45), likewise a rule (dge_nmf_coo, dge_nmf_flows) instead of nimfa's randomised runs.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
 import numpy as np
 
 
@@ -87,3 +88,47 @@ def clustering_accuracy_vectors(vectors, gnd_labels, k, seed=1, n_init=10, max_i
     acc, cnt, m = clustering_accuracy(labels, gnd_labels, k)
     info = dict(info, cnt=cnt, map=m)
     return acc, labels, info
+
+
+NMF_UPDATES = {"divergence": 0, "euclidean": 1}
+
+
+def nmf_config(rank=10, max_iter=30, update="divergence", seed=1):
+    """struct dge_nmf_cfg from the keywords nmf_gpu and Flows.nmf share; update: "divergence" / "euclidean" (nimfa's names) or 0 / 1."""
+    from ._native import NmfCfg
+    if isinstance(update, str):
+        if update not in NMF_UPDATES:
+            raise ValueError("update must be 'divergence' or 'euclidean', not %r" % (update,))
+        update = NMF_UPDATES[update]
+    return NmfCfg(int(rank), int(max_iter), int(update), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def nmf_gpu(rows, cols, vals, shape, rank=10, max_iter=30, update="divergence", seed=1, init=None, device=0):
+    """NMF of the sparse matrix V [n x m] = shape given as entries (rows[e], cols[e], vals[e]), on the device as the rule of include/dge.h (dge_nmf_coo): the
+    same bits for the same entries in any order, shape, rank, max_iter, update and seed.  init: (W [n x rank], H [rank x m]) replaces the generated factors.
+    -> (W float64 [n x rank], H float64 [rank x m], info: the fields of struct dge_nmf_info)."""
+    import ctypes as C
+    from ._native import NmfInfo, check, lib
+    r = np.ascontiguousarray(rows, np.int32); c = np.ascontiguousarray(cols, np.int32); v = np.ascontiguousarray(vals, np.float64)
+    if not (r.ndim == c.ndim == v.ndim == 1 and len(r) == len(c) == len(v)):
+        raise ValueError("rows, cols and vals must be one-dimensional and of one length")
+    n, m = int(shape[0]), int(shape[1])
+    cfg = nmf_config(rank, max_iter, update, seed)
+    rank = cfg.rank
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    iw = ih = None
+    if init is not None:
+        iw = np.ascontiguousarray(init[0], np.float64); ih = np.ascontiguousarray(init[1], np.float64)
+        if iw.shape != (n, rank) or ih.shape != (rank, m):
+            raise ValueError("init must be (W [%d x %d], H [%d x %d])" % (n, rank, rank, m))
+    W = np.empty((max(n, 0), max(rank, 0)), np.float64); H = np.empty((max(rank, 0), max(m, 0)), np.float64); inf = NmfInfo()
+    check(lib.dge_nmf_coo(int(device), p(r), p(c), p(v), len(v), n, m, C.byref(cfg), p(iw), p(ih), p(W), p(H), C.byref(inf)))
+    return W, H, {fl[0]: getattr(inf, fl[0]) for fl in NmfInfo._fields_ if fl[0] != "reserved"}
+
+
+def nmf_features(W, H):
+    """A region's MF feature as the reference forms it: concat(W, H^T) (P/matrixFactorization_tract.py:44).  Square matrices only."""
+    W = np.asarray(W); H = np.asarray(H)
+    if W.ndim != 2 or H.ndim != 2 or W.shape[1] != H.shape[0] or W.shape[0] != H.shape[1]:
+        raise ValueError("nmf_features needs W [n x rank] and H [rank x n] of a square matrix, not %s and %s" % (list(W.shape), list(H.shape)))
+    return np.concatenate([W, H.T], axis=1)

@@ -876,6 +876,77 @@ int  dge_kmeans(int device, const float* features, int64_t n_rows, int32_t dim, 
 int  dge_cluster_accuracy(const int32_t* labels, const int32_t* gnd, int64_t n_rows, int32_t k, int64_t* cnt, int32_t* map, double* accuracy);
 
 /* ------------------------------------------------------------------------------------------------
+ * NMF of a sparse matrix (new; additions only, DGE_VERSION unchanged): the "MF" column of the reference's figures (P/embeddingEvaluation_tract.py:318-342,604).
+ * The reference writes R x R text matrices (Tracts.outputAdjacencyMatrix, J/Tracts.java:269-301), reads them back with np.loadtxt and factors them with
+ * nimfa.Nmf(rank=10, max_iter=30, update="divergence") (P/matrixFactorization_tract.py:26-45; P/flowFeatureGeneration_tract.py:29-40 takes the Euclidean update
+ * and 100 iterations); a region's feature is concat(W, H^T).  nimfa draws its own random numbers: two of its runs do not agree.  Here NMF is a RULE
+ * (csrc/nmf.hip; the per-element pieces: csrc/nmf_rule.h): W and H are a pure function of the entries, the shape, rank, max_iter, update and the seed (or the
+ * initial factors).  Nothing depends on timing, launch geometry or the order of the input entries, and nothing of size n x m is ever formed.  Everything is
+ * binary64; fma(a, b, c) is a * b + c with ONE rounding; every other operation rounds once.  tests/nmf_ref.py is this text in Python.
+ *   - INPUT.  A matrix V [n x m] as n_entries entries (row, col, val).  An entry outside the matrix: DGE_ERR_ARG naming the least such input index.  A value
+ *     that is not finite: DGE_ERR_ARG naming the least such input index; then a value < 0: DGE_ERR_ARG likewise.  A value == 0 is dropped and counted in
+ *     info.zeros.  A second kept entry with the (row, col) of another: DGE_ERR_ARG naming the least input index that is not the first of its (row, col).  The
+ *     KEPT entries are held twice: by row with the columns ascending, by column with the rows ascending; "entry e" is one of them.  Limits: 1 <= rank <= 32,
+ *     1 <= n, m <= 2^31 - 1, 1 <= n_entries <= 2^31 - 1 with at least one kept, 1 <= max_iter <= 10000, update 0 (divergence) or 1 (euclidean).  Null
+ *     arguments, limit violations and bad initial factors: DGE_ERR_ARG before a device is looked for.  On any error the outputs are untouched.
+ *   - INIT.  vmax = the greatest kept value.  u(t) = (dge_mix64(seed + t) >> 11) * 2^-53 (dge_mix64: the splitmix64 of csrc/dge_algos.h; unsigned 64-bit
+ *     arithmetic, wrapping).  W[i][r] = u(i*rank + r) * vmax;  H[r][j] = u(n*rank + r*m + j) * vmax.  Caller-supplied W and H (host doubles, both or neither,
+ *     every value finite and >= 0) replace this.
+ *   - FLOOR.  EPS = 2^-52; a value of W or H below EPS becomes EPS: after INIT (supplied factors included) and after every update.  This is nimfa's
+ *     adjustment step AS RECALLED — nimfa is not at hand where this was written, so the constant and the place are not verified against it.
+ *   - SEGMENT SUM of a list of products a_t * b_t, t = 0 .. c-1.  16 partials p[0 .. 15] start at +0.0; product t goes to partial t mod 16, in ascending t:
+ *     p[l] = fma(a_t, b_t, p[l]).  Then for s = 8, 4, 2, 1 and every l < s: p[l] = p[l] + p[l+s].  The sum is p[0]; an empty list gives +0.0.  (16 lanes are
+ *     one DPP row: the fold is four row shifts.)
+ *   - BLOCKED SUM of a list of values: k-means' shape exactly — blocks of 256 added sequentially from +0.0, the block sums added sequentially from +0.0.
+ *   - P[e], for entry e = (i, j): acc = +0.0; for r ascending: acc = fma(W[i][r], H[r][j], acc).
+ *   - DIVERGENCE iteration (nimfa update="divergence": Lee and Seung's rule for the Kullback-Leibler divergence).
+ *       1. Q[e] = V[e] / P[e].                 2. N[r][j] = SEGMENT SUM over column j's entries (rows ascending) of W[i][r] * Q[e].
+ *       3. d[r] = BLOCKED SUM over i of W[i][r].                 4. H[r][j] = FLOOR(H[r][j] * (N[r][j] / d[r])): one division, then one multiplication.
+ *       5. P and Q again, with the new H.       6. N'[i][r] = SEGMENT SUM over row i's entries (columns ascending) of Q[e] * H[r][j].
+ *       7. d'[r] = BLOCKED SUM over j of H[r][j].                8. W[i][r] = FLOOR(W[i][r] * (N'[i][r] / d'[r])).
+ *   - EUCLIDEAN iteration (nimfa's default update).
+ *       1. A[r][j] = SEGMENT SUM over column j's entries of W[i][r] * V[e].      2. G[r][s] = BLOCKED SUM over i of the rounded product W[i][r] * W[i][s].
+ *       3. B[r][j]: acc = +0.0; for s ascending: acc = fma(G[r][s], H[s][j], acc) — every B from the OLD H.       4. H[r][j] = FLOOR(H[r][j] * (A[r][j] / B[r][j])).
+ *       5. with the new H: A'[i][r] = SEGMENT SUM over row i's entries of V[e] * H[r][j].      6. G'[r][s] = BLOCKED SUM over j of the rounded product H[r][j] * H[s][j].
+ *       7. B'[i][r]: acc = +0.0; for s ascending: acc = fma(W[i][s], G'[s][r], acc) — every B' from the OLD W.    8. W[i][r] = FLOOR(W[i][r] * (A'[i][r] / B'[i][r])).
+ *   - STOP.  Exactly max_iter iterations.  (The reference's objective="conn", conn_change=50 cannot stop before its max_iter=30 either.)
+ *   - NOT nimfa: the random numbers are this rule's own, there is no connectivity test and there are no multiple runs.
+ *   - OBJECTIVE (info.objective), of the final factors; OUTSIDE the exact rule, because the device's log is not libm's.  Divergence: the sum over the entries of
+ *     V log(V / P) - V, plus the sum over r of cw[r] * ch[r] (cw, ch: the blocked column sums of W and row sums of H) — the generalised Kullback-Leibler
+ *     divergence of V from W H.  Euclidean: the sum over the entries of (V - P)^2 - P^2, plus the sum over r, s of G[r][s] * G'[r][s] — the squared Frobenius
+ *     distance.  tests hold it to (entries + rank^2 + 8) * 2^-50 * (the sum of the absolute values of those terms).
+ *   - dge_nmf_flows replaces outputAdjacencyMatrix + loadtxt + the idx sub-matrix (P/matrixFactorization_tract.py:32-38): its entries are exactly the edges
+ *     dge_flows_slot_edges(f, T, mode, ..) gives for `slot`, V[index(src)][index(dst)] = w, restricted to the regions with a non-zero select byte ([R], NULL:
+ *     all) and re-indexed in ascending region index; n = m = the number of selected regions, region_index[n] (may be NULL) lists them.  The matrix is built on
+ *     the device from the resident table.  No selected region, or no entry of the slot between them: DGE_ERR_ARG.  dge_nmf_flows(f, 1, mode, 0, ..) factors
+ *     taxi-all.matrix.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_nmf_cfg {
+    int32_t  rank;
+    int32_t  max_iter;     /* iterations: exactly this many                                                */
+    int32_t  update;       /* 0 divergence, 1 euclidean                                                    */
+    int32_t  reserved;
+    uint64_t seed;
+} dge_nmf_cfg;             /* 24 bytes */
+typedef struct dge_nmf_info {
+    int64_t rows;              /* n                                                                        */
+    int64_t cols;              /* m                                                                        */
+    int64_t entries;           /* kept                                                                     */
+    int64_t zeros;             /* dropped                                                                  */
+    int32_t iterations;
+    int32_t reserved;
+    double  vmax;
+    double  objective;
+    double  kernel_ms;         /* HIP-event time from the first kernel of the call to its last             */
+} dge_nmf_info;                /* 64 bytes */
+/* row, col, val: host arrays of n_entries; W: host double[n x rank]; H: host double[rank x m]; init_W, init_H (both or neither) and info may be NULL */
+int  dge_nmf_coo(int device, const int32_t* row, const int32_t* col, const double* val, int64_t n_entries, int64_t n, int64_t m, const dge_nmf_cfg* cfg, const double* init_W,
+                 const double* init_H, double* W, double* H, dge_nmf_info* info);
+/* W: host double[n x rank], H: host double[rank x n] and region_index: host int64[n], n = the selected regions (at most the table's regions) */
+int  dge_nmf_flows(const dge_flows* f, int32_t T, int32_t mode, int32_t slot, const uint8_t* select, const dge_nmf_cfg* cfg, double* W, double* H, int64_t* region_index,
+                   dge_nmf_info* info);
+
+/* ------------------------------------------------------------------------------------------------
  * Ablation / test knobs of the trainer (process-wide relaxed atomics; nothing in a normal run sets them).  value < 0 puts
  * a knob back to the library's own rule.
  * ---------------------------------------------------------------------------------------------- */
