@@ -118,6 +118,17 @@ class NmfInfo(C.Structure):
                 ("vmax", C.c_double), ("objective", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class LineCfg(C.Structure):
+    """struct dge_line_cfg (include/dge.h)."""
+    _fields_ = [("dim", C.c_int32), ("order", C.c_int32), ("negative", C.c_int32), ("batch", C.c_int32), ("samples", C.c_int64), ("rho0", C.c_double), ("seed", C.c_uint64)]
+
+
+class LineInfo(C.Structure):
+    """struct dge_line_info (include/dge.h) — what dge_line_coo / dge_line_flows report."""
+    _fields_ = [("vertices", C.c_int64), ("entries", C.c_int64), ("zeros", C.c_int64), ("batches", C.c_int64), ("samples", C.c_int64), ("total_weight", C.c_int64),
+                ("neg_total", C.c_int64), ("max_abs", C.c_double), ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
 DGE_NMF_DIVERGENCE, DGE_NMF_EUCLIDEAN = 0, 1
 DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
@@ -250,6 +261,8 @@ SIGNATURES = {
     "dge_cluster_accuracy": (_int, [_vp, _vp, _i64, _i32, _vp, _vp, _P(_dbl)]),
     "dge_nmf_coo": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _P(NmfCfg), _vp, _vp, _vp, _vp, _P(NmfInfo)]),
     "dge_nmf_flows": (_int, [_vp, _i32, _i32, _i32, _vp, _P(NmfCfg), _vp, _vp, _vp, _P(NmfInfo)]),
+    "dge_line_coo": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _P(LineCfg), _vp, _vp, _vp, _vp, _vp, _P(LineInfo)]),
+    "dge_line_flows": (_int, [_vp, _i32, _i32, _i32, _vp, _P(LineCfg), _vp, _vp, _vp, _vp, _P(LineInfo)]),
     "dge_selftest_locked_rows": (_int, [_int, _i32, _i64, _i32, C.c_uint64, _i32, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave": (_int, [_int, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),

@@ -411,6 +411,29 @@ class Flows:
         info["region_index"] = index
         return W, H, (ids[index] if ids is not None else index), info
 
+    def line(self, slot, T=8, mode=DGE_SLOTS_EVEN, select=None, **kw):
+        """LINE on the flow graph of one slot (dge_line_flows; the rule of include/dge.h): the edges slot_edges(T, mode) gives for `slot`, restricted to the
+        regions select marks (one entry per region, by region index; None: all) and re-indexed in ascending region index, exactly as Flows.nmf takes them; the
+        graph is built on the device from the resident table.  kw: dim, order, negative, samples, batch, rho0, seed as evaluate.line_gpu takes them.
+        line(0, T=1) trains on taxi-all.od.
+        -> (X float64 [n x dim], Y float64 [n x dim], touched bool [n], region_ids int64 [n], info)"""
+        from ._native import LineInfo
+        from .evaluate import line_config
+        cfg = line_config(**kw)
+        R = self.regions.info()["regions"]
+        if select is not None:
+            select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+            if select.shape != (R,):
+                raise ValueError("select must hold one entry per region")
+        n = R if select is None else int(select.sum())
+        dim = max(cfg.dim, 0)
+        X = np.empty((n, dim), np.float64); Y = np.empty((n, dim), np.float64); touched = np.empty(n, np.uint8); index = np.empty(n, np.int64); inf = LineInfo()
+        check(lib.dge_line_flows(self._h, int(T), int(mode), int(slot), _ptr(select), C.byref(cfg), _ptr(X), _ptr(Y), _ptr(touched), _ptr(index), C.byref(inf)))
+        ids = getattr(self.regions, "ids", None)
+        info = _info_dict(inf)
+        info["region_index"] = index
+        return X, Y, touched.astype(bool), (ids[index] if ids is not None else index), info
+
     def to_od_bytes(self, T, mode=DGE_SLOTS_EVEN):
         """The T .od texts (J/Tracts.java:236-260), formatted on the host from slot_edges: the tables are small."""
         slot, src, dst, w = self.slot_edges(T, mode)
@@ -609,6 +632,13 @@ class Vectors:
         h = C.c_void_p(0)
         check(lib.dge_vectors_from_host(int(device), _ptr(rows), n, dim, _ptr(present), C.byref(h)))
         return cls(h, int(device))
+
+    @classmethod
+    def from_line(cls, X, touched, device=0):
+        """The rows of a LINE result (evaluate.line_gpu, Flows.line) as resident float32 rows with present = touched: a vertex no kept edge names is left out
+        of KNN, nDCG and k-means, as a region the reference's LINE output lacks is."""
+        from .evaluate import line_features
+        return cls.from_host(line_features(X, touched, np.float32), present=np.asarray(touched) != 0, device=device)
 
     def close(self):
         if getattr(self, "_h", None):

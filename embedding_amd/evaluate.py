@@ -2,7 +2,8 @@
 ndcg_atK): ctypes views of dge_knn_cosine / dge_ndcg_at_k.  Used as the statistical parity check between training schedules (in-order /
 Hogwild / multi-GPU) on one slice; and the reference's second figure, clusteringAccuracy (:539-571), on a k-means that is a fully specified rule
 (include/dge.h: dge_kmeans_vectors, dge_cluster_accuracy) instead of scikit-learn's randomised one; and the figures' "MF" baseline, NMF of a slice's flow matrix
-(P/matrixFactorization_tract.py:26-45), likewise a rule (dge_nmf_coo, dge_nmf_flows) instead of nimfa's randomised runs.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
+(P/matrixFactorization_tract.py:26-45), likewise a rule (dge_nmf_coo, dge_nmf_flows) instead of nimfa's randomised runs; and their "LINE" baseline
+(P/flowFeatureGeneration_tract.py:54-73), a rule as well (dge_line_coo, dge_line_flows) instead of a third-party tool's racing threads.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
 import numpy as np
 
 
@@ -132,3 +133,48 @@ def nmf_features(W, H):
     if W.ndim != 2 or H.ndim != 2 or W.shape[1] != H.shape[0] or W.shape[0] != H.shape[1]:
         raise ValueError("nmf_features needs W [n x rank] and H [rank x n] of a square matrix, not %s and %s" % (list(W.shape), list(H.shape)))
     return np.concatenate([W, H.T], axis=1)
+
+
+def line_config(dim=20, order=2, negative=5, samples=1000000, batch=4096, rho0=0.025, seed=1):
+    """struct dge_line_cfg from the keywords line_gpu and Flows.line share."""
+    from ._native import LineCfg
+    return LineCfg(int(dim), int(order), int(negative), int(batch), int(samples), float(rho0), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def line_gpu(src, dst, w, n, dim=20, order=2, negative=5, samples=1000000, batch=4096, rho0=0.025, seed=1, init=None, device=0):
+    """LINE on the directed weighted graph of n vertices given as entries (src[e], dst[e], w[e]), on the device as the rule of include/dge.h (dge_line_coo): the
+    same bits for the same entries in any order, n, dim, order, negative, samples, batch, rho0 and seed.  init: X [n x dim], or (X, Y), replaces the generated
+    tables.  -> (X float64 [n x dim], Y float64 [n x dim], touched bool [n], info: the fields of struct dge_line_info)."""
+    import ctypes as C
+    from ._native import LineInfo, check, lib
+    s = np.ascontiguousarray(src, np.int32); d = np.ascontiguousarray(dst, np.int32); v = np.ascontiguousarray(w, np.float64)
+    if not (s.ndim == d.ndim == v.ndim == 1 and len(s) == len(d) == len(v)):
+        raise ValueError("src, dst and w must be one-dimensional and of one length")
+    n = int(n)
+    cfg = line_config(dim, order, negative, samples, batch, rho0, seed)
+    dim = cfg.dim
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    ix = iy = None
+    if init is not None:
+        if isinstance(init, (tuple, list)):
+            ix, iy = init
+        else:
+            ix = init
+        ix = np.ascontiguousarray(ix, np.float64)
+        iy = None if iy is None else np.ascontiguousarray(iy, np.float64)
+        if ix.shape != (n, dim) or (iy is not None and iy.shape != (n, dim)):
+            raise ValueError("init must be X [%d x %d] or (X, Y) of that shape" % (n, dim))
+    X = np.empty((max(n, 0), max(dim, 0)), np.float64); Y = np.empty_like(X); touched = np.empty(max(n, 0), np.uint8); inf = LineInfo()
+    check(lib.dge_line_coo(int(device), p(s), p(d), p(v), len(v), n, C.byref(cfg), p(ix), p(iy), p(X), p(Y), p(touched), C.byref(inf)))
+    return X, Y, touched.astype(bool), {fl[0]: getattr(inf, fl[0]) for fl in LineInfo._fields_}
+
+
+def line_features(X, touched, dtype=np.float32):
+    """A region's LINE feature as the reference forms it: the vertex row, and a row of zeros for a region the edge file never names — what
+    getLINEembeddingFeatures inserts for missing regions (P/flowFeatureGeneration_tract.py:54-73)."""
+    X = np.asarray(X); touched = np.asarray(touched)
+    if X.ndim != 2 or touched.shape != (X.shape[0],):
+        raise ValueError("line_features needs X [n x dim] and touched [n], not %s and %s" % (list(X.shape), list(touched.shape)))
+    out = X.astype(dtype)
+    out[touched == 0] = 0
+    return out

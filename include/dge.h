@@ -947,6 +947,81 @@ int  dge_nmf_flows(const dge_flows* f, int32_t T, int32_t mode, int32_t slot, co
                    dge_nmf_info* info);
 
 /* ------------------------------------------------------------------------------------------------
+ * LINE on a weighted directed graph (new; additions only, DGE_VERSION unchanged): the "LINE" column of the reference's figures
+ * (P/embeddingEvaluation_tract.py:318-342,364; P/flowFeatureGeneration_tract.py:54-73,100; regression-eval.sh:14-27; J/Tracts.java:335).  The reference shells
+ * out to a third-party LINE/linux/train-CA.sh that is in neither tree; that tool draws from rand() and races its threads, so two of its runs disagree.  Here LINE
+ * is a RULE (csrc/line.hip; the per-element pieces: csrc/line_rule.h): X and Y are a pure function of the entries, n, the configuration and the seed (or the
+ * initial tables).  Nothing depends on timing, launch geometry or the order of the input entries.  LINE's source is not at hand where this was written: where
+ * the text says "LINE's", it is LINE AS RECALLED and not verified against it.  Everything real is binary64; every operation rounds once, in the order written;
+ * fma(a, b, c) is a * b + c with ONE rounding and appears only where written.  dge_mix64 is the splitmix64 of csrc/dge_algos.h; index arithmetic is unsigned
+ * 64-bit and wraps.  tests/line_ref.py is this text in Python.
+ *   - INPUT.  A directed weighted graph on n vertices as n_entries entries (src, dst, w).  An entry outside [0, n): DGE_ERR_ARG naming the least such input
+ *     index.  A w that is not finite, negative or not an integer value: DGE_ERR_ARG naming the least such input index.  w >= 2^31: DGE_ERR_ARG.  w == 0 is
+ *     dropped and counted in info.zeros.  A second kept entry with the (src, dst) of another: DGE_ERR_ARG naming the least input index that is not the first of
+ *     its pair.  The KEPT entries are sorted by (src, dst) ascending; "edge e" is the e-th of them.  Self loops are kept.  Limits: 1 <= n <= 2^22,
+ *     1 <= n_entries <= 2^31 - 1 with at least one kept, total weight W < 2^40, 1 <= dim <= 256, 0 <= negative (K) <= 32, order 1 or 2, 1 <= batch <= 65536,
+ *     1 <= samples <= 2^40, 0 < rho0 <= 1.  Null arguments and limit violations: DGE_ERR_ARG before a device is looked for.  On any error the outputs are
+ *     untouched.
+ *   - STATE.  Two int64 tables PX[n][dim] (vertex) and PY[n][dim] (context).  The value of a cell is (double)P * 2^-32, exact while |P| < 2^40.
+ *   - INIT.  seed2 = dge_mix64(seed ^ 0x4C494E45);  u(t) = (dge_mix64(seed2 + t) >> 11) * 2^-53;  PX[v][j] = rint(((u(v*dim + j) - 0.5) / dim) * 2^32) — LINE's
+ *     (rand()/RAND_MAX - 0.5)/dim;  PY = 0.  Caller-supplied host doubles replace this: init_X alone, or init_X and init_Y; every value finite with |x| < 256;
+ *     they are quantised the same way, rint(x * 2^32).  rint rounds to nearest, ties to even.
+ *   - EDGE TABLE.  C[e] = the inclusive int64 prefix sum of the weights in edge order, W = C[last].  For a draw r the edge is the least e with C[e] > r mod W.
+ *   - NEGATIVE TABLE.  d[v] = the int64 sum of the weights of the edges with src == v (LINE's degree: sources only);  p[v] = sqrt((double)d[v] *
+ *     sqrt((double)d[v])) (d^0.75 as two correctly rounded roots and one product);  nw[v] = (int64)(p[v] * 1024.0), truncated;  NC[v] = the inclusive prefix sum
+ *     of nw, N = NC[n-1].  For a draw r the negative is the least v with NC[v] > r mod N.  A vertex without an out-edge is never a negative; a negative that
+ *     equals the sample's source or target is trained like any other, as in LINE.
+ *   - SIGMOID TABLE.  1000 doubles built on the host with E = sw_exp_neg of csrc/spatial_weight.h:  x_k = (k * 12.0) / 1000.0 - 6.0;  x_k >= 0: T[k] = 1.0 /
+ *     (1.0 + E(-x_k)), else T[k] = E(x_k) / (1.0 + E(x_k)).  sig(f) = 1.0 if f > 6.0; 0.0 if f < -6.0; else T[min(999, (int)(((f + 6.0) * 1000.0) / 12.0))].
+ *   - DOT.  dot(a, b) over dim values is the SEGMENT SUM of the NMF rule above: 16 partials from +0.0, product j into partial j mod 16 by fma in ascending j,
+ *     folded 8, 4, 2, 1.
+ *   - SAMPLES.  Sample s = 0 .. samples-1: the edge by dge_mix64(seed + 64*s), giving (u, v); negative d = 1 .. K by dge_mix64(seed + 64*s + d).  Target
+ *     t_0 = v has label 1; the targets t_d, d >= 1, are the negatives, label 0.
+ *   - BATCHES.  Batch b holds the samples [b*batch, min((b+1)*batch, samples)).  rho_b = rho0 * (1.0 - (double)(b*batch) / (double)(samples + 1)); below
+ *     rho0 * 0.0001 it is rho0 * 0.0001.  All reads of a batch see the tables as they stood at its start (a synchronous mini-batch).  For every sample and every
+ *     d:  A = the value row PX[u];  Bt = the value row PX[t_d] (order 1) or PY[t_d] (order 2);  g = (label - sig(dot(A, Bt))) * rho_b;  for every j the
+ *     target's delta cell takes rint((g * A[j]) * 2^32) and u's delta cell in PX takes rint((g * Bt[j]) * 2^32).  The target's deltas go to PX for order 1, to
+ *     PY for order 2.  All adds are int64 adds; at the end of the batch P += delta for both tables.
+ *   - BOUND.  The greatest |value| of the state must stay below 256: then a term is below 2^40, a cell takes fewer than 2 * 65536 * 33 terms a batch, and nothing
+ *     overflows.  If the tables after some batch hold a cell with |P| >= 2^40 the call fails with DGE_ERR_ARG naming the least such batch; the outputs are
+ *     untouched.  (The apply pass folds the batch number into a device word by an integer minimum; the host reads it once, at the end.)
+ *   - OUTPUTS.  X: host double[n x dim].  Y: host double[n x dim], may be NULL; order 1 leaves it all zero.  touched: host uint8[n], may be NULL: 1 where the
+ *     vertex is an endpoint of a kept edge.  info.max_abs is the greatest |value| of both tables at the end.
+ *   - NOT LINE: its own random numbers; mini-batches instead of racing threads; rho stepped per batch, not per 10 000 samples; fixed-point tables; inverse-CDF
+ *     tables instead of alias tables and a 1e8-slot table.
+ *   - dge_line_flows takes its edges and the re-indexing exactly as dge_nmf_flows takes them: the edges dge_flows_slot_edges(f, T, mode, ..) gives for `slot`,
+ *     restricted to the regions with a non-zero select byte ([R], NULL: all) and re-indexed in ascending region index; n = the number of selected regions,
+ *     region_index[n] (may be NULL) lists them.  The graph is built on the device from the resident table.  dge_line_flows(f, 1, mode, 0, ..) trains on
+ *     taxi-all.od.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_line_cfg {
+    int32_t  dim;
+    int32_t  order;        /* 1 or 2                                                                       */
+    int32_t  negative;     /* K                                                                            */
+    int32_t  batch;
+    int64_t  samples;
+    double   rho0;
+    uint64_t seed;
+} dge_line_cfg;            /* 40 bytes */
+typedef struct dge_line_info {
+    int64_t vertices;          /* n                                                                        */
+    int64_t entries;           /* kept                                                                     */
+    int64_t zeros;             /* dropped                                                                  */
+    int64_t batches;
+    int64_t samples;
+    int64_t total_weight;      /* W                                                                        */
+    int64_t neg_total;         /* N                                                                        */
+    double  max_abs;
+    double  kernel_ms;         /* HIP-event time from the first kernel of the call to its last             */
+} dge_line_info;               /* 72 bytes */
+/* src, dst, w: host arrays of n_entries; X: host double[n x dim]; init_X, init_Y (only with init_X), Y, touched and info may be NULL */
+int  dge_line_coo(int device, const int32_t* src, const int32_t* dst, const double* w, int64_t n_entries, int64_t n, const dge_line_cfg* cfg, const double* init_X,
+                  const double* init_Y, double* X, double* Y, uint8_t* touched, dge_line_info* info);
+/* X, Y: host double[n x dim], touched: host uint8[n] and region_index: host int64[n], n = the selected regions (at most the table's regions) */
+int  dge_line_flows(const dge_flows* f, int32_t T, int32_t mode, int32_t slot, const uint8_t* select, const dge_line_cfg* cfg, double* X, double* Y, uint8_t* touched,
+                    int64_t* region_index, dge_line_info* info);
+
+/* ------------------------------------------------------------------------------------------------
  * Ablation / test knobs of the trainer (process-wide relaxed atomics; nothing in a normal run sets them).  value < 0 puts
  * a knob back to the library's own rule.
  * ---------------------------------------------------------------------------------------------- */
