@@ -21,6 +21,7 @@
 // floating-point atomics: the same call returns the same bits.
 #include <math.h>
 
+#include "dge_device.h"
 #include "sgns_kernels.h"      // neg_table_row; dge_algos.h (dge_mix64), dge_internal.h
 #include "sgns_model.h"
 
@@ -255,19 +256,12 @@ static void ev_empty(dge_eval_result* out) {
     out->auc = out->loss = nan(""); out->kernel_ms = 0.0;
 }
 
-struct EvalTimer {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EvalTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-// the partials of `blocks` workgroups -> one record on the host; *ms = event time from t.a to behind the final kernel
-static int ev_finish(dge_model* m, EvalTimer& t, const EvalPartial* d_part, int blocks, EvalPartial* d_total, EvalPartial* total, double* ms) {
+// the partials of `blocks` workgroups -> one record on the host; *ms = event time from t's start to behind the final kernel
+static int ev_finish(dge_model* m, dge_stopwatch& t, const EvalPartial* d_part, int blocks, EvalPartial* d_total, EvalPartial* total, double* ms) {
     hipLaunchKernelGGL(k_eval_final, dim3(1), dim3(256), 0, m->stream, d_part, blocks, d_total);
     DGE_HIP(hipGetLastError());
-    DGE_HIP(hipEventRecord(t.b, m->stream));
-    DGE_HIP(hipStreamSynchronize(m->stream));
     float f = 0.f;
-    DGE_HIP(hipEventElapsedTime(&f, t.a, t.b));
+    if (int rc = t.stop(&f)) return rc;
     *ms = (double)f;
     DGE_HIP(hipMemcpy(total, d_total, sizeof(EvalPartial), hipMemcpyDeviceToHost));
     return DGE_OK;
@@ -311,9 +305,8 @@ extern "C" int dge_model_eval_links(dge_model* m, const dge_walks* w, int64_t ro
     ev_geometry(m, n_steps, 64, &blocks, &per_block);
     dge_tmp<EvalPartial> d_part;
     if ((rc = d_part.alloc((size_t)blocks + 1))) return rc;
-    EvalTimer t;
-    DGE_HIP(hipEventCreate(&t.a)); DGE_HIP(hipEventCreate(&t.b));
-    DGE_HIP(hipEventRecord(t.a, m->stream));
+    dge_stopwatch t;
+    if ((rc = t.start(m->stream))) return rc;
 #define EV_CALL(N) hipLaunchKernelGGL((k_eval_links<N>), dim3(blocks), dim3(256), 0, m->stream, m->d_syn0, m->d_syn1neg, m->d_remap, m->NV, m->stride, w->d, row0, n_steps, w->L, regions_per_slice, seed, per_block, d_part.p)
     EV_SWITCH_DCH(m->stride / 64, EV_CALL)
 #undef EV_CALL
@@ -342,9 +335,8 @@ extern "C" int dge_model_eval_sgns(dge_model* m, const dge_walks* w, int64_t row
     ev_geometry(m, n_rows, groups, &blocks, &per_block);
     dge_tmp<EvalPartial> d_part;
     if ((rc = d_part.alloc((size_t)blocks + 1))) return rc;
-    EvalTimer t;
-    DGE_HIP(hipEventCreate(&t.a)); DGE_HIP(hipEventCreate(&t.b));
-    DGE_HIP(hipEventRecord(t.a, m->stream));
+    dge_stopwatch t;
+    if ((rc = t.start(m->stream))) return rc;
 #define EV_CALL(N) hipLaunchKernelGGL((k_eval_sgns<N>), dim3(blocks), dim3(16 * groups), lds, m->stream, m->d_syn0, m->d_syn1neg, m->d_remap, m->NV, m->stride, m->d_ctab, (uint64_t)m->T, w->d, row0, n_rows, w->L, m->cfg.window, m->cfg.negative, seed, per_block, d_part.p)
     EV_SWITCH_DCH(m->stride / 64, EV_CALL)
 #undef EV_CALL

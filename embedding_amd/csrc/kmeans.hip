@@ -14,7 +14,7 @@
 
 #include <vector>
 
-#include "dge_internal.h"
+#include "dge_device.h"
 #include "kmeans_rule.h"
 #include "cluster_match.h"
 
@@ -270,11 +270,6 @@ static int assign_pass(const float* x, const int64_t* sel, int64_t n, int dim, i
     return launch_assign<16>(x, sel, n, dim, k, s, cen, lab, d, S, count, changed);
 }
 
-struct km_events {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~km_events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
 static int kmeans_cfg_check(const char* who, const dge_kmeans_cfg* cfg) {
     if (cfg->k < 1 || cfg->k > KM_MAX_K) DGE_FAIL(DGE_ERR_ARG, "%s: k = %d is outside 1 .. %d", who, cfg->k, KM_MAX_K);
     if (cfg->n_init < 1) DGE_FAIL(DGE_ERR_ARG, "%s: n_init = %d must be at least 1", who, cfg->n_init);
@@ -322,9 +317,8 @@ static int kmeans_run(const char* who, const dge_vectors* v, const uint8_t* sele
         (rc = d_dmin.alloc((size_t)n)) || (rc = d_bs.alloc((size_t)n_blocks)) || (rc = d_dist[0].alloc((size_t)n)) || (rc = d_dist[1].alloc((size_t)n)) ||
         (rc = d_lab[0].alloc((size_t)n)) || (rc = d_lab[1].alloc((size_t)n)) || (rc = d_cen[0].alloc(kd)) || (rc = d_cen[1].alloc(kd))) return rc;
 
-    km_events ev;
-    DGE_HIP(hipEventCreate(&ev.e0)); DGE_HIP(hipEventCreate(&ev.e1));
-    DGE_HIP(hipEventRecord(ev.e0, 0));
+    dge_stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
 
     // max |x| and the finite check
     DGE_HIP(hipMemsetAsync(d_max.p, 0, sizeof(unsigned), 0));
@@ -389,10 +383,8 @@ static int kmeans_run(const char* who, const dge_vectors* v, const uint8_t* sele
             for (int c = 0; c < k; c++) if (cnt[(size_t)c] == 0) best_empty++;
         }
     }
-    DGE_HIP(hipEventRecord(ev.e1, 0));
-    DGE_HIP(hipEventSynchronize(ev.e1));
     float ms = 0.f;
-    DGE_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if ((rc = watch.stop(&ms))) return rc;
 
     // outputs last: an error above leaves them as they were
     std::vector<int32_t> lab((size_t)n);

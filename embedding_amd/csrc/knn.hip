@@ -15,7 +15,7 @@
 
 #include <vector>
 
-#include "dge_internal.h"
+#include "dge_device.h"
 
 #define KNN_MAX_K 64
 #define KNN_MAX_D 256
@@ -175,25 +175,21 @@ static int knn_device(const float* d_x, const uint8_t* d_present, int n, int D, 
                       double* ms_kernel) {
     const int dh = (D + 1) / 2 <= 16 ? 16 : ((D + 1) / 2 <= 32 ? 32 : ((D + 1) / 2 <= 64 ? 64 : 128));
     const int Dp = 2 * dh;
-    dge_tmp<double> d_norm;                       // freed at return, after the hipDeviceSynchronize below (an error return: hipFree itself waits for the device)
+    dge_tmp<double> d_norm;                       // freed at return, after the stopwatch's wait below (an error return: hipFree itself waits for the device)
     int rc;
     if ((rc = d_norm.alloc((size_t)n))) return rc;
     hipLaunchKernelGGL(k_row_norms, dim3((n + 255) / 256), dim3(256), 0, 0, d_x, d_present, n, D, d_norm.p);
     hipLaunchKernelGGL(k_normalise, dim3((unsigned)(((size_t)n * Dp + 255) / 256)), dim3(256), 0, 0, d_x, d_norm.p, n, D, Dp, d_xn, d_inv);
-    hipEvent_t e0, e1;
-    DGE_HIP(hipEventCreate(&e0)); DGE_HIP(hipEventCreate(&e1));
-    DGE_HIP(hipEventRecord(e0, 0));
+    dge_stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
     if (dh == 16) rc = launch_knn<16>(d_xn, d_inv, n, k, d_oi, d_od, 0);
     else if (dh == 32) rc = launch_knn<32>(d_xn, d_inv, n, k, d_oi, d_od, 0);
     else if (dh == 64) rc = launch_knn<64>(d_xn, d_inv, n, k, d_oi, d_od, 0);
     else rc = launch_knn<128>(d_xn, d_inv, n, k, d_oi, d_od, 0);
-    DGE_HIP(hipEventRecord(e1, 0));
-    if (rc) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); DGE_FAIL(DGE_ERR_ARG, "dge_knn_cosine: k = %d with dim = %d needs more than the 160 KB of LDS", k, D); }
+    if (rc) DGE_FAIL(DGE_ERR_ARG, "dge_knn_cosine: k = %d with dim = %d needs more than the 160 KB of LDS", k, D);
     DGE_HIP(hipGetLastError());
-    DGE_HIP(hipDeviceSynchronize());
     float ms = 0.f;
-    DGE_HIP(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if ((rc = watch.stop(&ms))) return rc;          // everything above went to the null stream: this is the call's one wait
     if (ms_kernel) *ms_kernel = ms;
     return DGE_OK;
 }

@@ -2,10 +2,10 @@
 // the fully specified rule of include/dge.h.  The per-element arithmetic lives in line_rule.h; this file is what runs it at full concurrency without changing a bit.
 //
 // Both tables are int64 fixed point (2^-32 a unit) and every gradient term is quantised before it is added, so a mini-batch is a set of 64-bit integer atomic
-// adds into delta tables: their sum does not depend on order, launch geometry or timing.  Per call: the entries are checked and sorted by (src, dst) (the shape
-// of nmf.hip), the edge and negative tables are two rocPRIM prefix sums.  Per chunk of batches one draw kernel, a lane per draw, does the binary searches and
+// adds into delta tables: their sum does not depend on order, launch geometry or timing.  Per call: the entries are checked and sorted by (src, dst) (the intake
+// shared with nmf.hip, coo_entries.h), the edge and negative tables are two rocPRIM prefix sums.  Per chunk of batches one draw kernel, a lane per draw, does the binary searches and
 // leaves int32 [samples x (K + 2)]: u, v, the K negatives.  Per batch: k_line_grad — one DPP row of 16 lanes per sample, lane l holds columns l, l + 16, ... of
-// u's row in registers across the K + 1 targets; partial l of the rule's dot is lane l's fma chain, the fold is four row rotations, which leave the sum in every
+// u's row in registers across the K + 1 targets; partial l of the rule's dot is lane l's fma chain, the fold is four row rotations (dge_row16_ror), which leave the sum in every
 // lane; u's K + 1 terms are summed as integers in registers and added once per cell — and k_line_apply over the batch's (K + 2) * count row ids, which claims a
 // delta cell with an exchange-with-zero (a duplicate finds 0 and skips), adds it to the table and folds the batch number into one word by an integer minimum
 // when a cell leaves the bound.  The host reads that word once, at the end.  No floating-point atomic anywhere.
@@ -15,42 +15,21 @@
 
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "dge_internal.h"
+#include "coo_entries.h"
 #include "line_rule.h"
 
 #define LINE_NONE (~0ULL)
 #define LINE_CHUNK (1LL << 20)          // samples drawn by one launch of the draw kernel (rounded to whole batches)
-enum { LC_RANGE = 0, LC_VALUE, LC_BIG, LC_DUP, LC_ZEROS, LC_N };
 
 typedef unsigned long long line_u64;
 
 // ------------------------------------------------------------------------------------------ the entries, once per call
-// every input entry: its checks (the least input index of each kind of fault), the zeros, and its sort key src * n + dst — a dropped entry sorts behind all kept ones
-__global__ void __launch_bounds__(256) k_line_scan(const int32_t* __restrict__ src, const int32_t* __restrict__ dst, const double* __restrict__ w, int64_t ne, int64_t n,
-                                                   uint64_t* __restrict__ key, int64_t* __restrict__ idx, line_u64* __restrict__ c) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= ne) return;
-    const double v = w[e];
-    const int64_t i = src[e], j = dst[e];
-    uint64_t k = LINE_NONE;
-    if (i < 0 || i >= n || j < 0 || j >= n) atomicMin(c + LC_RANGE, (line_u64)e);
-    else if (!isfinite(v) || v < 0.0 || v != rint(v)) atomicMin(c + LC_VALUE, (line_u64)e);
-    else if (v >= (double)LINE_MAX_WEIGHT) atomicMin(c + LC_BIG, (line_u64)e);
-    else if (v == 0.0) atomicAdd(c + LC_ZEROS, 1ULL);
-    else k = (uint64_t)i * (uint64_t)n + (uint64_t)j;
-    key[e] = k;
-    idx[e] = e;
-}
-
-// the sort is stable: among equal keys the input indices ascend, so every entry that equals the one in front of it is a second occurrence
-__global__ void __launch_bounds__(256) k_line_dups(const uint64_t* __restrict__ key, const int64_t* __restrict__ idx, int64_t kept, line_u64* __restrict__ c) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p < 1 || p >= kept) return;
-    if (key[p] == key[p - 1]) atomicMin(c + LC_DUP, (line_u64)idx[p]);
-}
+// a weight for the shared intake (coo_entries.h): kind 1 is not a finite integer >= 0, kind 2 is >= 2^31
+struct LineWeight {
+    static __device__ int kind(double v) {
+        return !isfinite(v) || v < 0.0 || v != rint(v) ? COO_KIND1 : v >= (double)LINE_MAX_WEIGHT ? COO_KIND2 : v == 0.0 ? COO_ZEROS : COO_KEEP;
+    }
+};
 
 // edge e: its ends, its weight as an integer, and the mark of both ends
 __global__ void __launch_bounds__(256) k_line_edges(const uint64_t* __restrict__ key, const int64_t* __restrict__ idx, const double* __restrict__ w, int64_t kept, int64_t n,
@@ -66,13 +45,7 @@ __global__ void __launch_bounds__(256) k_line_edges(const uint64_t* __restrict__
 __global__ void __launch_bounds__(256) k_line_neg_weights(const uint64_t* __restrict__ key, const int64_t* __restrict__ C, int64_t kept, int64_t n, int64_t* __restrict__ nw) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= n) return;
-    int64_t at[2];
-    for (int x = 0; x < 2; x++) {
-        const uint64_t want = (uint64_t)(v + x) * (uint64_t)n;
-        int64_t lo = 0, hi = kept;
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (key[mid] < want) lo = mid + 1; else hi = mid; }
-        at[x] = lo;
-    }
+    const int64_t at[2] = {coo_lower_bound(key, kept, (uint64_t)v * (uint64_t)n), coo_lower_bound(key, kept, (uint64_t)(v + 1) * (uint64_t)n)};
     const int64_t d = (at[1] ? C[at[1] - 1] : 0) - (at[0] ? C[at[0] - 1] : 0);
     nw[v] = line_neg_weight(d);
 }
@@ -101,21 +74,13 @@ __global__ void __launch_bounds__(256) k_line_draw(const int64_t* __restrict__ C
 }
 
 // ------------------------------------------------------------------------------------------ a batch
-// lane l of a DPP row takes the value of lane (l + S) mod 16 of its row
-template <int S>
-__device__ __forceinline__ double line_row_ror(double x) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x120 + S, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x120 + S, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-
 // the fold of the 16 partials, one per lane: p[l] + p[l + s] for s = 8, 4, 2, 1.  A rotation instead of a shift gives every lane, not only lane 0, the rule's
 // sum: addition commutes, so after the step s the row holds the rule's values with period s, and lane l reads what the rule's lane l mod s reads.
 __device__ __forceinline__ double line_fold(double p) {
-    p = p + line_row_ror<8>(p);
-    p = p + line_row_ror<4>(p);
-    p = p + line_row_ror<2>(p);
-    p = p + line_row_ror<1>(p);
+    p = p + dge_row16_ror<8>(p);
+    p = p + dge_row16_ror<4>(p);
+    p = p + dge_row16_ror<2>(p);
+    p = p + dge_row16_ror<1>(p);
     return p;
 }
 
@@ -188,38 +153,9 @@ __global__ void __launch_bounds__(256) k_line_apply(const int32_t* __restrict__ 
 // ------------------------------------------------------------------------------------------ host side
 namespace {
 
-struct line_events {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~line_events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
-inline unsigned line_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-int line_sort(const uint64_t* k_in, uint64_t* k_out, const int64_t* v_in, int64_t* v_out, int64_t n) {
-    size_t bytes = 0;
-    dge_tmp<uint8_t> tmp;
-    int rc;
-    DGE_HIP(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, 64, 0));
-    if ((rc = tmp.alloc(bytes))) return rc;
-    DGE_HIP(rocprim::radix_sort_pairs((void*)tmp.p, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, 64, 0));
-    DGE_HIP(hipStreamSynchronize(0));                       // the scratch goes when this returns
-    return DGE_OK;
-}
-
-int line_prefix(const int64_t* in, int64_t* out, int64_t n) {
-    size_t bytes = 0;
-    dge_tmp<uint8_t> tmp;
-    int rc;
-    DGE_HIP(rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)n, rocprim::plus<int64_t>(), 0));
-    if ((rc = tmp.alloc(bytes))) return rc;
-    DGE_HIP(rocprim::inclusive_scan((void*)tmp.p, bytes, in, out, (size_t)n, rocprim::plus<int64_t>(), 0));
-    DGE_HIP(hipStreamSynchronize(0));
-    return DGE_OK;
-}
-
 void grad(int64_t count, const int32_t* draws, const dge_line_cfg* cfg, const int64_t* PX, const int64_t* PY, int64_t* DX, int64_t* DY, const double* T, double rho,
           const line_u64* flag) {
-    const dim3 grid(line_grid(count * NMF_LANES)), block(256);
+    const dim3 grid(dge_grid(count * NMF_LANES)), block(256);
     const int K = cfg->negative, dim = cfg->dim, order = cfg->order;
     if (dim <= 16) hipLaunchKernelGGL((k_line_grad<1>), grid, block, 0, 0, draws, count, K, dim, order, PX, PY, DX, DY, T, rho, flag);
     else if (dim <= 32) hipLaunchKernelGGL((k_line_grad<2>), grid, block, 0, 0, draws, count, K, dim, order, PX, PY, DX, DY, T, rho, flag);
@@ -245,31 +181,21 @@ int line_run(const char* who, const int32_t* d_src, const int32_t* d_dst, const 
     int rc;
     const int dim = cfg->dim, K = cfg->negative;
     const size_t cells = (size_t)n * (size_t)dim;
-    line_events ev;
-    DGE_HIP(hipEventCreate(&ev.e0)); DGE_HIP(hipEventCreate(&ev.e1));
-    DGE_HIP(hipEventRecord(ev.e0, 0));
+    dge_stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
 
-    // ---- the entries: checks, the order by (src, dst)
-    dge_tmp<line_u64> d_c;
-    dge_tmp<uint64_t> key, skey;
-    dge_tmp<int64_t> idx, sidx;
-    if ((rc = d_c.alloc(LC_N + 1)) || (rc = key.alloc((size_t)ne)) || (rc = skey.alloc((size_t)ne)) || (rc = idx.alloc((size_t)ne)) || (rc = sidx.alloc((size_t)ne))) return rc;
-    line_u64* d_flag = d_c.p + LC_N;
-    line_u64 c[LC_N + 1] = {LINE_NONE, LINE_NONE, LINE_NONE, LINE_NONE, 0, LINE_NONE};
-    DGE_HIP(hipMemcpy(d_c.p, c, sizeof c, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_line_scan, dim3(line_grid(ne)), dim3(256), 0, 0, d_src, d_dst, d_w, ne, n, key.p, idx.p, d_c.p);
-    DGE_HIP(hipGetLastError());
-    DGE_HIP(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
-    if (c[LC_RANGE] != LINE_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld names a vertex outside 0 .. %lld", who, (long long)c[LC_RANGE], (long long)n - 1);
-    if (c[LC_VALUE] != LINE_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld holds a weight that is not a finite integer >= 0", who, (long long)c[LC_VALUE]);
-    if (c[LC_BIG] != LINE_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld holds a weight >= 2^31", who, (long long)c[LC_BIG]);
-    const int64_t zeros = (int64_t)c[LC_ZEROS], kept = ne - zeros;
-    if (kept < 1) DGE_FAIL(DGE_ERR_ARG, "%s: no entry is left: all %lld weights are zero", who, (long long)ne);
-    if ((rc = line_sort(key.p, skey.p, idx.p, sidx.p, ne))) return rc;
-    hipLaunchKernelGGL(k_line_dups, dim3(line_grid(kept)), dim3(256), 0, 0, skey.p, sidx.p, kept, d_c.p);
-    DGE_HIP(hipGetLastError());
-    DGE_HIP(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
-    if (c[LC_DUP] != LINE_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld repeats the source and destination of an earlier entry", who, (long long)c[LC_DUP]);
+    // ---- the entries: checks, the order by (src, dst) (the shared intake)
+    coo_entries E;
+    if ((rc = coo_intake<LineWeight, false>(d_src, d_dst, d_w, ne, n, n, INT64_MAX, E))) return rc;
+    switch (E.fault) {
+    case COO_RANGE: DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld names a vertex outside 0 .. %lld", who, (long long)E.at, (long long)n - 1);
+    case COO_KIND1: DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld holds a weight that is not a finite integer >= 0", who, (long long)E.at);
+    case COO_KIND2: DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld holds a weight >= 2^31", who, (long long)E.at);
+    case COO_ZEROS: DGE_FAIL(DGE_ERR_ARG, "%s: no entry is left: all %lld weights are zero", who, (long long)ne);
+    case COO_DUP: DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld repeats the source and destination of an earlier entry", who, (long long)E.at);
+    }
+    const int64_t zeros = E.zeros, kept = E.kept;
+    line_u64* d_flag = E.d_c.p + COO_SPARE;                 // LINE_NONE so far: the least batch that left the bound
 
     // ---- the edge table and the negative table
     dge_tmp<int32_t> es, ed, draws;
@@ -278,15 +204,15 @@ int line_run(const char* who, const int32_t* d_src, const int32_t* d_dst, const 
     if ((rc = es.alloc((size_t)kept)) || (rc = ed.alloc((size_t)kept)) || (rc = ew.alloc((size_t)kept)) || (rc = C.alloc((size_t)kept)) || (rc = nw.alloc((size_t)n)) ||
         (rc = NC.alloc((size_t)n)) || (rc = d_touched.alloc((size_t)n))) return rc;
     DGE_HIP(hipMemset(d_touched.p, 0, (size_t)n));
-    hipLaunchKernelGGL(k_line_edges, dim3(line_grid(kept)), dim3(256), 0, 0, skey.p, sidx.p, d_w, kept, n, es.p, ed.p, ew.p, d_touched.p);
+    hipLaunchKernelGGL(k_line_edges, dim3(dge_grid(kept)), dim3(256), 0, 0, E.skey.p, E.sidx.p, d_w, kept, n, es.p, ed.p, ew.p, d_touched.p);
     DGE_HIP(hipGetLastError());
-    if ((rc = line_prefix(ew.p, C.p, kept))) return rc;
+    if ((rc = dge_inclusive_sum(dge_scratch(), (const int64_t*)ew.p, C.p, kept, 0, true))) return rc;
     int64_t W = 0, N = 0;
     DGE_HIP(hipMemcpy(&W, C.p + (kept - 1), sizeof W, hipMemcpyDeviceToHost));
     if (W >= LINE_MAX_TOTAL) DGE_FAIL(DGE_ERR_ARG, "%s: the total weight %lld is not below 2^40", who, (long long)W);
-    hipLaunchKernelGGL(k_line_neg_weights, dim3(line_grid(n)), dim3(256), 0, 0, skey.p, C.p, kept, n, nw.p);
+    hipLaunchKernelGGL(k_line_neg_weights, dim3(dge_grid(n)), dim3(256), 0, 0, E.skey.p, C.p, kept, n, nw.p);
     DGE_HIP(hipGetLastError());
-    if ((rc = line_prefix(nw.p, NC.p, n))) return rc;
+    if ((rc = dge_inclusive_sum(dge_scratch(), (const int64_t*)nw.p, NC.p, n, 0, true))) return rc;
     DGE_HIP(hipMemcpy(&N, NC.p + (n - 1), sizeof N, hipMemcpyDeviceToHost));
 
     // ---- the tables, their deltas, the sigmoid table
@@ -300,7 +226,7 @@ int line_run(const char* who, const int32_t* d_src, const int32_t* d_dst, const 
         for (size_t t = 0; t < cells; t++) host[t] = line_quant(init_X[t]);
         DGE_HIP(hipMemcpy(PX.p, host.data(), cells * sizeof(int64_t), hipMemcpyHostToDevice));
     } else {
-        hipLaunchKernelGGL(k_line_init, dim3(line_grid((int64_t)cells)), dim3(256), 0, 0, PX.p, (int64_t)cells, dim, line_seed2(cfg->seed));
+        hipLaunchKernelGGL(k_line_init, dim3(dge_grid((int64_t)cells)), dim3(256), 0, 0, PX.p, (int64_t)cells, dim, line_seed2(cfg->seed));
         DGE_HIP(hipGetLastError());
     }
     if (init_Y) {
@@ -320,20 +246,18 @@ int line_run(const char* who, const int32_t* d_src, const int32_t* d_dst, const 
     if ((rc = draws.alloc((size_t)(chunk < samples ? chunk : samples) * (size_t)(K + 2)))) return rc;
     for (int64_t first = 0; first < samples; first += chunk) {
         const int64_t count = samples - first < chunk ? samples - first : chunk;
-        hipLaunchKernelGGL(k_line_draw, dim3(line_grid(count * (K + 1))), dim3(256), 0, 0, C.p, kept, W, es.p, ed.p, NC.p, n, N, cfg->seed, first, count, K, draws.p);
+        hipLaunchKernelGGL(k_line_draw, dim3(dge_grid(count * (K + 1))), dim3(256), 0, 0, C.p, kept, W, es.p, ed.p, NC.p, n, N, cfg->seed, first, count, K, draws.p);
         for (int64_t o = 0; o < count; o += batch) {
             const int64_t cnt = count - o < batch ? count - o : batch;
             const int32_t* dr = draws.p + (size_t)o * (size_t)(K + 2);
             grad(cnt, dr, cfg, PX.p, PY.p, DX.p, DY.p, T.p, line_rho(cfg->rho0, first + o, samples), d_flag);
-            hipLaunchKernelGGL(k_line_apply, dim3(line_grid(cnt * (K + 2) * dim)), dim3(256), 0, 0, dr, cnt, K, dim, cfg->order, PX.p, PY.p, DX.p, DY.p,
+            hipLaunchKernelGGL(k_line_apply, dim3(dge_grid(cnt * (K + 2) * dim)), dim3(256), 0, 0, dr, cnt, K, dim, cfg->order, PX.p, PY.p, DX.p, DY.p,
                                (line_u64)((first + o) / batch), d_flag);
         }
         DGE_HIP(hipGetLastError());
     }
-    DGE_HIP(hipEventRecord(ev.e1, 0));
-    DGE_HIP(hipEventSynchronize(ev.e1));
     float ms = 0.f;
-    DGE_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if ((rc = watch.stop(&ms))) return rc;
     line_u64 over = LINE_NONE;
     DGE_HIP(hipMemcpy(&over, d_flag, sizeof over, hipMemcpyDeviceToHost));
     if (over != LINE_NONE)
@@ -387,10 +311,7 @@ extern "C" int dge_line_coo(int device, const int32_t* src, const int32_t* dst, 
     if ((rc = dge_require_device(device))) return rc;
     dge_tmp<int32_t> d_src, d_dst;
     dge_tmp<double> d_w;
-    if ((rc = d_src.alloc((size_t)n_entries)) || (rc = d_dst.alloc((size_t)n_entries)) || (rc = d_w.alloc((size_t)n_entries))) return rc;
-    DGE_HIP(hipMemcpy(d_src.p, src, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
-    DGE_HIP(hipMemcpy(d_dst.p, dst, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
-    DGE_HIP(hipMemcpy(d_w.p, w, (size_t)n_entries * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = coo_upload(src, dst, w, n_entries, d_src, d_dst, d_w))) return rc;
     return line_run(who, d_src.p, d_dst.p, d_w.p, n_entries, n, cfg, init_X, init_Y, X, Y, touched, info);
 }
 

@@ -2,10 +2,10 @@
 // (P/matrixFactorization_tract.py:26-45, P/flowFeatureGeneration_tract.py:29-40) without a dense R x R array.  The per-element arithmetic lives in nmf_rule.h;
 // this file is what runs it at full concurrency without changing a bit.
 //
-// Everything here is a memory-bound sparse pass.  The kept entries are sorted once by (row, column); a second sort of (column, row) gives the permutation that
+// Everything here is a memory-bound sparse pass.  The shared intake (coo_entries.h) checks the entries and sorts the kept ones by (row, column); a second sort of (column, row) gives the permutation that
 // lists them by column.  W is held [n x rank] and H transposed, [m x rank], so that the rank values a pass gathers for an entry are one contiguous run; H is
 // turned back on the host at the end.  One pass forms P (and Q = V / P) per entry.  A segment sum — over a row's or a column's entries — is done by 16 lanes,
-// four segments a wave: lane l takes the products l, l + 16, ... of the segment into `rank` accumulators, then four DPP row shifts fold the 16 partials as the rule
+// four segments a wave: lane l takes the products l, l + 16, ... of the segment into `rank` accumulators, then four DPP row shifts (dge_row16_shl) fold the 16 partials as the rule
 // says (8, 4, 2, 1), without LDS.  The blocked sums, the Gram matrices and the update with its floor are small kernels over n or m values.  No atomic on a
 // floating-point value anywhere: the only atomics are integer minima / maxima of the input scan, which are the same in any order.
 #include <hip/hip_runtime.h>
@@ -14,42 +14,14 @@
 
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
-#include "dge_internal.h"
+#include "coo_entries.h"
 #include "nmf_rule.h"
 
-#define NMF_NONE (~0ULL)
-enum { NC_RANGE = 0, NC_NONFINITE, NC_NEGATIVE, NC_DUP, NC_ZEROS, NC_VMAX, NC_N };
-
 // ------------------------------------------------------------------------------------------ the entries, once per call
-// every input entry: its checks (the least input index of each kind of fault), the zeros, the greatest value (the bits of non-negative doubles order as
-// unsigned integers), and its sort key row * m + col — a dropped entry sorts behind all kept ones
-__global__ void __launch_bounds__(256) k_nmf_scan(const int32_t* __restrict__ row, const int32_t* __restrict__ col, const double* __restrict__ val, int64_t ne, int64_t n, int64_t m,
-                                                  uint64_t* __restrict__ key, int64_t* __restrict__ idx, unsigned long long* __restrict__ c) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= ne) return;
-    const double v = val[e];
-    const int64_t i = row[e], j = col[e];
-    uint64_t k = NMF_NONE;
-    if (i < 0 || i >= n || j < 0 || j >= m) atomicMin(c + NC_RANGE, (unsigned long long)e);
-    else if (!isfinite(v)) atomicMin(c + NC_NONFINITE, (unsigned long long)e);
-    else if (v < 0.0) atomicMin(c + NC_NEGATIVE, (unsigned long long)e);
-    else if (v == 0.0) atomicAdd(c + NC_ZEROS, 1ULL);
-    else {
-        k = (uint64_t)i * (uint64_t)m + (uint64_t)j;
-        atomicMax(c + NC_VMAX, (unsigned long long)__double_as_longlong(v));
-    }
-    key[e] = k;
-    idx[e] = e;
-}
-
-// the sort is stable: among equal keys the input indices ascend, so every entry that equals the one in front of it is a second occurrence
-__global__ void __launch_bounds__(256) k_nmf_dups(const uint64_t* __restrict__ key, const int64_t* __restrict__ idx, int64_t kept, unsigned long long* __restrict__ c) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p < 1 || p >= kept) return;
-    if (key[p] == key[p - 1]) atomicMin(c + NC_DUP, (unsigned long long)idx[p]);
-}
+// a value of the matrix for the shared intake (coo_entries.h): kind 1 is not finite, kind 2 is negative
+struct NmfValue {
+    static __device__ int kind(double v) { return !isfinite(v) ? COO_KIND1 : v < 0.0 ? COO_KIND2 : v == 0.0 ? COO_ZEROS : COO_KEEP; }
+};
 
 // the entries by row: row, column and value of each, and its key for the order by column
 __global__ void __launch_bounds__(256) k_nmf_by_row(const uint64_t* __restrict__ key, const int64_t* __restrict__ idx, const double* __restrict__ val, int64_t kept, int64_t n, int64_t m,
@@ -75,10 +47,7 @@ __global__ void __launch_bounds__(256) k_nmf_by_col(const uint64_t* __restrict__
 __global__ void __launch_bounds__(256) k_nmf_ptr(const uint64_t* __restrict__ key, int64_t kept, uint64_t stride, int64_t count, int64_t* __restrict__ ptr) {
     const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (x > count) return;
-    const uint64_t want = (uint64_t)x * stride;
-    int64_t lo = 0, hi = kept;
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (key[mid] < want) lo = mid + 1; else hi = mid; }
-    ptr[x] = lo;
+    ptr[x] = coo_lower_bound(key, kept, (uint64_t)x * stride);
 }
 
 // X[x][r] = nmf_init(seed, base + x * sx + r * sr, vmax)
@@ -104,14 +73,6 @@ __global__ void __launch_bounds__(256) k_nmf_entries(const int32_t* __restrict__
     out[e] = o;
 }
 
-// lane l of a DPP row takes the value of lane l + S (lanes past the row's end give 0, which no lane that counts reads)
-template <int S>
-__device__ __forceinline__ double nmf_row_shl(double x) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), 0x100 + S, 0xF, 0xF, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), 0x100 + S, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
-
 // the segment sums of every row (or column): out[g][r] = SEGMENT SUM over the entries c of segment g of Y[other[c]][r] * b[c], b[c] = val[perm[c]] or val[c].
 // RB: the accumulators a lane holds, the least of 4, 10, 16, 32 that is at least rank.
 template <int RB>
@@ -134,10 +95,10 @@ __global__ void __launch_bounds__(256) k_nmf_segments(const int64_t* __restrict_
 #pragma unroll
     for (int r = 0; r < RB; r++) {
         double p = acc[r];
-        p = p + nmf_row_shl<8>(p);
-        p = p + nmf_row_shl<4>(p);
-        p = p + nmf_row_shl<2>(p);
-        p = p + nmf_row_shl<1>(p);
+        p = p + dge_row16_shl<8>(p);
+        p = p + dge_row16_shl<4>(p);
+        p = p + dge_row16_shl<2>(p);
+        p = p + dge_row16_shl<1>(p);
         acc[r] = p;
     }
     if (l == 0) {
@@ -203,29 +164,8 @@ __global__ void __launch_bounds__(256) k_nmf_update(double* __restrict__ X, int6
 // ------------------------------------------------------------------------------------------ host side
 namespace {
 
-struct nmf_events {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~nmf_events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
-
-inline unsigned nmf_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-int bits_for(uint64_t v) { int b = 1; while (b < 64 && (v >> b)) b++; return b; }
-
-template <typename K, typename Vv>
-int nmf_sort(const K* k_in, K* k_out, const Vv* v_in, Vv* v_out, int64_t n, int end_bit) {
-    size_t bytes = 0;
-    dge_tmp<uint8_t> tmp;
-    int rc;
-    DGE_HIP(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, end_bit, 0));
-    if ((rc = tmp.alloc(bytes))) return rc;
-    DGE_HIP(rocprim::radix_sort_pairs((void*)tmp.p, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, end_bit, 0));
-    DGE_HIP(hipStreamSynchronize(0));                       // the scratch goes when this returns
-    return DGE_OK;
-}
-
 int segments(const int64_t* ptr, const int32_t* other, const double* val, const int32_t* perm, const double* Y, int rank, int64_t cnt, double* out) {
-    const dim3 grid(nmf_grid(cnt * NMF_LANES)), block(256);
+    const dim3 grid(dge_grid(cnt * NMF_LANES)), block(256);
     if (rank <= 4) hipLaunchKernelGGL((k_nmf_segments<4>), grid, block, 0, 0, ptr, other, val, perm, Y, rank, cnt, out);
     else if (rank <= 10) hipLaunchKernelGGL((k_nmf_segments<10>), grid, block, 0, 0, ptr, other, val, perm, Y, rank, cnt, out);
     else if (rank <= 16) hipLaunchKernelGGL((k_nmf_segments<16>), grid, block, 0, 0, ptr, other, val, perm, Y, rank, cnt, out);
@@ -235,7 +175,7 @@ int segments(const int64_t* ptr, const int32_t* other, const double* val, const 
 }
 
 int update(double* X, int64_t cnt, int rank, const double* num, const double* d, const double* G, int g_rows) {
-    const dim3 grid(nmf_grid(cnt)), block(256);
+    const dim3 grid(dge_grid(cnt)), block(256);
     if (rank <= 4) hipLaunchKernelGGL((k_nmf_update<4>), grid, block, 0, 0, X, cnt, rank, num, d, G, g_rows);
     else if (rank <= 10) hipLaunchKernelGGL((k_nmf_update<10>), grid, block, 0, 0, X, cnt, rank, num, d, G, g_rows);
     else if (rank <= 16) hipLaunchKernelGGL((k_nmf_update<16>), grid, block, 0, 0, X, cnt, rank, num, d, G, g_rows);
@@ -250,7 +190,7 @@ int blocked(const double* X, int64_t cnt, int rank, bool gram, double* bs, doubl
     const int comps = gram ? rank * rank : rank;
     if (gram) hipLaunchKernelGGL(k_nmf_gram_blocks, dim3((unsigned)n_blocks), dim3(256), 0, 0, X, cnt, rank, bs);
     else hipLaunchKernelGGL(k_nmf_col_blocks, dim3((unsigned)n_blocks), dim3(NMF_MAX_RANK), 0, 0, X, cnt, rank, bs);
-    hipLaunchKernelGGL(k_nmf_sum_blocks, dim3(nmf_grid(comps)), dim3(256), 0, 0, bs, n_blocks, comps, out);
+    hipLaunchKernelGGL(k_nmf_sum_blocks, dim3(dge_grid(comps)), dim3(256), 0, 0, bs, n_blocks, comps, out);
     DGE_HIP(hipGetLastError());
     return DGE_OK;
 }
@@ -270,45 +210,36 @@ int nmf_run(const char* who, const int32_t* d_row, const int32_t* d_col, const d
     int rc;
     const int rank = cfg->rank;
     const size_t nW = (size_t)n * (size_t)rank, nH = (size_t)m * (size_t)rank;
-    nmf_events ev;
-    DGE_HIP(hipEventCreate(&ev.e0)); DGE_HIP(hipEventCreate(&ev.e1));
-    DGE_HIP(hipEventRecord(ev.e0, 0));
+    dge_stopwatch watch;
+    if ((rc = watch.start(0))) return rc;
 
-    // ---- the entries: checks, the order by row, the order by column
-    dge_tmp<unsigned long long> d_c;
-    dge_tmp<uint64_t> key, skey, key2, skey2;
-    dge_tmp<int64_t> idx, sidx, rptr, cptr;
+    // ---- the entries: checks and the order by row (the shared intake), the order by column
+    coo_entries E;
+    if ((rc = coo_intake<NmfValue, true>(d_row, d_col, d_val, ne, n, m, 0x7fffffffLL, E))) return rc;
+    switch (E.fault) {
+    case COO_RANGE: DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld lies outside the %lld x %lld matrix", who, (long long)E.at, (long long)n, (long long)m);
+    case COO_KIND1: DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld holds a value that is not finite", who, (long long)E.at);
+    case COO_KIND2: DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld holds a negative value", who, (long long)E.at);
+    case COO_ZEROS: DGE_FAIL(DGE_ERR_ARG, "%s: no entry is left: all %lld values are zero", who, (long long)ne);
+    case COO_MANY: DGE_FAIL(DGE_ERR_ARG, "%s: %lld entries exceed 2^31 - 1", who, (long long)E.kept);
+    case COO_DUP: DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld repeats the row and column of an earlier entry", who, (long long)E.at);
+    }
+    const int64_t zeros = E.zeros, kept = E.kept;
+    const double vmax = E.vmax;
+
+    dge_tmp<uint64_t> key2, skey2;
+    dge_tmp<int64_t> rptr, cptr;
     dge_tmp<int32_t> ri, ci, pos, perm, crow;
     dge_tmp<double> V, cV, Q;
-    if ((rc = d_c.alloc(NC_N)) || (rc = key.alloc((size_t)ne)) || (rc = skey.alloc((size_t)ne)) || (rc = idx.alloc((size_t)ne)) || (rc = sidx.alloc((size_t)ne))) return rc;
-    unsigned long long c[NC_N] = {NMF_NONE, NMF_NONE, NMF_NONE, NMF_NONE, 0, 0};
-    DGE_HIP(hipMemcpy(d_c.p, c, sizeof c, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_nmf_scan, dim3(nmf_grid(ne)), dim3(256), 0, 0, d_row, d_col, d_val, ne, n, m, key.p, idx.p, d_c.p);
-    DGE_HIP(hipGetLastError());
-    DGE_HIP(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
-    if (c[NC_RANGE] != NMF_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld lies outside the %lld x %lld matrix", who, (long long)c[NC_RANGE], (long long)n, (long long)m);
-    if (c[NC_NONFINITE] != NMF_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld holds a value that is not finite", who, (long long)c[NC_NONFINITE]);
-    if (c[NC_NEGATIVE] != NMF_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld holds a negative value", who, (long long)c[NC_NEGATIVE]);
-    const int64_t zeros = (int64_t)c[NC_ZEROS], kept = ne - zeros;
-    if (kept < 1) DGE_FAIL(DGE_ERR_ARG, "%s: no entry is left: all %lld values are zero", who, (long long)ne);
-    if (kept > 0x7fffffffLL) DGE_FAIL(DGE_ERR_ARG, "%s: %lld entries exceed 2^31 - 1", who, (long long)kept);
-    double vmax;
-    memcpy(&vmax, &c[NC_VMAX], sizeof vmax);
-    if ((rc = nmf_sort(key.p, skey.p, idx.p, sidx.p, ne, 64))) return rc;
-    hipLaunchKernelGGL(k_nmf_dups, dim3(nmf_grid(kept)), dim3(256), 0, 0, skey.p, sidx.p, kept, d_c.p);
-    DGE_HIP(hipGetLastError());
-    DGE_HIP(hipMemcpy(c, d_c.p, sizeof c, hipMemcpyDeviceToHost));
-    if (c[NC_DUP] != NMF_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: entry %lld repeats the row and column of an earlier entry", who, (long long)c[NC_DUP]);
-
     if ((rc = ri.alloc((size_t)kept)) || (rc = ci.alloc((size_t)kept)) || (rc = pos.alloc((size_t)kept)) || (rc = perm.alloc((size_t)kept)) || (rc = crow.alloc((size_t)kept)) ||
         (rc = V.alloc((size_t)kept)) || (rc = cV.alloc((size_t)kept)) || (rc = Q.alloc((size_t)kept)) || (rc = key2.alloc((size_t)kept)) || (rc = skey2.alloc((size_t)kept)) ||
         (rc = rptr.alloc((size_t)n + 1)) || (rc = cptr.alloc((size_t)m + 1))) return rc;
-    hipLaunchKernelGGL(k_nmf_by_row, dim3(nmf_grid(kept)), dim3(256), 0, 0, skey.p, sidx.p, d_val, kept, n, m, ri.p, ci.p, V.p, key2.p, pos.p);
+    hipLaunchKernelGGL(k_nmf_by_row, dim3(dge_grid(kept)), dim3(256), 0, 0, E.skey.p, E.sidx.p, d_val, kept, n, m, ri.p, ci.p, V.p, key2.p, pos.p);
     DGE_HIP(hipGetLastError());
-    if ((rc = nmf_sort(key2.p, skey2.p, pos.p, perm.p, kept, bits_for((uint64_t)n * (uint64_t)m)))) return rc;
-    hipLaunchKernelGGL(k_nmf_by_col, dim3(nmf_grid(kept)), dim3(256), 0, 0, skey2.p, perm.p, V.p, kept, n, crow.p, cV.p);
-    hipLaunchKernelGGL(k_nmf_ptr, dim3(nmf_grid(n + 1)), dim3(256), 0, 0, skey.p, kept, (uint64_t)m, n, rptr.p);
-    hipLaunchKernelGGL(k_nmf_ptr, dim3(nmf_grid(m + 1)), dim3(256), 0, 0, skey2.p, kept, (uint64_t)n, m, cptr.p);
+    if ((rc = dge_sort_pairs(dge_scratch(), (const uint64_t*)key2.p, skey2.p, (const int32_t*)pos.p, perm.p, kept, dge_bits((uint64_t)n * (uint64_t)m), 0, true))) return rc;
+    hipLaunchKernelGGL(k_nmf_by_col, dim3(dge_grid(kept)), dim3(256), 0, 0, skey2.p, perm.p, V.p, kept, n, crow.p, cV.p);
+    hipLaunchKernelGGL(k_nmf_ptr, dim3(dge_grid(n + 1)), dim3(256), 0, 0, E.skey.p, kept, (uint64_t)m, n, rptr.p);
+    hipLaunchKernelGGL(k_nmf_ptr, dim3(dge_grid(m + 1)), dim3(256), 0, 0, skey2.p, kept, (uint64_t)n, m, cptr.p);
     DGE_HIP(hipGetLastError());
 
     // ---- the factors: W [n x rank], H transposed [m x rank]
@@ -328,12 +259,12 @@ int nmf_run(const char* who, const int32_t* d_row, const int32_t* d_col, const d
         DGE_HIP(hipMemcpy(dW.p, hostW.data(), nW * sizeof(double), hipMemcpyHostToDevice));
         DGE_HIP(hipMemcpy(dHt.p, hostHt.data(), nH * sizeof(double), hipMemcpyHostToDevice));
     } else {
-        hipLaunchKernelGGL(k_nmf_init, dim3(nmf_grid((int64_t)nW)), dim3(256), 0, 0, dW.p, n, rank, cfg->seed, (uint64_t)0, (uint64_t)rank, (uint64_t)1, vmax);
-        hipLaunchKernelGGL(k_nmf_init, dim3(nmf_grid((int64_t)nH)), dim3(256), 0, 0, dHt.p, m, rank, cfg->seed, (uint64_t)n * (uint64_t)rank, (uint64_t)1, (uint64_t)m, vmax);
+        hipLaunchKernelGGL(k_nmf_init, dim3(dge_grid((int64_t)nW)), dim3(256), 0, 0, dW.p, n, rank, cfg->seed, (uint64_t)0, (uint64_t)rank, (uint64_t)1, vmax);
+        hipLaunchKernelGGL(k_nmf_init, dim3(dge_grid((int64_t)nH)), dim3(256), 0, 0, dHt.p, m, rank, cfg->seed, (uint64_t)n * (uint64_t)rank, (uint64_t)1, (uint64_t)m, vmax);
         DGE_HIP(hipGetLastError());
     }
 
-    const dim3 egrid(nmf_grid(kept)), eblock(256);
+    const dim3 egrid(dge_grid(kept)), eblock(256);
     for (int it = 0; it < cfg->max_iter; it++) {
         if (cfg->update == 0) {
             hipLaunchKernelGGL(k_nmf_entries, egrid, eblock, 0, 0, ri.p, ci.p, V.p, dW.p, dHt.p, rank, kept, 0, Q.p);
@@ -372,10 +303,8 @@ int nmf_run(const char* who, const int32_t* d_row, const int32_t* d_col, const d
         for (int t = 0; t < comps; t++) cross += a[(size_t)t] * b[(size_t)t];
         objective = terms + cross;
     }
-    DGE_HIP(hipEventRecord(ev.e1, 0));
-    DGE_HIP(hipEventSynchronize(ev.e1));
     float ms = 0.f;
-    DGE_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if ((rc = watch.stop(&ms))) return rc;
 
     // outputs last: an error above leaves them as they were
     hostW.resize(nW);
@@ -409,10 +338,7 @@ extern "C" int dge_nmf_coo(int device, const int32_t* row, const int32_t* col, c
     if ((rc = dge_require_device(device))) return rc;
     dge_tmp<int32_t> d_row, d_col;
     dge_tmp<double> d_val;
-    if ((rc = d_row.alloc((size_t)n_entries)) || (rc = d_col.alloc((size_t)n_entries)) || (rc = d_val.alloc((size_t)n_entries))) return rc;
-    DGE_HIP(hipMemcpy(d_row.p, row, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
-    DGE_HIP(hipMemcpy(d_col.p, col, (size_t)n_entries * sizeof(int32_t), hipMemcpyHostToDevice));
-    DGE_HIP(hipMemcpy(d_val.p, val, (size_t)n_entries * sizeof(double), hipMemcpyHostToDevice));
+    if ((rc = coo_upload(row, col, val, n_entries, d_row, d_col, d_val))) return rc;
     return nmf_run(who, d_row.p, d_col.p, d_val.p, n_entries, n, m, cfg, init_W, init_H, W, H, info);
 }
 

@@ -5,7 +5,6 @@
 // the layer-0 marks), k_od_sources, the names "<h>-<region id>", and the hand-over to the graph (edges, reserved vertices, dge_graph_set_sources).
 // Everything is static, as in seq_tokens.h: each translation unit gets its own copy and the library exports nothing from here.  Outside the build stamp.
 #pragma once
-#include <rocprim/device/device_radix_sort.hpp>
 
 #include "seq_tokens.h"
 
@@ -77,18 +76,18 @@ void od_reset(dge_graph* g) {
     dge_tmp<int64_t> regions;
     {
         dge_tmp<int64_t> ends, sorted, newx;
-        dge_tmp<uint8_t> tmp;
         SEQ_TRY(seq_alloc(R, ends, 2 * E, "the endpoints"));
         SEQ_TRY(seq_alloc(R, sorted, 2 * E, "the sorted endpoints"));
         SEQ_TRY(seq_alloc(R, newx, 2 * E + 1, "the regions' numbers"));
-        size_t bytes = 0;
-        if (E) DGE_HIP(rocprim::radix_sort_keys(nullptr, bytes, ends.p, sorted.p, (size_t)(2 * E), 0, 64, R.stream));
-        SEQ_TRY(seq_alloc(R, tmp, (int64_t)bytes, "the sort's scratch"));
-        SEQ_TRY(seq_kernels_begin(R));
-        if (E) {
+        SeqScratch tmp{R, "the sort's scratch", true};
+        void* none = nullptr;
+        auto tmp_then_ends = [&](size_t bytes, void** p) -> int {       // the sort's input is made once the clock runs
+            SEQ_TRY(tmp(bytes, p));
             hipLaunchKernelGGL(k_od_endpoints, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, src_id, dst_id, keepx, rows, ends.p);
-            DGE_HIP(rocprim::radix_sort_keys((void*)tmp.p, bytes, ends.p, sorted.p, (size_t)(2 * E), 0, 64, R.stream));
-        }
+            return DGE_OK;
+        };
+        if (E) SEQ_TRY(dge_sort_keys(tmp_then_ends, ends.p, sorted.p, 2 * E, 64, R.stream, false));
+        else SEQ_TRY(tmp(0, &none));
         SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdNewFlag{sorted.p, 2 * E}), newx.p, 2 * E + 1));
         SEQ_TRY(seq_kernels_end(R));
         SEQ_TRY(seq_read_back(R, &n_regions, newx.p + 2 * E, 8));
@@ -98,7 +97,7 @@ void od_reset(dge_graph* g) {
         SEQ_TRY(seq_kernels_begin(R));
         if (E) hipLaunchKernelGGL(k_od_unique, dim3(seq_grid(2 * E)), dim3(SEQ_BLOCK), 0, R.stream, sorted.p, newx.p, 2 * E, regions.p);
         SEQ_TRY(seq_kernels_end(R));
-        seq_release(R, ends, 2 * E); seq_release(R, sorted, 2 * E); seq_release(R, newx, 2 * E + 1); seq_release(R, tmp, (int64_t)bytes);
+        seq_release(R, ends, 2 * E); seq_release(R, sorted, 2 * E); seq_release(R, newx, 2 * E + 1); tmp.release();
     }
     const int64_t Rn = n_regions;
 

@@ -39,13 +39,12 @@
 #include <chrono>
 #include <hipcub/hipcub.hpp>
 #include <memory>
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 #include <string_view>
 
 #include "dge_algos.h"
-#include "dge_internal.h"
+#include "dge_device.h"
 #include "seq_plan.h"
 
 // blob: count strings, string k at blob + off[k], NUL-terminated; takes the blob over
@@ -296,7 +295,8 @@ struct SeqPiece { const char* path = nullptr; const uint8_t* mem = nullptr; int 
 struct SeqRun {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ka = nullptr, kb = nullptr, copied[2] = {nullptr, nullptr};
+    hipEvent_t copied[2] = {nullptr, nullptr};
+    dge_stopwatch kernels;            // seq_kernels_begin .. seq_kernels_end, summed in kernel_ms
     uint8_t* pin[2] = {nullptr, nullptr};
     std::vector<SeqPiece> pieces;
     seq_layout L;
@@ -316,8 +316,6 @@ struct SeqRun {
     ~SeqRun() {
         for (SeqPiece& p : pieces) if (p.fd >= 0) close(p.fd);
         for (int i = 0; i < 2; i++) { if (pin[i]) (void)hipHostFree(pin[i]); if (copied[i]) (void)hipEventDestroy(copied[i]); }
-        if (ka) (void)hipEventDestroy(ka);
-        if (kb) (void)hipEventDestroy(kb);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -346,26 +344,29 @@ int seq_read_back(SeqRun& R, void* dst, const void* src, size_t bytes) {
     DGE_HIP(hipStreamSynchronize(R.stream));
     return DGE_OK;
 }
-int seq_kernels_begin(SeqRun& R) { DGE_HIP(hipEventRecord(R.ka, R.stream)); return DGE_OK; }
+int seq_kernels_begin(SeqRun& R) { return R.kernels.start(R.stream); }
 int seq_kernels_end(SeqRun& R) {
-    DGE_HIP(hipEventRecord(R.kb, R.stream));
-    DGE_HIP(hipEventSynchronize(R.kb));
     float ms = 0.f;
-    DGE_HIP(hipEventElapsedTime(&ms, R.ka, R.kb));
+    SEQ_TRY(R.kernels.stop(&ms));
     R.kernel_ms += ms;
     return DGE_OK;
 }
 unsigned seq_grid(int64_t n) { return (unsigned)((n + SEQ_BLOCK - 1) / SEQ_BLOCK); }
 
+// the allocator of a library call's scratch (dge_two_pass) under the run's accounting; begin: the kernels' clock starts once the scratch is there
+struct SeqScratch {
+    SeqRun& R; const char* what; bool begin;
+    dge_tmp<uint8_t> t;
+    int64_t n = 0;
+    int operator()(size_t bytes, void** p) { n = (int64_t)bytes; SEQ_TRY(seq_alloc(R, t, n, what)); *p = t.p; return begin ? seq_kernels_begin(R) : DGE_OK; }
+    void release() { seq_release(R, t, n); }
+};
+
 template <typename In>
 int seq_scan(SeqRun& R, In in, int64_t* out, int64_t n) {      // out[i] = sum of in[0 .. i), n entries
-    size_t bytes = 0;
-    DGE_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), R.stream));
-    dge_tmp<uint8_t> tmp;
-    SEQ_TRY(seq_alloc(R, tmp, (int64_t)bytes, "the scan's scratch"));
-    DGE_HIP(rocprim::exclusive_scan((void*)tmp.p, bytes, in, out, (int64_t)0, (size_t)n, rocprim::plus<int64_t>(), R.stream));
-    DGE_HIP(hipStreamSynchronize(R.stream));
-    seq_release(R, tmp, (int64_t)bytes);
+    SeqScratch tmp{R, "the scan's scratch", false};
+    SEQ_TRY(dge_exclusive_sum(tmp, in, out, n, R.stream, true));
+    tmp.release();
     return DGE_OK;
 }
 
@@ -448,8 +449,6 @@ struct SeqOptions { int32_t hash_bits = 64; int64_t initial_slots = 0; int inter
     for (const SeqPiece& p : R.pieces) sizes.push_back(p.size);
     if (!seq_plan_layout((int64_t)prefix.size(), sizes.data(), (int64_t)sizes.size(), &R.L)) DGE_FAIL(DGE_ERR_ARG, "%s: the text's size leaves 64 bits", who);
     DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-    DGE_HIP(hipEventCreate(&R.ka));
-    DGE_HIP(hipEventCreate(&R.kb));
     // ---- bytes to the device: chunk c + 1 is read (or copied out of the caller's memory) into one pinned buffer while chunk c leaves the other
     const auto t0 = clock::now();
     SEQ_TRY(seq_alloc(R, R.buf, R.L.padded, "the text"));

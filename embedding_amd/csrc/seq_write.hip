@@ -28,9 +28,8 @@
 #include <algorithm>
 #include <chrono>
 #include <hipcub/hipcub.hpp>
-#include <rocprim/device/device_scan.hpp>
 
-#include "dge_internal.h"
+#include "dge_device.h"
 #include "seq_out_plan.h"
 
 // ------------------------------------------------------------------------------------------ kernels
@@ -289,17 +288,18 @@ int sqw_run(const dge_walks* w, int64_t row0, int64_t n_rows, const dge_names* n
         SQW_TRY(R.row_off.alloc((size_t)n_rows + 1));
         SQW_TRY(R.row_last.alloc((size_t)n_rows));
         SQW_TRY(R.counters.alloc(3));
-        size_t scan_bytes = 0;
-        DGE_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, R.row_len.p, R.row_off.p, (int64_t)0, (size_t)n_rows + 1, rocprim::plus<int64_t>(), R.ks));
-        SQW_TRY(R.scratch.alloc(scan_bytes));
-        DGE_HIP(hipEventRecord(R.ka[0], R.ks));
-        DGE_HIP(hipMemsetAsync(R.counters.p, 0, 16, R.ks));
-        DGE_HIP(hipMemsetAsync(R.counters.p + 2, 0xFF, 8, R.ks));
-        DGE_HIP(hipMemsetAsync(R.row_len.p + n_rows, 0, 8, R.ks));
-        hipLaunchKernelGGL(k_sqw_size, dim3((unsigned)((n_rows + SQW_BLOCK - 1) / SQW_BLOCK)), dim3(SQW_BLOCK), 0, R.ks, walks, L, n_rows, N, prefix, R.row_len.p, R.row_last.p,
-                           R.counters.p);
-        DGE_HIP(hipGetLastError());
-        DGE_HIP(rocprim::exclusive_scan((void*)R.scratch.p, scan_bytes, R.row_len.p, R.row_off.p, (int64_t)0, (size_t)n_rows + 1, rocprim::plus<int64_t>(), R.ks));
+        auto scratch_then_sizes = [&](size_t scan_bytes, void** p) -> int {         // the scan's input is made once its scratch is there and the clock runs
+            SQW_TRY(R.scratch.alloc(scan_bytes));
+            *p = R.scratch.p;
+            DGE_HIP(hipEventRecord(R.ka[0], R.ks));
+            DGE_HIP(hipMemsetAsync(R.counters.p, 0, 16, R.ks));
+            DGE_HIP(hipMemsetAsync(R.counters.p + 2, 0xFF, 8, R.ks));
+            DGE_HIP(hipMemsetAsync(R.row_len.p + n_rows, 0, 8, R.ks));
+            hipLaunchKernelGGL(k_sqw_size, dim3(dge_grid(n_rows, SQW_BLOCK)), dim3(SQW_BLOCK), 0, R.ks, walks, L, n_rows, N, prefix, R.row_len.p, R.row_last.p, R.counters.p);
+            DGE_HIP(hipGetLastError());
+            return DGE_OK;
+        };
+        SQW_TRY(dge_exclusive_sum(scratch_then_sizes, R.row_len.p, R.row_off.p, n_rows + 1, R.ks, false));
         DGE_HIP(hipEventRecord(R.kb[0], R.ks));
         DGE_HIP(hipMemcpyAsync(counters, R.counters.p, sizeof counters, hipMemcpyDeviceToHost, R.ks));
         DGE_HIP(hipMemcpyAsync(&total, R.row_off.p + n_rows, 8, hipMemcpyDeviceToHost, R.ks));

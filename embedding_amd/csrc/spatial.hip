@@ -119,8 +119,6 @@ namespace {
 int sp_open(SeqRun& R, int device, const char* what) {
     R.device = device; R.what = what;
     DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-    DGE_HIP(hipEventCreate(&R.ka));
-    DGE_HIP(hipEventCreate(&R.kb));
     return DGE_OK;
 }
 

@@ -30,6 +30,7 @@
 #include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/iterator/constant_iterator.hpp>
 
+#include "coo_entries.h"
 #include "od_commit.h"
 #include "pip_exact.h"
 
@@ -79,9 +80,7 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_trip_keys(const double* xy, int64
 __global__ void __launch_bounds__(SEQ_BLOCK) k_trip_bounds(const uint32_t* key, int64_t n, int64_t cells, int64_t* cell_start) {
     const int64_t c = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
     if (c > cells) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)key[mid] < c) lo = mid + 1; else hi = mid; }
-    cell_start[c] = lo;
+    cell_start[c] = coo_lower_bound(key, n, (uint32_t)c);
 }
 
 struct TripBlocks { const int64_t* cell_start; int64_t cells; __device__ int64_t operator()(int64_t c) const { return c < cells ? (cell_start[c + 1] - cell_start[c] + SEQ_BLOCK - 1) / SEQ_BLOCK : 0; } };
@@ -171,8 +170,7 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_slot_items(const uint64_t* key, c
         bool ok = slot >= 0 && slot < T;
         if (ok && j > 0) {
             const uint64_t want = ((uint64_t)slot * R + s) * R + e;
-            int64_t lo = 0, hi = n;
-            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (key[mid] < want) lo = mid + 1; else hi = mid; }
+            const int64_t lo = coo_lower_bound(key, n, want);
             ok = lo < n && key[lo] == want;
         }
         item_key[t] = ok ? ((uint64_t)slot * R + (uint64_t)idrank[s]) * R + (uint64_t)idrank[e] : ~0ull;
@@ -216,8 +214,6 @@ namespace {
 int trip_open(SeqRun& R, int device, const char* what) {
     R.device = device; R.what = what;
     DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-    DGE_HIP(hipEventCreate(&R.ka));
-    DGE_HIP(hipEventCreate(&R.kb));
     return DGE_OK;
 }
 
@@ -231,8 +227,6 @@ int trip_upload(SeqRun& R, T** dst, const T* src, int64_t n, const char* what) {
     return DGE_OK;
 }
 
-int bits_of(uint64_t v) { int b = 0; while (v) { b++; v >>= 1; } return std::max(b, 1); }
-
 // regions of n <= TRIP_CHUNK points already on the device; the counters (device, TC_N words) are added to
 int trip_locate(SeqRun& R, const dge_regions* rg, const double* d_xy, int64_t n, int32_t* d_region, unsigned long long* d_counters) {
     if (n == 0) return DGE_OK;
@@ -240,20 +234,19 @@ int trip_locate(SeqRun& R, const dge_regions* rg, const double* d_xy, int64_t n,
     const TripIndex ix = {rg->box[0], rg->box[1], rg->box[2], rg->box[3], rg->invx, rg->invy, rg->grid, rg->R > 0 ? 1 : 0};
     dge_tmp<uint32_t> key, idx, key2, idx2;
     dge_tmp<int64_t> cell_start, blk_first;
-    dge_tmp<uint8_t> tmp;
     SEQ_TRY(seq_alloc(R, key, n, "the points' cells"));
     SEQ_TRY(seq_alloc(R, idx, n, "the points' numbers"));
     SEQ_TRY(seq_alloc(R, key2, n, "the sorted cells"));
     SEQ_TRY(seq_alloc(R, idx2, n, "the sorted points"));
     SEQ_TRY(seq_alloc(R, cell_start, cells + 1, "the cells' runs"));
     SEQ_TRY(seq_alloc(R, blk_first, cells + 1, "the cells' workgroups"));
-    size_t bytes = 0;
-    const int end_bit = bits_of((uint64_t)cells);
-    DGE_HIP(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key2.p, idx.p, idx2.p, (size_t)n, 0, end_bit, R.stream));
-    SEQ_TRY(seq_alloc(R, tmp, (int64_t)bytes, "the sort's scratch"));
-    SEQ_TRY(seq_kernels_begin(R));
-    hipLaunchKernelGGL(k_trip_keys, dim3(seq_grid(n)), dim3(SEQ_BLOCK), 0, R.stream, d_xy, n, ix, key.p, idx.p, d_region, d_counters);
-    DGE_HIP(rocprim::radix_sort_pairs((void*)tmp.p, bytes, key.p, key2.p, idx.p, idx2.p, (size_t)n, 0, end_bit, R.stream));
+    SeqScratch tmp{R, "the sort's scratch", true};
+    auto tmp_then_keys = [&](size_t bytes, void** p) -> int {           // the sort's input is made once the clock runs
+        SEQ_TRY(tmp(bytes, p));
+        hipLaunchKernelGGL(k_trip_keys, dim3(seq_grid(n)), dim3(SEQ_BLOCK), 0, R.stream, d_xy, n, ix, key.p, idx.p, d_region, d_counters);
+        return DGE_OK;
+    };
+    SEQ_TRY(dge_sort_pairs(tmp_then_keys, key.p, key2.p, idx.p, idx2.p, n, dge_bits((uint64_t)cells), R.stream, false));
     hipLaunchKernelGGL(k_trip_bounds, dim3(seq_grid(cells + 1)), dim3(SEQ_BLOCK), 0, R.stream, key2.p, n, cells, cell_start.p);
     SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), TripBlocks{cell_start.p, cells}), blk_first.p, cells + 1));
     SEQ_TRY(seq_kernels_end(R));
@@ -276,30 +269,22 @@ int trip_reduce(SeqRun& R, const uint64_t* keys, const int64_t* vals, int64_t n,
     SEQ_TRY(seq_alloc(R, usum, n, "the summed counts"));
     if (n == 0) return DGE_OK;
     dge_tmp<int64_t> count;
-    dge_tmp<uint8_t> tmp;
     SEQ_TRY(seq_alloc(R, count, 1, "the number of keys"));
-    size_t bytes = 0;
-    const rocprim::constant_iterator<int64_t> ones(1);
-    if (vals) DGE_HIP(rocprim::reduce_by_key(nullptr, bytes, keys, vals, (size_t)n, ukey.p, usum.p, count.p, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), R.stream));
-    else DGE_HIP(rocprim::reduce_by_key(nullptr, bytes, keys, ones, (size_t)n, ukey.p, usum.p, count.p, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), R.stream));
-    SEQ_TRY(seq_alloc(R, tmp, (int64_t)bytes, "the reduction's scratch"));
-    SEQ_TRY(seq_kernels_begin(R));
-    if (vals) DGE_HIP(rocprim::reduce_by_key((void*)tmp.p, bytes, keys, vals, (size_t)n, ukey.p, usum.p, count.p, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), R.stream));
-    else DGE_HIP(rocprim::reduce_by_key((void*)tmp.p, bytes, keys, ones, (size_t)n, ukey.p, usum.p, count.p, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), R.stream));
+    SeqScratch tmp{R, "the reduction's scratch", true};
+    auto reduce = [&](auto values) {
+        return dge_two_pass(tmp, [&](void* t, size_t& bytes) {
+            return rocprim::reduce_by_key(t, bytes, keys, values, (size_t)n, ukey.p, usum.p, count.p, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), R.stream);
+        }, R.stream, false);
+    };
+    SEQ_TRY(vals ? reduce(vals) : reduce(rocprim::constant_iterator<int64_t>(1)));
     SEQ_TRY(seq_kernels_end(R));
     return seq_read_back(R, n_out, count.p, 8);
 }
 
 int trip_sort_pairs(SeqRun& R, const uint64_t* k_in, uint64_t* k_out, const int64_t* v_in, int64_t* v_out, int64_t n, int end_bit) {
     if (n == 0) return DGE_OK;
-    size_t bytes = 0;
-    dge_tmp<uint8_t> tmp;
-    if (v_in) DGE_HIP(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, end_bit, R.stream));
-    else DGE_HIP(rocprim::radix_sort_keys(nullptr, bytes, k_in, k_out, (size_t)n, 0, end_bit, R.stream));
-    SEQ_TRY(seq_alloc(R, tmp, (int64_t)bytes, "the sort's scratch"));
-    SEQ_TRY(seq_kernels_begin(R));
-    if (v_in) DGE_HIP(rocprim::radix_sort_pairs((void*)tmp.p, bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, end_bit, R.stream));
-    else DGE_HIP(rocprim::radix_sort_keys((void*)tmp.p, bytes, k_in, k_out, (size_t)n, 0, end_bit, R.stream));
+    SeqScratch tmp{R, "the sort's scratch", true};
+    SEQ_TRY(v_in ? dge_sort_pairs(tmp, k_in, k_out, v_in, v_out, n, end_bit, R.stream, false) : dge_sort_keys(tmp, k_in, k_out, n, end_bit, R.stream, false));
     return seq_kernels_end(R);
 }
 
@@ -452,7 +437,7 @@ int flows_add(dge_flows* f, const double* sxy, const double* exy, const int32_t*
         }
         DGE_HIP(hipMemcpyAsync(ckey.p + tn, ukey.p, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
         DGE_HIP(hipMemcpyAsync(ccnt.p + tn, ucnt.p, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
-        SEQ_TRY(trip_sort_pairs(R, ckey.p, cskey.p, ccnt.p, cscnt.p, tn + u, bits_of(24 * Ru * Ru)));
+        SEQ_TRY(trip_sort_pairs(R, ckey.p, cskey.p, ccnt.p, cscnt.p, tn + u, dge_bits(24 * Ru * Ru)));
         SEQ_TRY(trip_reduce(R, cskey.p, cscnt.p, tn + u, nkey, ncnt, &nn));
         DGE_HIP(hipStreamSynchronize(R.stream));
         if (tkey.p) { (void)hipFree(tkey.p); (void)hipFree(tcnt.p); }
@@ -639,7 +624,7 @@ int dge_flows_merge(dge_flows* f, const dge_flows* part) {
         }
         DGE_HIP(hipMemcpyAsync(ckey.p + tn, part->d_key, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
         DGE_HIP(hipMemcpyAsync(ccnt.p + tn, part->d_cnt, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
-        SEQ_TRY(trip_sort_pairs(R, ckey.p, cskey.p, ccnt.p, cscnt.p, tn + u, bits_of(24 * Ru * Ru)));
+        SEQ_TRY(trip_sort_pairs(R, ckey.p, cskey.p, ccnt.p, cscnt.p, tn + u, dge_bits(24 * Ru * Ru)));
         SEQ_TRY(trip_reduce(R, cskey.p, cscnt.p, tn + u, nkey, ncnt, &nn));
         DGE_HIP(hipStreamSynchronize(R.stream));
         // nothing can fail from here on

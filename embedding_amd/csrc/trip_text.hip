@@ -289,8 +289,6 @@ struct TripReader {
         c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
         if (!c_locale) DGE_FAIL(DGE_ERR_STATE, "%s: the \"C\" locale is not available", who);
         DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-        DGE_HIP(hipEventCreate(&R.ka));
-        DGE_HIP(hipEventCreate(&R.kb));
         DGE_HIP(hipEventCreate(&ea));
         DGE_HIP(hipEventCreate(&eb));
         int64_t total = 0, largest = 0;

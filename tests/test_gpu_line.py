@@ -1,8 +1,8 @@
 """GPU: dge_line_coo / dge_line_flows (csrc/line.hip) against the rule of include/dge.h as tests/line_ref.py reads it: X, Y and touched as bits and the counters
 of info, for both orders, at the row widths where a lane takes another column (dim 1, 15, 16, 17, 20, 33, 64, 65, 128, 256), K 0, 1, 5, 32 and batches of 1, 7
 and 256 samples with a short last batch; a larger run equals the host loop of tests/native/line_rule_harness.cpp; two calls and a shuffled input give the same
-bits; leaving the bound is an error that names the batch; errors name the right entry and leave the outputs untouched; the flow table's slots as graphs; and the
-three-block graph is learnt: every cosine neighbour of every vertex lies in its block.
+bits; leaving the bound is an error that names the batch; errors name the right entry and leave the outputs untouched, in the order of their kinds, a repeat across
+a workgroup boundary of the check and dropped entries that are none included; the flow table's slots as graphs; and the three-block graph is learnt: every cosine neighbour of every vertex lies in its block.
 
 The "mixed" graph has 40 vertices: vertex 38 has in-edges and no out-edge (never a negative, touched), vertex 39 no edge at all (untouched, its row stays at its
 initial value).  The "hub" graph points every edge at vertex 3, so one row takes every target add of a batch."""
@@ -210,6 +210,81 @@ def test_errors_name_the_entry_and_leave_the_outputs_untouched(dge):
         assert (X == 9.0).all() and (Y == 7.0).all() and (touched == 5).all() and info.vertices == -5, what
     assert call(w=poke({33: 2.0 ** 31 - 1}))[0] == 0 and info.total_weight == int(w.sum() - w[33]) + 2 ** 31 - 1      # the greatest weight
     assert call()[0] == 0 and (X[:39] != 9.0).all() and info.vertices == n and info.entries == n_e and (touched <= 1).all()
+
+
+def _error_call(dge):
+    """dge_line_coo on 40 vertices with sentinel-filled outputs: call(s, d, w) -> the message; asserts the error return and the untouched outputs"""
+    from embedding_amd._native import LineCfg, LineInfo
+    X = np.full((40, 8), 9.0); Y = np.full((40, 8), 7.0); touched = np.full(40, 5, np.uint8); info = LineInfo(); info.vertices = -5
+    p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+
+    def call(s, d, w):
+        cfg = LineCfg(8, 2, 5, 64, 500, 0.025, 1)
+        s = np.ascontiguousarray(s, np.int32); d = np.ascontiguousarray(d, np.int32); w = np.ascontiguousarray(w, np.float64)
+        rc = dge.lib.dge_line_coo(0, p(s), p(d), p(w), len(w), 40, C.byref(cfg), None, None, p(X), p(Y), p(touched), C.byref(info))
+        msg = (dge.lib.dge_last_error() or b"").decode()
+        assert rc == 1 and "dge_line_coo" in msg, (rc, msg)
+        assert (X == 9.0).all() and (Y == 7.0).all() and (touched == 5).all() and info.vertices == -5, msg
+        return msg
+    return call
+
+
+def test_faults_of_every_kind_at_once_are_reported_in_the_order_of_the_kinds(dge):
+    """one input holds a weight of 2^31 (entry 20), a fraction (30), a repeat (40 repeats 3) and a vertex outside (60): the kinds are looked for in the order
+    outside, not an integer, too great, repeat, whatever their indices — the least index over all kinds, 20, comes third"""
+    call = _error_call(dge)
+    s, d, w, n = mixed_graph()
+    assert n == 40 and len(w) > 61
+    s = s.copy(); d = d.copy(); w = w.copy()
+    good_d60 = d[60]
+    s[40], d[40] = s[3], d[3]
+    w[20] = 2.0 ** 31; w[30] = 1.5; d[60] = 40
+    msg = call(s, d, w)
+    assert "entry 60 " in msg and "outside" in msg, msg
+    d[60] = good_d60
+    msg = call(s, d, w)
+    assert "entry 30 " in msg and "integer" in msg, msg
+    w[30] = 2.0
+    msg = call(s, d, w)
+    assert "entry 20 " in msg and "2^31" in msg, msg
+    w[20] = 2.0
+    msg = call(s, d, w)
+    assert "entry 40 " in msg and "repeats" in msg, msg
+
+
+def distinct_edges(count, seed):
+    """count edges among 40 vertices on distinct (source, destination) pairs, in no order, integer weights"""
+    rng = np.random.default_rng(seed)
+    k = rng.permutation(40 * 40)[:count]
+    return (k // 40).astype(np.int32), (k % 40).astype(np.int32), rng.integers(1, 51, count).astype(np.float64)
+
+
+def test_a_repeat_whose_two_entries_sort_into_different_workgroups_of_the_check(dge):
+    """258 kept entries; the last repeats the pair of the entry that sorts to position 255 of the others, so the two sit at sorted positions 255 and 256"""
+    call = _error_call(dge)
+    s, d, w = distinct_edges(258, 11)
+    at = int(np.argsort(s[:257].astype(np.int64) * 40 + d[:257])[255])
+    s[257], d[257] = s[at], d[at]
+    msg = call(s, d, w)
+    assert "entry 257 " in msg and "repeats" in msg, msg
+    front = lambda a: np.concatenate([a[[257]], a[:257]])      # noqa: E731    the copy in front: the original, shifted by one, is the second occurrence
+    msg = call(front(s), front(d), front(w))
+    assert ("entry %d " % (at + 1)) in msg and "repeats" in msg, msg
+
+
+def test_dropped_entries_are_no_repeats(dge):
+    """three zeros on one pair that a kept entry holds and two -0.0 on another, spread through the input: counted, and the tables are those without them"""
+    import embedding_amd.evaluate as ev
+    s, d, w = distinct_edges(258, 11)
+    kw = dict(dim=8, order=2, negative=5, samples=500, batch=64, rho0=0.025, seed=5)
+    X, Y, touched, info = ev.line_gpu(s, d, w, 40, **kw)
+    assert info["entries"] == 258 and info["zeros"] == 0
+    s2, d2, w2 = s.tolist(), d.tolist(), w.tolist()
+    for at, edge, zero in ((258, 7, 0.0), (200, 100, -0.0), (129, 7, 0.0), (40, 100, -0.0), (0, 7, 0.0)):      # descending places: each insert leaves the earlier ones where they are
+        s2.insert(at, int(s[edge])); d2.insert(at, int(d[edge])); w2.insert(at, zero)
+    X2, Y2, touched2, info2 = ev.line_gpu(np.array(s2, np.int32), np.array(d2, np.int32), np.array(w2), 40, **kw)
+    assert info2["zeros"] == 5 and info2["entries"] == 258
+    assert ref.same_bits(X2, X) and ref.same_bits(Y2, Y) and np.array_equal(touched2, touched)
 
 
 def flows_fixture(dge):

@@ -1,7 +1,8 @@
 """GPU: dge_nmf_coo / dge_nmf_flows (csrc/nmf.hip) against the rule of include/dge.h as tests/nmf_ref.py reads it: W and H as bits and the counters of info,
 for both updates, at the sizes where a segment sum or a blocked sum changes its shape; a larger matrix equals the host loop of
-tests/native/nmf_rule_harness.cpp; two calls and a shuffled input give the same bits; errors name the right entry and leave the outputs untouched; the flow
-table's slots as matrices; the features end to end.
+tests/native/nmf_rule_harness.cpp; two calls and a shuffled input give the same bits; errors name the right entry and leave the outputs untouched, in the order
+of their kinds, a repeat across a workgroup boundary of the check and dropped entries that are none included; the flow table's slots as matrices; the features end
+to end.
 
 The 64 x 48 case holds rows and columns of exactly 0, 1, 15, 16, 17, 31, 32 and 33 entries.  A row or column of 700 entries — the hub — does not fit into a
 64 x 48 matrix; it is the 40 x 720 and 720 x 40 cases."""
@@ -190,6 +191,81 @@ def test_errors_name_the_entry_and_leave_the_outputs_untouched(dge):
             assert w in msg, (what, msg)
         assert (W == 9.0).all() and (H == 7.0).all() and info.rows == -5, what
     assert call()[0] == 0 and (W.ravel()[:200] != 9.0).all() and info.rows == 50 and info.entries == n_e
+
+
+def _error_call(dge):
+    """dge_nmf_coo on a 50 x 40 matrix with sentinel-filled outputs: call(r, c, v) -> the message; asserts the error return and the untouched outputs"""
+    from embedding_amd._native import NmfCfg, NmfInfo
+    W = np.full((50, 4), 9.0); H = np.full((4, 40), 7.0); info = NmfInfo(); info.rows = -5
+    p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+
+    def call(r, c, v):
+        cfg = NmfCfg(4, 2, 0, 0, 1)
+        r = np.ascontiguousarray(r, np.int32); c = np.ascontiguousarray(c, np.int32); v = np.ascontiguousarray(v, np.float64)
+        rc = dge.lib.dge_nmf_coo(0, p(r), p(c), p(v), len(v), 50, 40, C.byref(cfg), None, None, p(W), p(H), C.byref(info))
+        msg = (dge.lib.dge_last_error() or b"").decode()
+        assert rc == 1 and "dge_nmf_coo" in msg, (rc, msg)
+        assert (W == 9.0).all() and (H == 7.0).all() and info.rows == -5, msg
+        return msg
+    return call
+
+
+def test_faults_of_every_kind_at_once_are_reported_in_the_order_of_the_kinds(dge):
+    """one input holds a negative value (entry 20), a NaN (30), a repeat (40 repeats 3) and a column outside (60): the kinds are looked for in the order outside,
+    not finite, negative, repeat, whatever their indices — the least index over all kinds, 20, comes third"""
+    call = _error_call(dge)
+    r, c, v = ref.random_sparse(50, 40, 0.2, 9)
+    assert len(v) > 61
+    r = r.copy(); c = c.copy(); v = v.copy()
+    good_c60 = c[60]
+    r[40], c[40] = r[3], c[3]
+    v[20] = -1.0; v[30] = np.nan; c[60] = 40
+    msg = call(r, c, v)
+    assert "entry 60 " in msg and "outside" in msg, msg
+    c[60] = good_c60
+    msg = call(r, c, v)
+    assert "entry 30 " in msg and "not finite" in msg, msg
+    v[30] = 2.0
+    msg = call(r, c, v)
+    assert "entry 20 " in msg and "negative" in msg, msg
+    v[20] = 2.0
+    msg = call(r, c, v)
+    assert "entry 40 " in msg and "repeats" in msg, msg
+
+
+def distinct_cells(count, seed):
+    """count entries of a 50 x 40 matrix on distinct cells, in no order, integer values"""
+    rng = np.random.default_rng(seed)
+    k = rng.permutation(50 * 40)[:count]
+    return (k // 40).astype(np.int32), (k % 40).astype(np.int32), rng.integers(1, 51, count).astype(np.float64)
+
+
+def test_a_repeat_whose_two_entries_sort_into_different_workgroups_of_the_check(dge):
+    """258 kept entries; the last repeats the cell of the entry that sorts to position 255 of the others, so the pair sits at sorted positions 255 and 256"""
+    call = _error_call(dge)
+    r, c, v = distinct_cells(258, 11)
+    at = int(np.argsort(r[:257].astype(np.int64) * 40 + c[:257])[255])
+    r[257], c[257] = r[at], c[at]
+    msg = call(r, c, v)
+    assert "entry 257 " in msg and "repeats" in msg, msg
+    front = lambda a: np.concatenate([a[[257]], a[:257]])      # noqa: E731    the copy in front: the original, shifted by one, is the second occurrence
+    msg = call(front(r), front(c), front(v))
+    assert ("entry %d " % (at + 1)) in msg and "repeats" in msg, msg
+
+
+def test_dropped_entries_are_no_repeats(dge):
+    """three zeros on one cell that a kept entry holds and two -0.0 on another, spread through the input: counted, and the factors are those without them"""
+    import embedding_amd.evaluate as ev
+    r, c, v = distinct_cells(258, 11)
+    kw = dict(rank=4, max_iter=2, update="divergence", seed=5)
+    W, H, info = ev.nmf_gpu(r, c, v, (50, 40), **kw)
+    assert info["entries"] == 258 and info["zeros"] == 0
+    r2, c2, v2 = r.tolist(), c.tolist(), v.tolist()
+    for at, cell, zero in ((258, 7, 0.0), (200, 100, -0.0), (129, 7, 0.0), (40, 100, -0.0), (0, 7, 0.0)):      # descending places: each insert leaves the earlier ones where they are
+        r2.insert(at, int(r[cell])); c2.insert(at, int(c[cell])); v2.insert(at, zero)
+    W2, H2, info2 = ev.nmf_gpu(np.array(r2, np.int32), np.array(c2, np.int32), np.array(v2), (50, 40), **kw)
+    assert info2["zeros"] == 5 and info2["entries"] == 258
+    assert ref.same_bits(W2, W) and ref.same_bits(H2, H)
 
 
 def flows_fixture(dge):
