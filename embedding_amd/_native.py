@@ -129,6 +129,17 @@ class LineInfo(C.Structure):
                 ("neg_total", C.c_int64), ("max_abs", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class TreeCfg(C.Structure):
+    """struct dge_tree_cfg (include/dge.h)."""
+    _fields_ = [("max_depth", C.c_int32), ("min_samples_split", C.c_int32), ("min_samples_leaf", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TreeInfo(C.Structure):
+    """struct dge_tree_info (include/dge.h) — what dge_tree_fit* / dge_tree_cv* report."""
+    _fields_ = [("rows", C.c_int64), ("n_nodes", C.c_int64), ("depth", C.c_int32), ("levels", C.c_int32), ("trees", C.c_int32), ("batches", C.c_int32),
+                ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
 DGE_NMF_DIVERGENCE, DGE_NMF_EUCLIDEAN = 0, 1
 DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
@@ -263,6 +274,11 @@ SIGNATURES = {
     "dge_nmf_flows": (_int, [_vp, _i32, _i32, _i32, _vp, _P(NmfCfg), _vp, _vp, _vp, _P(NmfInfo)]),
     "dge_line_coo": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _P(LineCfg), _vp, _vp, _vp, _vp, _vp, _P(LineInfo)]),
     "dge_line_flows": (_int, [_vp, _i32, _i32, _i32, _vp, _P(LineCfg), _vp, _vp, _vp, _vp, _P(LineInfo)]),
+    "dge_tree_fit_vectors": (_int, [_vp, _vp, _vp, _P(TreeCfg), _i64, _vp, _vp, _vp, _vp, _vp, _P(TreeInfo)]),
+    "dge_tree_predict_vectors": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "dge_tree_cv_vectors": (_int, [_vp, _vp, _vp, _i32, _P(TreeCfg), _vp, _vp, _vp, _vp, _P(TreeInfo)]),
+    "dge_tree_fit": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _P(TreeCfg), _i64, _vp, _vp, _vp, _vp, _vp, _P(TreeInfo)]),
+    "dge_tree_cv": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i32, _P(TreeCfg), _vp, _vp, _vp, _vp, _P(TreeInfo)]),
     "dge_selftest_locked_rows": (_int, [_int, _i32, _i64, _i32, C.c_uint64, _i32, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave": (_int, [_int, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),

@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TripTextInfo, TripTextOptions, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -697,6 +697,62 @@ class Vectors:
         return labels, centres, {f[0]: getattr(inf, f[0]) for f in KmeansInfo._fields_}
 
 
+    def _labels(self, y):
+        y = np.asarray(y)
+        if y.shape != (self.shape[0],):
+            raise ValueError("y must hold one label per row")
+        if y.dtype != np.uint8:
+            y = np.where((y == 0) | (y == 1), y, 255).astype(np.uint8)      # anything but 0 and 1 is refused by the library where the row is used
+        return np.ascontiguousarray(y)
+
+    def tree_fit(self, y, select=None, max_depth=0, min_samples_split=2, min_samples_leaf=1):
+        """A binary decision tree on these rows as the rule of include/dge.h (dge_tree_fit_vectors): the same bits for the same set of rows, labels and limits.
+        y: one label, 0 or 1, per row.  select: one entry per row, non-zero = take the row (default: every present row).
+        -> (tree: dict of feature int32, threshold float64, left int32, count int64, pos int64, one entry per node; info: the fields of struct dge_tree_info)."""
+        n = self.shape[0]
+        y = self._labels(y)
+        if select is not None:
+            select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+            if select.shape != (n,):
+                raise ValueError("select must hold one entry per row")
+        cfg = TreeCfg(int(max_depth), int(min_samples_split), int(min_samples_leaf), 0)
+        cap = max(2 * n - 1, 1)
+        feature = np.empty(cap, np.int32); threshold = np.empty(cap, np.float64); left = np.empty(cap, np.int32)
+        count = np.empty(cap, np.int64); pos = np.empty(cap, np.int64); inf = TreeInfo()
+        check(lib.dge_tree_fit_vectors(self._h, _ptr(y), _ptr(select), C.byref(cfg), cap, _ptr(feature), _ptr(threshold), _ptr(left), _ptr(count), _ptr(pos), C.byref(inf)))
+        m = inf.n_nodes
+        tree = dict(feature=feature[:m].copy(), threshold=threshold[:m].copy(), left=left[:m].copy(), count=count[:m].copy(), pos=pos[:m].copy())
+        return tree, {f[0]: getattr(inf, f[0]) for f in TreeInfo._fields_}
+
+    def tree_predict(self, tree):
+        """The leaf vote of `tree` (the dict tree_fit gives) for every row (dge_tree_predict_vectors) -> uint8 [rows], 255 on an absent row."""
+        feature = np.ascontiguousarray(tree["feature"], np.int32); threshold = np.ascontiguousarray(tree["threshold"], np.float64)
+        left = np.ascontiguousarray(tree["left"], np.int32); count = np.ascontiguousarray(tree["count"], np.int64); pos = np.ascontiguousarray(tree["pos"], np.int64)
+        m = len(feature)
+        if not (feature.shape == threshold.shape == left.shape == count.shape == pos.shape == (m,)):
+            raise ValueError("the five arrays of a tree must be one-dimensional and of one length")
+        out = np.empty(self.shape[0], np.uint8)
+        check(lib.dge_tree_predict_vectors(self._h, m, _ptr(feature), _ptr(threshold), _ptr(left), _ptr(count), _ptr(pos), _ptr(out)))
+        return out
+
+    def tree_cv(self, y, fold, n_folds, max_depth=0, min_samples_split=2, min_samples_leaf=1):
+        """Cross-validated accuracy of the tree of tree_fit (dge_tree_cv_vectors): tree t trains on the present rows with fold != t and is tested on those with
+        fold == t; fold -1 takes a row out.  -> dict(scores float64 [n_folds], NaN for a fold without test rows; mean over the others; correct, tested int64;
+        n_nodes, depth int32; info: the fields of struct dge_tree_info)."""
+        n = self.shape[0]
+        y = self._labels(y)
+        fold = np.ascontiguousarray(fold, np.int32)
+        if fold.shape != (n,):
+            raise ValueError("fold must hold one entry per row")
+        F = int(n_folds)
+        cfg = TreeCfg(int(max_depth), int(min_samples_split), int(min_samples_leaf), 0)
+        correct = np.zeros(max(F, 0), np.int64); tested = np.zeros(max(F, 0), np.int64); nodes = np.zeros(max(F, 0), np.int32); depth = np.zeros(max(F, 0), np.int32)
+        inf = TreeInfo()
+        check(lib.dge_tree_cv_vectors(self._h, _ptr(y), _ptr(fold), F, C.byref(cfg), _ptr(correct), _ptr(tested), _ptr(nodes), _ptr(depth), C.byref(inf)))
+        from .evaluate import cv_scores
+        return dict(cv_scores(correct, tested), n_nodes=nodes, depth=depth, info={f[0]: getattr(inf, f[0]) for f in TreeInfo._fields_})
+
+
 def make_config(dim, window, n_vertices, negative=5, min_count=2, epochs=1, workers=0, alpha=0.025, min_alpha=1e-4,
                 seed=1, table_size=100_000_000, update_policy=0, use_hs=False):
     """struct dge_train_config, field by field (a ctypes view, not a mirror of DeepWalk: use_hs defaults to the plain
@@ -995,7 +1051,7 @@ def build_stamp():
     return dict(kv.split("=") for kv in lib.dge_build_stamp().decode().split())
 
 
-TUNING_KNOBS = {"hot_rows": 0, "hs_drain": 1, "force_segments": 2, "segment_shift": 3, "sorted_chunk": 4, "sorted_walks": 5, "workers": 6, "static_walks": 7, "hs_cold": 8, "hs_wave": 9, "acc_rows": 10, "acc_drain": 11, "table_runs": 12, "block_syn0_free": 13, "hs_centre": 14, "hs_hot_kb": 15, "allow_unsafe": 16, "watchdog_ms": 17, "hs_copies": 18, "small_rows": 19}      # include/dge.h: DGE_TUNE_*
+TUNING_KNOBS = {"hot_rows": 0, "hs_drain": 1, "force_segments": 2, "segment_shift": 3, "sorted_chunk": 4, "sorted_walks": 5, "workers": 6, "static_walks": 7, "hs_cold": 8, "hs_wave": 9, "acc_rows": 10, "acc_drain": 11, "table_runs": 12, "block_syn0_free": 13, "hs_centre": 14, "hs_hot_kb": 15, "allow_unsafe": 16, "watchdog_ms": 17, "hs_copies": 18, "small_rows": 19, "tree_batch": 20}      # include/dge.h: DGE_TUNE_*
 
 
 class tuning:

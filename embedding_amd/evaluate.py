@@ -3,7 +3,8 @@ ndcg_atK): ctypes views of dge_knn_cosine / dge_ndcg_at_k.  Used as the statisti
 Hogwild / multi-GPU) on one slice; and the reference's second figure, clusteringAccuracy (:539-571), on a k-means that is a fully specified rule
 (include/dge.h: dge_kmeans_vectors, dge_cluster_accuracy) instead of scikit-learn's randomised one; and the figures' "MF" baseline, NMF of a slice's flow matrix
 (P/matrixFactorization_tract.py:26-45), likewise a rule (dge_nmf_coo, dge_nmf_flows) instead of nimfa's randomised runs; and their "LINE" baseline
-(P/flowFeatureGeneration_tract.py:54-73), a rule as well (dge_line_coo, dge_line_flows) instead of a third-party tool's racing threads.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
+(P/flowFeatureGeneration_tract.py:54-73), a rule as well (dge_line_coo, dge_line_flows) instead of a third-party tool's racing threads; and their third figure, the cross-validated accuracy of a decision
+tree on median labels (:201-232, :34-47), again a rule (dge_tree_fit, dge_tree_cv) instead of scikit-learn's randomly tie-broken one.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
 import numpy as np
 
 
@@ -178,3 +179,99 @@ def line_features(X, touched, dtype=np.float32):
     out = X.astype(dtype)
     out[touched == 0] = 0
     return out
+
+
+def cv_scores(correct, tested):
+    """Per-fold accuracies from counts: scores[t] = correct[t] / tested[t] in binary64, NaN where a fold tested nothing; mean: numpy's mean of the others (what
+    cross_val_score(..).mean() is in the reference), NaN if there is none.  -> dict(scores, mean, correct, tested)."""
+    correct = np.asarray(correct, np.int64); tested = np.asarray(tested, np.int64)
+    scores = np.full(len(tested), np.nan, np.float64)
+    ok = tested > 0
+    scores[ok] = correct[ok].astype(np.float64) / tested[ok].astype(np.float64)
+    return dict(scores=scores, mean=float(scores[ok].mean()) if ok.any() else float("nan"), correct=correct, tested=tested)
+
+
+def median_labels(counts):
+    """generatePOIlabel_helper of the reference (P/embeddingEvaluation_tract.py:34-47) on integer counts, decided in integers: label 1 iff val >= median, and the
+    flag median >= 1 (the reference keeps a label only where it holds).  -> (labels uint8 [n], flag)."""
+    c = np.asarray(counts)
+    if c.ndim != 1 or len(c) == 0 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError("counts must be a non-empty one-dimensional array of integers")
+    s = sorted(int(v) for v in c)
+    twice = 2 * s[len(s) // 2] if len(s) % 2 else s[len(s) // 2 - 1] + s[len(s) // 2]       # twice the median, an integer
+    return np.array([1 if 2 * int(v) >= twice else 0 for v in c], np.uint8), twice >= 2
+
+
+def stratified_folds(y, n_folds, select=None):
+    """The folds of the tree's cross-validation as a rule: the j-th used row of its class, in row order, gets fold j mod n_folds; a row `select` leaves out gets -1.
+    -> int32 [n]."""
+    y = np.asarray(y)
+    F = int(n_folds)
+    if y.ndim != 1 or F < 1:
+        raise ValueError("y must be one-dimensional and n_folds at least 1")
+    use = np.ones(len(y), bool) if select is None else np.asarray(select) != 0
+    if use.shape != y.shape:
+        raise ValueError("select must hold one entry per row")
+    fold = np.full(len(y), -1, np.int32)
+    for cls in np.unique(y[use]):
+        idx = np.flatnonzero(use & (y == cls))
+        fold[idx] = np.arange(len(idx)) % F
+    return fold
+
+
+def _tree_args(features, y):
+    f = np.ascontiguousarray(features, np.float32)
+    if f.ndim != 2:
+        raise ValueError("features must be [n x dim]")
+    y = np.asarray(y)
+    if y.shape != (len(f),):
+        raise ValueError("y must hold one label per row")
+    if y.dtype != np.uint8:
+        y = np.where((y == 0) | (y == 1), y, 255).astype(np.uint8)
+    return f, np.ascontiguousarray(y)
+
+
+def tree_fit_gpu(features, y, select=None, max_depth=0, min_samples_split=2, min_samples_leaf=1, device=0):
+    """A binary decision tree on host rows [n x dim] with labels y in {0, 1}, on the device as the rule of include/dge.h (dge_tree_fit).
+    -> (tree: dict of feature, threshold, left, count, pos; info: the fields of struct dge_tree_info)."""
+    import ctypes as C
+    from ._native import TreeCfg, TreeInfo, check, lib
+    f, y = _tree_args(features, y)
+    n, dim = f.shape
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    if select is not None:
+        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+        if select.shape != (n,):
+            raise ValueError("select must hold one entry per row")
+    cfg = TreeCfg(int(max_depth), int(min_samples_split), int(min_samples_leaf), 0)
+    cap = max(2 * n - 1, 1)
+    feature = np.empty(cap, np.int32); threshold = np.empty(cap, np.float64); left = np.empty(cap, np.int32); count = np.empty(cap, np.int64); pos = np.empty(cap, np.int64)
+    inf = TreeInfo()
+    check(lib.dge_tree_fit(int(device), p(f), n, dim, p(y), p(select), C.byref(cfg), cap, p(feature), p(threshold), p(left), p(count), p(pos), C.byref(inf)))
+    m = inf.n_nodes
+    tree = dict(feature=feature[:m].copy(), threshold=threshold[:m].copy(), left=left[:m].copy(), count=count[:m].copy(), pos=pos[:m].copy())
+    return tree, {fl[0]: getattr(inf, fl[0]) for fl in TreeInfo._fields_}
+
+
+def tree_cv_gpu(features, y, n_folds=10, fold=None, select=None, max_depth=0, min_samples_split=2, min_samples_leaf=1, device=0):
+    """cross_val_score(DecisionTreeClassifier(), features, y, cv=n_folds) of the reference (P/embeddingEvaluation_tract.py:224-225) as the rule of include/dge.h
+    (dge_tree_cv).  fold: one fold number per row, -1 = leave the row out (default: stratified_folds(y, n_folds, select)).
+    -> dict(scores, mean, correct, tested, n_nodes, depth, info)."""
+    import ctypes as C
+    from ._native import TreeCfg, TreeInfo, check, lib
+    f, y = _tree_args(features, y)
+    n, dim = f.shape
+    F = int(n_folds)
+    if fold is None:
+        fold = stratified_folds(y, F, select)
+    elif select is not None:
+        raise ValueError("give fold or select, not both: fold -1 leaves a row out")
+    fold = np.ascontiguousarray(fold, np.int32)
+    if fold.shape != (n,):
+        raise ValueError("fold must hold one entry per row")
+    p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    cfg = TreeCfg(int(max_depth), int(min_samples_split), int(min_samples_leaf), 0)
+    correct = np.zeros(max(F, 0), np.int64); tested = np.zeros(max(F, 0), np.int64); nodes = np.zeros(max(F, 0), np.int32); depth = np.zeros(max(F, 0), np.int32)
+    inf = TreeInfo()
+    check(lib.dge_tree_cv(int(device), p(f), n, dim, p(y), p(fold), F, C.byref(cfg), p(correct), p(tested), p(nodes), p(depth), C.byref(inf)))
+    return dict(cv_scores(correct, tested), n_nodes=nodes, depth=depth, info={fl[0]: getattr(inf, fl[0]) for fl in TreeInfo._fields_})

@@ -1022,6 +1022,77 @@ int  dge_line_flows(const dge_flows* f, int32_t T, int32_t mode, int32_t slot, c
                     int64_t* region_index, dge_line_info* info);
 
 /* ------------------------------------------------------------------------------------------------
+ * Decision-tree classification accuracy (new; additions only, DGE_VERSION unchanged): the reference's third figure of merit, evalute_by_binary_classification
+ * (P/embeddingEvaluation_tract.py:201-232; labels by generatePOIlabel_helper, :34-47) and P/binaryClassification_CA.py:33-58: for every label, slice and method
+ * cross_val_score(tree.DecisionTreeClassifier(), features, L, cv=10).  scikit-learn's tree breaks equal splits by a random permutation of the features: two of
+ * its runs do not agree.  Here a binary CART classifier and its F-fold cross-validated accuracy are a RULE (csrc/tree.hip; the per-element pieces and the one
+ * comparator: csrc/tree_rule.h); the result is a pure function of the used rows AS A SET, their labels, the fold numbers and the three limits.  Nothing depends
+ * on the order of the rows, launch geometry, concurrency or timing: every comparison that chooses a split is made on integers.  tests/tree_ref.py is this text
+ * in Python.
+ *   - ROWS.  Resident float32 rows [rows x dim], 1 <= dim <= 4096, one present byte per row, and a host label y[i] in {0, 1} per row.  A row is USED if it is
+ *     present and, where a `select` mask is given, selected (non-zero byte); in a cross-validation, if it is present and its fold is not -1.  Values compare as
+ *     numbers: -0.0 equals +0.0.  A value that is not finite in a used row: DGE_ERR_ARG naming the least (row, column); a label other than 0 or 1 on a used
+ *     row: DGE_ERR_ARG naming the row; rows that are not used may hold anything.  At most 2^20 rows may train one tree, more is DGE_ERR_RANGE: the bound makes
+ *     the cross products below fit 128 bits.
+ *   - A NODE holds a set of training rows: n of them, p with label 1, at depth d (the root: depth 0).  It is a LEAF if p == 0, or p == n, or
+ *     n < min_samples_split, or max_depth > 0 and d == max_depth, or it has no valid candidate.  A split that gains nothing is still taken (scikit-learn with
+ *     min_impurity_decrease = 0 does the same).
+ *   - CANDIDATES.  For feature f, every pair of consecutive distinct values a < b among the node's rows: the rows with value <= a go left, nL of them, pL with
+ *     label 1; nR = n - nL, pR = p - pL.  A candidate is valid if nL >= min_samples_leaf and nR >= min_samples_leaf.
+ *   - SCORE.  S = (pL^2 + qL^2) / nL + (pR^2 + qR^2) / nR with q = n - p on each side (the greatest S is the least weighted Gini impurity).  The greatest S
+ *     wins.  Scores are compared exactly, as rationals: N = (pL^2 + qL^2) nR + (pR^2 + qR^2) nL, Dn = nL nR, and N1 Dn2 against N2 Dn1 in 128-bit integers
+ *     (N <= 2^58, Dn <= 2^38).  Among equal scores the least feature index wins, then the least a.  That order is total: any reduction tree gives the same winner.
+ *   - THRESHOLD.  m = RN(RN((double)a + (double)b) * 0.5), the only floating-point operations of the rule.  At prediction x goes left iff (double)x <= m.
+ *     a <= m < b always holds, so training and prediction send every row the same way: 2a <= RN(a + b) <= 2b because rounding is monotone and 2a, 2b are
+ *     binary64 values; halving is exact (a non-zero sum of two float32 values is no binary64 subnormal); and m = b would need b - a <= half a binary64 ulp of
+ *     2b, while two distinct float32 values are a float32 step apart.
+ *   - LEAF VOTE.  1 iff 2p > n; a tie gives 0.
+ *   - NODE NUMBERS.  The root is node 0.  The levels are processed in turn and a level's nodes in the order of their numbers; a node that splits receives the
+ *     next two numbers, left then right: right = left + 1.  The tree is five arrays of n_nodes: feature int32 (-1 in a leaf), threshold double (0 in a leaf),
+ *     left int32 (-1 in a leaf), count int64 (n), pos int64 (p).
+ *   - CROSS-VALIDATION.  fold[i] in -1 .. F-1, 1 <= F <= 64 (anything else: DGE_ERR_ARG); -1 takes the row out.  Tree t trains on the used rows with fold != t
+ *     and is tested on the used rows with fold == t: correct[t] of tested[t] rows get their label, and n_nodes[t], depth[t] describe the tree.  A fold without
+ *     training rows: DGE_ERR_ARG naming it.  A fold without test rows reports 0 of 0.  The folds are the caller's; embedding_amd.evaluate.stratified_folds is the
+ *     rule the Python view offers (the j-th used row of its class, in row order, gets fold j mod F).
+ *   - NOT scikit-learn: ties are broken by the rule above, not by a random order of the features; binary labels only; no sample weights; the folds are a rule
+ *     of our own, not StratifiedKFold's.  (scikit-learn also thresholds at the float32 midpoint where ours is the binary64 one; both lie in [a, b).)
+ *   - Null and negative arguments and limits outside max_depth >= 0, min_samples_split >= 2, min_samples_leaf >= 1: DGE_ERR_ARG before a device is looked for.
+ *     Device memory that does not suffice: DGE_ERR_CAP.  The trees of a cross-validation grow together where the device's free memory holds their lists
+ *     (about 23 bytes x dim x rows a tree), else in batches, one after another (DGE_TUNE_TREE_BATCH sets the batch by hand); the result is the same.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_tree_cfg {
+    int32_t max_depth;           /* 0 = no limit                                                             */
+    int32_t min_samples_split;   /* default 2                                                                */
+    int32_t min_samples_leaf;    /* default 1                                                                */
+    int32_t reserved;
+} dge_tree_cfg;                  /* 16 bytes */
+typedef struct dge_tree_info {
+    int64_t rows;              /* the used rows                                                            */
+    int64_t n_nodes;           /* of all trees of the call                                                 */
+    int32_t depth;             /* the deepest tree's                                                       */
+    int32_t levels;            /* level passes, summed over the batches                                    */
+    int32_t trees;
+    int32_t batches;           /* 1: all trees grew together                                               */
+    double  kernel_ms;         /* HIP-event time from the first kernel of the call to its last             */
+} dge_tree_info;               /* 40 bytes */
+/* y: host uint8[rows]; select, cfg (NULL: the defaults) and info may be NULL; the five arrays: host, `cap` entries each.  A tree of more than cap nodes:
+   DGE_ERR_CAP with info->n_nodes set (2 x used rows - 1 always suffices) */
+int  dge_tree_fit_vectors(const dge_vectors* v, const uint8_t* y, const uint8_t* select, const dge_tree_cfg* cfg, int64_t cap, int32_t* feature, double* threshold,
+                          int32_t* left, int64_t* count, int64_t* pos, dge_tree_info* info);
+/* out_labels: host uint8[rows], the leaf vote of every present row, 255 on an absent one.  A malformed tree — an inner node whose feature is outside the rows'
+   columns or whose children are not behind it and inside the tree — is DGE_ERR_ARG; nothing is read out of bounds */
+int  dge_tree_predict_vectors(const dge_vectors* v, int64_t n_nodes, const int32_t* feature, const double* threshold, const int32_t* left, const int64_t* count,
+                              const int64_t* pos, uint8_t* out_labels);
+/* y: host uint8[rows], fold: host int32[rows]; correct, tested: host int64[n_folds]; n_nodes, depth: host int32[n_folds], may be NULL, as cfg and info */
+int  dge_tree_cv_vectors(const dge_vectors* v, const uint8_t* y, const int32_t* fold, int32_t n_folds, const dge_tree_cfg* cfg, int64_t* correct, int64_t* tested,
+                         int32_t* n_nodes, int32_t* depth, dge_tree_info* info);
+/* the same on host rows float32 [n_rows x dim], every row present (through dge_vectors_from_host) */
+int  dge_tree_fit(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* y, const uint8_t* select, const dge_tree_cfg* cfg, int64_t cap,
+                  int32_t* feature, double* threshold, int32_t* left, int64_t* count, int64_t* pos, dge_tree_info* info);
+int  dge_tree_cv(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* y, const int32_t* fold, int32_t n_folds, const dge_tree_cfg* cfg,
+                 int64_t* correct, int64_t* tested, int32_t* n_nodes, int32_t* depth, dge_tree_info* info);
+
+/* ------------------------------------------------------------------------------------------------
  * Ablation / test knobs of the trainer (process-wide relaxed atomics; nothing in a normal run sets them).  value < 0 puts
  * a knob back to the library's own rule.
  * ---------------------------------------------------------------------------------------------- */
@@ -1047,7 +1118,8 @@ enum {
     DGE_TUNE_WATCHDOG_MS = 17,    /* the lock kernels' watchdog: a worker still waiting for a row lock after this many milliseconds of the launch gives up (dge_model_stats then returns DGE_ERR_STATE); 0 = no watchdog; default: 5 s + 100 x the launch's bytes at the 8 TB/s roofline */
     DGE_TUNE_HS_COPIES = 18,      /* k_sgns_train_hsw, copies form: the root's number of copies (a node's copies = ceil(its share of the paths x value), at most 16); default 16 */
     DGE_TUNE_SMALL_ROWS = 19,     /* rows of 17 .. 32 floats under the atomics policy: 1 = k_sgns_train_small (32 lanes a worker, a row = one request), 0 = k_sgns_train's 16-lane groups; default: the small-row kernel wherever it applies (v106) */
-    DGE_TUNE_COUNT = 20
+    DGE_TUNE_TREE_BATCH = 20,     /* dge_tree_cv*: at most this many trees grow together (1: one after another); default: as many as half the free device memory holds */
+    DGE_TUNE_COUNT = 21
 };
 int  dge_set_tuning(int32_t knob, int64_t value);
 int  dge_get_tuning(int32_t knob, int64_t* value);   /* -1 = the library's own rule */
