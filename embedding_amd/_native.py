@@ -140,6 +140,22 @@ class TreeInfo(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class HourWindow(C.Structure):
+    """struct dge_hour_window (include/dge.h): the hours start, start + 1, .., start + hours - 1, each mod 24."""
+    _fields_ = [("start", C.c_int32), ("hours", C.c_int32)]
+
+
+class TripletRule(C.Structure):
+    """struct dge_triplet_rule (include/dge.h): five windows, two minima and the ratio of the triplet search."""
+    _fields_ = [("A", HourWindow), ("B", HourWindow), ("C", HourWindow), ("D", HourWindow), ("E", HourWindow), ("min_a", C.c_int64), ("min_b", C.c_int64),
+                ("ratio", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TripletInfo(C.Structure):
+    """struct dge_triplet_info (include/dge.h) — what dge_flows_triplets reports."""
+    _fields_ = [("pairs_12", C.c_int64), ("pairs_23", C.c_int64), ("pairs_31", C.c_int64), ("candidates", C.c_int64), ("triplets", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
 DGE_NMF_DIVERGENCE, DGE_NMF_EUCLIDEAN = 0, 1
 DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
@@ -185,6 +201,12 @@ SIGNATURES = {
     "dge_flows_slot_edges": (_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "dge_flows_free": (None, [_vp]),
     "dge_graph_add_flows": (_int, [_vp, _vp, _i32, _i32, _vp, _P(OdInfo)]),
+    "dge_flows_add_entries": (_int, [_vp, _vp, _vp, _vp, _vp, _i64]),
+    "dge_flows_window_edges": (_int, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
+    "dge_graph_add_flow_windows": (_int, [_vp, _vp, _vp, _i32, _vp, _P(OdInfo)]),
+    "dge_triplet_rule_default": (_int, [_P(TripletRule)]),
+    "dge_triplet_rule_check": (_int, [_P(TripletRule), _vp, _P(_i32)]),
+    "dge_flows_triplets": (_int, [_vp, _P(TripletRule), _vp, _vp, _vp, _i64, _P(_i64), _P(TripletInfo)]),
     "dge_regions_centroids": (_int, [_vp, _vp, _i64, _P(_i64)]),
     "dge_graph_add_spatial": (_int, [_vp, _vp, _i32, _dbl, _vp, _P(SpatialInfo)]),
     "dge_graph_add_spatial_points": (_int, [_vp, _vp, _vp, _i64, _i32, _dbl, _vp, _P(SpatialInfo)]),

@@ -26,40 +26,16 @@
 // dge_graph_add_flows hands the slot edges to od_commit.h — the commit path of od_read.hip.
 //
 // Coherence: no protocol.  Every array is written by one kernel and read by later ones on the same stream.
-#include <algorithm>
-#include <rocprim/device/device_reduce_by_key.hpp>
-#include <rocprim/iterator/constant_iterator.hpp>
-
-#include "coo_entries.h"
 #include "od_commit.h"
 #include "pip_exact.h"
+#include "trip_flows.h"                          // the table itself and the passes shared with flow_windows.hip
 
 constexpr int TRIP_TILE = 1024;                  // segments one LDS tile holds: 32 KiB of the CU's 160
 constexpr int64_t TRIP_CHUNK = (int64_t)1 << 24; // points (or trips) taken at a time
 constexpr int32_t TRIP_MAX_GRID = 4096;
-enum { TC_LOCATED = 0, TC_BOUNDARY, TC_MULTI, TC_OUTSIDE, TC_EXACT, TC_MAPPED, TC_BAD, TC_NO_START, TC_NO_END, TC_VALID, TC_N };
-
-struct dge_flows {
-    dge_regions* regions = nullptr;
-    uint64_t* d_key = nullptr;                   // ascending
-    int64_t* d_cnt = nullptr;
-    int64_t n = 0;
-    struct dge_flows_info info = {};
-};
 
 // ------------------------------------------------------------------------------------------ kernels
 struct TripIndex { double x0, y0, x1, y1, invx, invy; int32_t G; int32_t has; };
-
-template <int N>
-__device__ __forceinline__ void trip_count(unsigned long long (&v)[N], const int (&which)[N], unsigned long long* counters) {
-    typedef hipcub::BlockReduce<unsigned long long, SEQ_BLOCK> Reduce;
-    __shared__ typename Reduce::TempStorage tmp;
-    for (int k = 0; k < N; k++) {
-        const unsigned long long sum = Reduce(tmp).Sum(v[k]);
-        if (threadIdx.x == 0 && sum) atomicAdd(counters + which[k], sum);
-        __syncthreads();
-    }
-}
 
 __global__ void __launch_bounds__(SEQ_BLOCK) k_trip_keys(const double* xy, int64_t n, TripIndex ix, uint32_t* key, uint32_t* idx, int32_t* region, unsigned long long* counters) {
     const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
@@ -181,19 +157,6 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_slot_items(const uint64_t* key, c
     trip_count(v, which, counters);
 }
 
-__global__ void __launch_bounds__(SEQ_BLOCK) k_slot_decode(const uint64_t* key, const int64_t* w, int64_t n, uint64_t R, const int64_t* id_by_rank, int32_t* slot, int64_t* src_id,
-                                                           int64_t* dst_id, uint64_t* w_bits, int64_t* iota) {
-    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (i == 0) iota[n] = n;
-    if (i >= n) return;
-    const uint64_t k = key[i];
-    slot[i] = (int32_t)(k / R / R);
-    src_id[i] = id_by_rank[(k / R) % R];
-    dst_id[i] = id_by_rank[k % R];
-    w_bits[i] = (uint64_t)__double_as_longlong((double)w[i]);     // round to nearest even: the binary64 nearest the decimal, as the .od reader gives
-    iota[i] = i;
-}
-
 // the slot's edges inside a selection as matrix entries: map[rank] = the compact index of the region of that rank, or -1.  The positions come from a counter:
 // the order of the entries is of no account to their reader, which sorts them
 __global__ void __launch_bounds__(SEQ_BLOCK) k_slot_coo(const uint64_t* key, const int64_t* w, int64_t n, uint64_t R, int32_t slot, const int32_t* map, int32_t* row, int32_t* col,
@@ -210,12 +173,6 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_slot_coo(const uint64_t* key, con
 
 // ------------------------------------------------------------------------------------------ host side
 namespace {
-
-int trip_open(SeqRun& R, int device, const char* what) {
-    R.device = device; R.what = what;
-    DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-    return DGE_OK;
-}
 
 template <typename T>
 int trip_upload(SeqRun& R, T** dst, const T* src, int64_t n, const char* what) {
@@ -262,32 +219,6 @@ int trip_locate(SeqRun& R, const dge_regions* rg, const double* d_xy, int64_t n,
     return DGE_OK;
 }
 
-// keys ascending with duplicates, vals: -> distinct keys with summed values.  vals == nullptr: every value is 1.  The outputs are allocated here.
-int trip_reduce(SeqRun& R, const uint64_t* keys, const int64_t* vals, int64_t n, dge_tmp<uint64_t>& ukey, dge_tmp<int64_t>& usum, int64_t* n_out) {
-    *n_out = 0;
-    SEQ_TRY(seq_alloc(R, ukey, n, "the distinct keys"));
-    SEQ_TRY(seq_alloc(R, usum, n, "the summed counts"));
-    if (n == 0) return DGE_OK;
-    dge_tmp<int64_t> count;
-    SEQ_TRY(seq_alloc(R, count, 1, "the number of keys"));
-    SeqScratch tmp{R, "the reduction's scratch", true};
-    auto reduce = [&](auto values) {
-        return dge_two_pass(tmp, [&](void* t, size_t& bytes) {
-            return rocprim::reduce_by_key(t, bytes, keys, values, (size_t)n, ukey.p, usum.p, count.p, rocprim::plus<int64_t>(), rocprim::equal_to<uint64_t>(), R.stream);
-        }, R.stream, false);
-    };
-    SEQ_TRY(vals ? reduce(vals) : reduce(rocprim::constant_iterator<int64_t>(1)));
-    SEQ_TRY(seq_kernels_end(R));
-    return seq_read_back(R, n_out, count.p, 8);
-}
-
-int trip_sort_pairs(SeqRun& R, const uint64_t* k_in, uint64_t* k_out, const int64_t* v_in, int64_t* v_out, int64_t n, int end_bit) {
-    if (n == 0) return DGE_OK;
-    SeqScratch tmp{R, "the sort's scratch", true};
-    SEQ_TRY(v_in ? dge_sort_pairs(tmp, k_in, k_out, v_in, v_out, n, end_bit, R.stream, false) : dge_sort_keys(tmp, k_in, k_out, n, end_bit, R.stream, false));
-    return seq_kernels_end(R);
-}
-
 int slot_check(int32_t T, int32_t mode, const char* who) {
     if (mode == DGE_SLOTS_EVEN) { if (T < 1 || T > 24 || 24 % T != 0) DGE_FAIL(DGE_ERR_ARG, "%s: DGE_SLOTS_EVEN needs a T that divides 24, not %d", who, T); }
     else if (mode == DGE_SLOTS_AS_TRACTS) { if (T < 1 || T > 24) DGE_FAIL(DGE_ERR_ARG, "%s: DGE_SLOTS_AS_TRACTS needs 1 <= T <= 24, not %d", who, T); }
@@ -319,20 +250,6 @@ int trip_slot_edges(SeqRun& R, const dge_flows* f, int32_t T, int32_t mode, dge_
     unsigned long long valid = 0;
     SEQ_TRY(seq_read_back(R, &valid, counters.p + TC_VALID, 8));
     return trip_reduce(R, skey.p, sw.p, (int64_t)valid, okey, ow, n_out);
-}
-
-struct SlotArrays { dge_tmp<int32_t> slot; dge_tmp<int64_t> src_id, dst_id, iota; dge_tmp<uint64_t> w_bits; };
-
-int trip_slot_decode(SeqRun& R, const dge_flows* f, const uint64_t* okey, const int64_t* ow, int64_t n, SlotArrays& A) {
-    SEQ_TRY(seq_alloc(R, A.slot, n, "the edges' slots"));
-    SEQ_TRY(seq_alloc(R, A.src_id, n, "the edges' sources"));
-    SEQ_TRY(seq_alloc(R, A.dst_id, n, "the edges' destinations"));
-    SEQ_TRY(seq_alloc(R, A.w_bits, n, "the edges' weights"));
-    SEQ_TRY(seq_alloc(R, A.iota, n + 1, "the edges' numbers"));
-    SEQ_TRY(seq_kernels_begin(R));
-    hipLaunchKernelGGL(k_slot_decode, dim3(seq_grid(n + 1)), dim3(SEQ_BLOCK), 0, R.stream, okey, ow, n, (uint64_t)std::max<int64_t>(f->regions->R, 1), f->regions->d_id_by_rank, A.slot.p, A.src_id.p,
-                       A.dst_id.p, A.w_bits.p, A.iota.p);
-    return seq_kernels_end(R);
 }
 
 void locate_counters(const unsigned long long* c, int64_t points, double ms, dge_locate_info* info) {
@@ -420,26 +337,12 @@ int flows_add(dge_flows* f, const double* sxy, const double* exy, const int32_t*
         const int64_t fresh = (int64_t)(mapped - before);
         before = mapped;
         // ---- the chunk's run lengths, then the merge with the table: concatenate, sort, reduce by key
-        dge_tmp<uint64_t> ukey, ckey, cskey, nkey;
-        dge_tmp<int64_t> ucnt, ccnt, cscnt, ncnt;
+        dge_tmp<uint64_t> ukey, nkey;
+        dge_tmp<int64_t> ucnt, ncnt;
         int64_t u = 0, nn = 0;
         SEQ_TRY(trip_reduce(R, skey.p, nullptr, fresh, ukey, ucnt, &u));
         if (u == 0) continue;
-        const uint64_t* old_key = own_table ? tkey.p : f->d_key;
-        const int64_t* old_cnt = own_table ? tcnt.p : f->d_cnt;
-        SEQ_TRY(seq_alloc(R, ckey, tn + u, "the joined tables"));
-        SEQ_TRY(seq_alloc(R, ccnt, tn + u, "the joined tables' counts"));
-        SEQ_TRY(seq_alloc(R, cskey, tn + u, "the joined tables, sorted"));
-        SEQ_TRY(seq_alloc(R, cscnt, tn + u, "the joined tables' counts, sorted"));
-        if (tn) {
-            DGE_HIP(hipMemcpyAsync(ckey.p, old_key, (size_t)tn * 8, hipMemcpyDeviceToDevice, R.stream));
-            DGE_HIP(hipMemcpyAsync(ccnt.p, old_cnt, (size_t)tn * 8, hipMemcpyDeviceToDevice, R.stream));
-        }
-        DGE_HIP(hipMemcpyAsync(ckey.p + tn, ukey.p, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
-        DGE_HIP(hipMemcpyAsync(ccnt.p + tn, ucnt.p, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
-        SEQ_TRY(trip_sort_pairs(R, ckey.p, cskey.p, ccnt.p, cscnt.p, tn + u, dge_bits(24 * Ru * Ru)));
-        SEQ_TRY(trip_reduce(R, cskey.p, cscnt.p, tn + u, nkey, ncnt, &nn));
-        DGE_HIP(hipStreamSynchronize(R.stream));
+        SEQ_TRY(trip_join(R, own_table ? tkey.p : f->d_key, own_table ? tcnt.p : f->d_cnt, tn, ukey.p, ucnt.p, u, Ru, nkey, ncnt, &nn));
         if (tkey.p) { (void)hipFree(tkey.p); (void)hipFree(tcnt.p); }
         tkey.p = nkey.release(); tcnt.p = ncnt.release(); tn = nn; own_table = true;
     }
@@ -609,24 +512,10 @@ int dge_flows_merge(dge_flows* f, const dge_flows* part) {
     if (part->n > 0) {
         SEQ_TRY(dge_require_device(f->regions->device));
         SEQ_TRY(trip_open(R, f->regions->device, who));
-        const int64_t tn = f->n, u = part->n;
-        const uint64_t Ru = (uint64_t)std::max<int64_t>(f->regions->R, 1);
-        dge_tmp<uint64_t> ckey, cskey, nkey;
-        dge_tmp<int64_t> ccnt, cscnt, ncnt;
+        dge_tmp<uint64_t> nkey;
+        dge_tmp<int64_t> ncnt;
         int64_t nn = 0;
-        SEQ_TRY(seq_alloc(R, ckey, tn + u, "the joined tables"));
-        SEQ_TRY(seq_alloc(R, ccnt, tn + u, "the joined tables' counts"));
-        SEQ_TRY(seq_alloc(R, cskey, tn + u, "the joined tables, sorted"));
-        SEQ_TRY(seq_alloc(R, cscnt, tn + u, "the joined tables' counts, sorted"));
-        if (tn) {
-            DGE_HIP(hipMemcpyAsync(ckey.p, f->d_key, (size_t)tn * 8, hipMemcpyDeviceToDevice, R.stream));
-            DGE_HIP(hipMemcpyAsync(ccnt.p, f->d_cnt, (size_t)tn * 8, hipMemcpyDeviceToDevice, R.stream));
-        }
-        DGE_HIP(hipMemcpyAsync(ckey.p + tn, part->d_key, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
-        DGE_HIP(hipMemcpyAsync(ccnt.p + tn, part->d_cnt, (size_t)u * 8, hipMemcpyDeviceToDevice, R.stream));
-        SEQ_TRY(trip_sort_pairs(R, ckey.p, cskey.p, ccnt.p, cscnt.p, tn + u, dge_bits(24 * Ru * Ru)));
-        SEQ_TRY(trip_reduce(R, cskey.p, cscnt.p, tn + u, nkey, ncnt, &nn));
-        DGE_HIP(hipStreamSynchronize(R.stream));
+        SEQ_TRY(trip_join(R, f->d_key, f->d_cnt, f->n, part->d_key, part->d_cnt, part->n, (uint64_t)std::max<int64_t>(f->regions->R, 1), nkey, ncnt, &nn));
         // nothing can fail from here on
         dge_dev_free(f->d_key); dge_dev_free(f->d_cnt);
         f->d_key = nkey.release(); f->d_cnt = ncnt.release(); f->n = nn;

@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -76,6 +76,23 @@ class DeviceGraph:
         g = cls(flows.regions.device)
         inf = OdInfo()
         check(lib.dge_graph_add_flows(g._h, flows._h, int(T), int(mode), names._h if names is not None else None, C.byref(inf)))
+        return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
+
+    @classmethod
+    def from_flow_windows(cls, flows, windows, names=True):
+        """A Flows table and K hour windows [(start, hours), ..] -> (graph, names, info): the window edges become the layered graph on the device (include/dge.h:
+        dge_graph_add_flow_windows), exactly the graph from_od gives for the texts of flows.window_edges(windows), slice k = window k.
+        from_flow_windows(f, Flows.windows_cross_time(T)) is CrossTimeGraph.constructGraph_tract with numLayer = T (J/CrossTimeGraph.java:25-52) — the graph
+        DeepWalk trains on; from_flows(f, T, AS_TRACTS) keeps only the destinations seen in the window's first hour and is not.
+        from_flow_windows(f, Flows.windows_from_intervals(iv)) is constructGraph_CA(iv) (:68-95).  names as in from_od."""
+        if names is True:
+            names = Names()
+        elif not names and not isinstance(names, Names):
+            names = None
+        g = cls(flows.regions.device)
+        inf = OdInfo()
+        win = _windows(windows)
+        check(lib.dge_graph_add_flow_windows(g._h, flows._h, win, len(win), names._h if names is not None else None, C.byref(inf)))
         return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
 
     @classmethod
@@ -213,6 +230,12 @@ class DeviceGraph:
 
 def _info_dict(inf):
     return {f[0]: getattr(inf, f[0]) for f in inf._fields_}
+
+
+def _windows(windows):
+    """[(start, hours), ..] -> a C array of struct dge_hour_window"""
+    windows = [(int(a), int(b)) for a, b in windows]
+    return (HourWindow * len(windows))(*[HourWindow(a, b) for a, b in windows])
 
 
 def _text_args(texts):
@@ -387,6 +410,92 @@ class Flows:
         if m:
             check(lib.dge_flows_slot_edges(self._h, int(T), int(mode), _ptr(slot), _ptr(src), _ptr(dst), _ptr(w), m, C.byref(n)))
         return slot, src, dst, w
+
+    def add_entries(self, hour, src, dst, count):
+        """Table entries back in (include/dge.h: dge_flows_add_entries; replaces Tracts.deserialzeTracts, J/Tracts.java:115-125): hour int32 in 0 .. 23, src /
+        dst int32 region INDICES, count int64 >= 1 — what to_host() gave, in any order, with repeats, over any number of calls.  The table stands where
+        add_trips leaves it on `count` trips per entry."""
+        h = np.ascontiguousarray(hour, np.int32); s = np.ascontiguousarray(src, np.int32); d = np.ascontiguousarray(dst, np.int32); c = np.ascontiguousarray(count, np.int64)
+        if not (h.shape == s.shape == d.shape == c.shape and h.ndim == 1):
+            raise ValueError("hour / src / dst / count are four arrays of one length")
+        check(lib.dge_flows_add_entries(self._h, _ptr(h), _ptr(s), _ptr(d), _ptr(c), len(h)))
+
+    @staticmethod
+    def windows_cross_time(T):
+        """The windows of CrossTimeGraph.constructGraph_tract with numLayer = T (J/CrossTimeGraph.java:31-36): window h starts at hour h and holds 24 // T hours."""
+        T = int(T)
+        if not 1 <= T <= 24:
+            raise ValueError("1 <= T <= 24")
+        return [(h, 24 // T) for h in range(T)]
+
+    @staticmethod
+    def windows_from_intervals(intervals):
+        """constructGraph_CA(int[] timeIntervals) (J/CrossTimeGraph.java:68-95): window h is CommunityArea.getFlowTo(dst, iv[h], iv[h + 1]) — exclusive
+        high, wrapping past midnight (J/CommunityAreas.java:240-245): (iv[h], (iv[h + 1] - iv[h]) mod 24).  iv[h] == iv[h + 1] is an empty window, as there."""
+        iv = [int(v) for v in intervals]
+        if len(iv) < 2 or not all(0 <= v <= 23 for v in iv):
+            raise ValueError("two hours at least, each in 0 .. 23")
+        return [(lo, (hi - lo) % 24) for lo, hi in zip(iv[:-1], iv[1:])]
+
+    @staticmethod
+    def windows_ca_default(num_layer):
+        """The windows constructGraph_CA() gets from the interval array it builds, as written (J/CrossTimeGraph.java:54-61), quirks kept: only every
+        (24 // numLayer)-th entry of the array is set, to (i * timeStep) % numLayer, the others stay 0.  numLayer = 24 gives the 24 one-hour windows."""
+        n = int(num_layer)
+        if not 1 <= n <= 24:
+            raise ValueError("1 <= num_layer <= 24")
+        step = 24 // n
+        iv = [0] * (n + 1)
+        for i in range(0, n + 1, step):
+            iv[i] = (i * step) % n
+        return Flows.windows_from_intervals(iv)
+
+    def window_edges(self, windows):
+        """K hour windows [(start, hours), ..] -> k int32, src id int64, dst id int64, w int64: the sums of the table over each window's hours where they are
+        > 0, ascending by (k, src id, dst id) (include/dge.h: dge_flows_window_edges).  Windows may overlap, repeat and be empty."""
+        win = _windows(windows)
+        n = C.c_int64(0)
+        rc = lib.dge_flows_window_edges(self._h, win, len(win), None, None, None, None, 0, C.byref(n))          # a size query
+        if rc not in (0, DGE_ERR_CAP):
+            check(rc)
+        m = n.value
+        k = np.empty(m, np.int32); src = np.empty(m, np.int64); dst = np.empty(m, np.int64); w = np.empty(m, np.int64)
+        if m:
+            check(lib.dge_flows_window_edges(self._h, win, len(win), _ptr(k), _ptr(src), _ptr(dst), _ptr(w), m, C.byref(n)))
+        return k, src, dst, w
+
+    @staticmethod
+    def triplet_rule(**kw):
+        """The default rule of the triplet search (the reference's constants) with the given fields replaced: A .. E as (start, hours), min_a, min_b, ratio."""
+        r = TripletRule()
+        check(lib.dge_triplet_rule_default(C.byref(r)))
+        for name, v in kw.items():
+            if name in "ABCDE" and len(name) == 1:
+                setattr(r, name, HourWindow(int(v[0]), int(v[1])))
+            elif name in ("min_a", "min_b", "ratio"):
+                setattr(r, name, int(v))
+            else:
+                raise TypeError("triplet_rule has no field %r" % name)
+        return r
+
+    def triplets(self, rule=None, return_info=False):
+        """The brute-force triplet search (include/dge.h: dge_flows_triplets; replaces Tracts.bruteForceSearchCase, J/Tracts.java:371-415) as a directed-triangle
+        listing on the device: -> int64 [n, 3], the (residence, office, night life) region ids that pass the ten conditions, ascending.  rule: None (the
+        reference's constants), a TripletRule, or a dict of the fields triplet_rule takes.  return_info: also the fields of struct dge_triplet_info."""
+        if isinstance(rule, dict):
+            rule = Flows.triplet_rule(**rule)
+        rp = C.byref(rule) if rule is not None else None
+        n = C.c_int64(0)
+        inf = TripletInfo()
+        rc = lib.dge_flows_triplets(self._h, rp, None, None, None, 0, C.byref(n), C.byref(inf))          # a size query
+        if rc not in (0, DGE_ERR_CAP):
+            check(rc)
+        m = n.value
+        a = np.empty(m, np.int64); b = np.empty(m, np.int64); c = np.empty(m, np.int64)
+        if m:
+            check(lib.dge_flows_triplets(self._h, rp, _ptr(a), _ptr(b), _ptr(c), m, C.byref(n), C.byref(inf)))
+        out = np.stack([a, b, c], 1) if m else np.empty((0, 3), np.int64)
+        return (out, _info_dict(inf)) if return_info else out
 
     def nmf(self, slot, T=8, mode=DGE_SLOTS_EVEN, select=None, **kw):
         """NMF of the flow matrix of one slot (dge_nmf_flows; the rule of include/dge.h): V[src][dst] = w over the edges slot_edges(T, mode) gives for `slot`,

@@ -247,6 +247,73 @@ void dge_flows_free(dge_flows* f);
 /* replaces outputEdgeFile followed by CrossTimeGraph.constructGraphFromOD (J/CrossTimeGraph.java:25-52): no text in between */
 int  dge_graph_add_flows(dge_graph* g, const dge_flows* f, int32_t T, int32_t mode, struct dge_names* names /* may be NULL */, dge_od_info* info /* may be NULL */);
 
+/* ---- hour windows of the flow table (new; additions only, DGE_VERSION unchanged): the reads of taxiFlows by hour interval — Tract.getFlowTo(d, lo, hi)
+ * (J/Tracts.java:477-482), CommunityArea.getFlowTo(d, lo, hi) (J/CommunityAreas.java:240-245) — and what the reference builds on them: the cross-time graph
+ * DeepWalk trains on (CrossTimeGraph.constructGraph_tract, J/CrossTimeGraph.java:25-52), the hand-picked intervals (constructGraph_CA(int[]), :68-95), the
+ * brute-force triplet search (Tracts.bruteForceSearchCase, J/Tracts.java:371-415), and the way back into the table (deserialzeTracts, J/Tracts.java:115-125)
+ * — on the device (csrc/flow_windows.hip, csrc/flow_rule.h).  Everything is integer arithmetic; the results are pure functions of the table and the arguments,
+ * whatever calls built the table, and nothing depends on timing or launch geometry.  The rule:
+ *   - An HOUR WINDOW (start, hours) holds the hours start, start+1, .., start+hours-1, each mod 24.  0 <= start <= 23, 0 <= hours <= 24; hours = 0 is an empty
+ *     window, not an error.  Tract.getFlowTo(d, lo, hi) is (lo, hi-lo+1) with hi <= 23 (inclusive high, no wrap); CommunityArea.getFlowTo(d, lo, hi) is
+ *     (lo, (hi-lo) mod 24) (exclusive high, wrapping).  W(start, hours)[s, e] is the int64 sum of c(h, s, e) over the window's hours.
+ *   - The WINDOW EDGES of a list of K windows are the tuples (k, ids[s], ids[e], w) with w = W_k[s, e] > 0, ascending by (k, src id, dst id).  Windows may
+ *     overlap, repeat and be empty.  1 <= K; K*R*R must fit 63 bits, and for a graph K*R' <= 2^31-1 as for slots: else DGE_ERR_RANGE.  constructGraph_tract
+ *     with numLayer = T is the windows (h, 24/T), h = 0 .. T-1, over ALL destinations; DGE_SLOTS_AS_TRACTS keeps only destinations seen in hour h itself, so
+ *     the two differ whenever a pair is silent in hour h and not in the rest of the window.
+ *   - dge_flows_add_entries takes host arrays: hour in 0 .. 23, region INDICES in 0 .. R-1, count >= 1, in any order, with repeats, over any number of calls.
+ *     The table stands bit for bit where dge_flows_add_trips leaves it on `count` trips per entry; info.trips and info.mapped grow by the counts added, the
+ *     other counters do not move.  A bad hour, index or count: DGE_ERR_ARG naming the least offending position.  A key's total above 2^40: DGE_ERR_RANGE.  On
+ *     any error the table is as it was.
+ *   - dge_graph_add_flow_windows leaves g exactly where dge_graph_add_od_texts leaves it when slice k's text is the lines "%d %d %d\n" % (src id, dst id, w) of
+ *     window k's edges in that order: the commit path (csrc/od_commit.h), the fresh-graph and names rules and the statuses of dge_graph_add_flows; info as there,
+ *     slices = K.
+ *   - The TRIPLET SEARCH.  A rule holds five windows A, B, C, D, E, the minima min_a, min_b (0 .. 2^40) and ratio r (1 .. 65536).  A triplet of pairwise distinct
+ *     regions (t1, t2, t3) — residence, office, night life — is kept iff all ten conditions hold (J/Tracts.java:391-400 negated), W[x,y] = W[t_x, t_y]:
+ *        1  A[1,2] > min_a        2  B[3,1] > min_b          3  B[2,3] > min_b          4  A[1,2] > r A[2,1]       5  C[1,3] > r D[1,3]
+ *        6  C[2,1] > r C[1,2]     7  C[2,3] > r D[2,3]       8  B[3,1] > r E[3,1]       9  B[3,1] > r B[3,2]      10  B[3,1] > r B[1,3]
+ *     An absent pair is 0; self flows play no part.  The conditions read THIRTEEN distinct sums; dge_triplet_rule_check takes them in the order
+ *        A12, A21, C21, C12, B31, E31, C13, D13, B13, B23, C23, D23, B32
+ *     (sums[0] .. sums[12]) and needs no device.  Conditions 1, 4, 6 belong to the pair (t1, t2), 3, 7 to (t2, t3), 2, 5, 8, 10 to (t3, t1); the ninth needs all
+ *     three.  The result is the triplets as region IDS, ascending by (id1, id2, id3): the reference's HashMap order is not an order.  dge_triplet_info: the
+ *     ordered pairs of distinct regions that pass their pair's conditions, the triangles of three such pairs over pairwise distinct regions before the ninth
+ *     condition (candidates), and the triplets.  The default rule holds the reference's constants: A = (7,3), B = (17,7), C = (17,6), D = (7,6), E = (7,7),
+ *     min_a = 30, min_b = 70, ratio = 2.
+ *   - dge_flows_window_edges and dge_flows_triplets: cap too small is DGE_ERR_CAP with *n set, cap = 0 with null outputs is a size query.  The plain values
+ *     are checked first, the handles after: null or negative arguments, a bad window and a bad rule are DGE_ERR_ARG before a device is looked for.  Out of
+ *     device memory: DGE_ERR_CAP.  R < 3, an empty table and an empty window are fine. */
+typedef struct dge_hour_window { int32_t start; int32_t hours; } dge_hour_window;      /* 8 bytes */
+typedef struct dge_triplet_rule {
+    dge_hour_window A;            /* morning:            the reference's getFlowTo(.., 7, 9)               */
+    dge_hour_window B;            /* evening and night:  (.., 17, 23)                                      */
+    dge_hour_window C;            /* evening:            (.., 17, 22)                                      */
+    dge_hour_window D;            /* day:                (.., 7, 12)                                       */
+    dge_hour_window E;            /* day, an hour more:  (.., 7, 13)                                       */
+    int64_t min_a;
+    int64_t min_b;
+    int32_t ratio;
+    int32_t reserved;             /* 0                                                                     */
+} dge_triplet_rule;               /* 64 bytes */
+typedef struct dge_triplet_info {
+    int64_t pairs_12;             /* (t1, t2), t1 != t2, that pass conditions 1, 4, 6                       */
+    int64_t pairs_23;             /* (t2, t3) that pass 3, 7                                                */
+    int64_t pairs_31;             /* (t3, t1) that pass 2, 5, 8, 10                                         */
+    int64_t candidates;           /* triangles of three such pairs, pairwise distinct, before the ninth    */
+    int64_t triplets;
+    double  kernel_ms;
+} dge_triplet_info;               /* 48 bytes */
+/* replaces Tracts.deserialzeTracts (J/Tracts.java:115-125): what dge_flows_to_host gave goes back in */
+int  dge_flows_add_entries(dge_flows* f, const int32_t* hour, const int32_t* src, const int32_t* dst, const int64_t* count, int64_t n);
+/* replaces the getFlowTo(dst, lo, hi) loops over all pairs; k: int32[cap], the others int64[cap] */
+int  dge_flows_window_edges(const dge_flows* f, const dge_hour_window* win, int32_t K, int32_t* k, int64_t* src_id, int64_t* dst_id, int64_t* w, int64_t cap, int64_t* n);
+/* replaces CrossTimeGraph.constructGraph_tract and constructGraph_CA(int[] timeIntervals) (J/CrossTimeGraph.java:25-52, 68-95) */
+int  dge_graph_add_flow_windows(dge_graph* g, const dge_flows* f, const dge_hour_window* win, int32_t K, struct dge_names* names /* may be NULL */, dge_od_info* info /* may be NULL */);
+int  dge_triplet_rule_default(dge_triplet_rule* rule);
+/* the ten conditions on thirteen given sums: *keep = 1 or 0.  No device, no table */
+int  dge_triplet_rule_check(const dge_triplet_rule* rule /* NULL: the default */, const int64_t sums[13], int32_t* keep);
+/* replaces Tracts.bruteForceSearchCase (J/Tracts.java:371-415); id1, id2, id3: int64[cap] */
+int  dge_flows_triplets(const dge_flows* f, const dge_triplet_rule* rule /* NULL: the default */, int64_t* id1, int64_t* id2, int64_t* id3, int64_t cap, int64_t* n,
+                        dge_triplet_info* info /* may be NULL */);
+
 /* ---- taxi trip text in (new; additions only, DGE_VERSION unchanged): the lines the reference reads in TaxiTrip(String line) and ShortDate
  * (J/TaxiTrip.java:39-78,199-223; the loops J/TaxiTrip.java:123-143 and J/TaxiTripIterator.java:32-62) are parsed on the device (csrc/trip_text.hip, csrc/trip_parse.h)
  * and go into a flow table without per-trip work on the host.  The rule; the result is a pure function of the bytes, the format and the header flag — nothing
