@@ -140,6 +140,11 @@ class TreeInfo(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class RidgeInfo(C.Structure):
+    """struct dge_ridge_info (include/dge.h) — what dge_ridge_loo_vectors / dge_ridge_loo report."""
+    _fields_ = [("rows", C.c_int64), ("blocks", C.c_int64), ("chunks", C.c_int64), ("min_pivot", C.c_double), ("max_leverage", C.c_double), ("kernel_ms", C.c_double)]
+
+
 class HourWindow(C.Structure):
     """struct dge_hour_window (include/dge.h): the hours start, start + 1, .., start + hours - 1, each mod 24."""
     _fields_ = [("start", C.c_int32), ("hours", C.c_int32)]
@@ -301,6 +306,9 @@ SIGNATURES = {
     "dge_tree_cv_vectors": (_int, [_vp, _vp, _vp, _i32, _P(TreeCfg), _vp, _vp, _vp, _vp, _P(TreeInfo)]),
     "dge_tree_fit": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _P(TreeCfg), _i64, _vp, _vp, _vp, _vp, _vp, _P(TreeInfo)]),
     "dge_tree_cv": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i32, _P(TreeCfg), _vp, _vp, _vp, _vp, _P(TreeInfo)]),
+    "dge_ridge_loo_vectors": (_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _P(RidgeInfo)]),
+    "dge_ridge_loo": (_int, [_int, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _P(RidgeInfo)]),
+    "dge_ridge_predict_vectors": (_int, [_vp, _vp, _i32, _vp]),
     "dge_selftest_locked_rows": (_int, [_int, _i32, _i64, _i32, C.c_uint64, _i32, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave": (_int, [_int, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),

@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
 
 
 def _ptr(a):
@@ -861,6 +861,33 @@ class Vectors:
         from .evaluate import cv_scores
         return dict(cv_scores(correct, tested), n_nodes=nodes, depth=depth, info={f[0]: getattr(inf, f[0]) for f in TreeInfo._fields_})
 
+    def ridge_loo(self, y, lambdas, select=None, want_beta=True, want_pred=True):
+        """Leave-one-out ridge regression on these rows as the rule of include/dge.h (dge_ridge_loo_vectors): the same bits for the same used rows in row order,
+        targets and penalties.  y: [rows] or [rows x n_targets]; lambdas: the penalties, each >= 0; select: one entry per row, non-zero = take the row
+        (default: every present row).  -> dict(mae, mre float64 [n_lambda x n_targets]; beta [n_lambda x n_targets x (dim + 1)], the intercept first;
+        loo_pred [n_lambda x n_targets x rows], NaN on rows not used; info: the fields of struct dge_ridge_info)."""
+        from .evaluate import _ridge_args
+        n, dim = self.shape
+        y, lam, select = _ridge_args(n, y, lambdas, select)
+        T, L = y.shape[1], len(lam)
+        mae = np.empty((L, T), np.float64); mre = np.empty((L, T), np.float64); inf = RidgeInfo()
+        beta = np.empty((L, T, dim + 1), np.float64) if want_beta else None
+        pred = np.empty((L, T, n), np.float64) if want_pred else None
+        check(lib.dge_ridge_loo_vectors(self._h, _ptr(y), T, _ptr(select), _ptr(lam), L, _ptr(mae), _ptr(mre), _ptr(beta), _ptr(pred), C.byref(inf)))
+        return dict(mae=mae, mre=mre, beta=beta, loo_pred=pred, info={f[0]: getattr(inf, f[0]) for f in RidgeInfo._fields_})
+
+    def ridge_predict(self, beta):
+        """The predictions of the models beta [.. x (dim + 1)] (what ridge_loo gives, the intercept first) for every row (dge_ridge_predict_vectors)
+        -> float64 [.. x rows], NaN on an absent row."""
+        n, dim = self.shape
+        beta = np.ascontiguousarray(beta, np.float64)
+        if beta.ndim < 1 or beta.shape[-1] != dim + 1:
+            raise ValueError("beta must be [.. x (dim + 1)] = [.. x %d], not %s" % (dim + 1, list(beta.shape)))
+        m = int(np.prod(beta.shape[:-1], dtype=np.int64))
+        out = np.empty(beta.shape[:-1] + (n,), np.float64)
+        check(lib.dge_ridge_predict_vectors(self._h, _ptr(beta), m, _ptr(out)))
+        return out
+
 
 def make_config(dim, window, n_vertices, negative=5, min_count=2, epochs=1, workers=0, alpha=0.025, min_alpha=1e-4,
                 seed=1, table_size=100_000_000, update_policy=0, use_hs=False):
@@ -1160,7 +1187,7 @@ def build_stamp():
     return dict(kv.split("=") for kv in lib.dge_build_stamp().decode().split())
 
 
-TUNING_KNOBS = {"hot_rows": 0, "hs_drain": 1, "force_segments": 2, "segment_shift": 3, "sorted_chunk": 4, "sorted_walks": 5, "workers": 6, "static_walks": 7, "hs_cold": 8, "hs_wave": 9, "acc_rows": 10, "acc_drain": 11, "table_runs": 12, "block_syn0_free": 13, "hs_centre": 14, "hs_hot_kb": 15, "allow_unsafe": 16, "watchdog_ms": 17, "hs_copies": 18, "small_rows": 19, "tree_batch": 20}      # include/dge.h: DGE_TUNE_*
+TUNING_KNOBS = {"hot_rows": 0, "hs_drain": 1, "force_segments": 2, "segment_shift": 3, "sorted_chunk": 4, "sorted_walks": 5, "workers": 6, "static_walks": 7, "hs_cold": 8, "hs_wave": 9, "acc_rows": 10, "acc_drain": 11, "table_runs": 12, "block_syn0_free": 13, "hs_centre": 14, "hs_hot_kb": 15, "allow_unsafe": 16, "watchdog_ms": 17, "hs_copies": 18, "small_rows": 19, "tree_batch": 20, "ridge_chunk": 21}      # include/dge.h: DGE_TUNE_*
 
 
 class tuning:

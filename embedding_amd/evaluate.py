@@ -4,7 +4,8 @@ Hogwild / multi-GPU) on one slice; and the reference's second figure, clustering
 (include/dge.h: dge_kmeans_vectors, dge_cluster_accuracy) instead of scikit-learn's randomised one; and the figures' "MF" baseline, NMF of a slice's flow matrix
 (P/matrixFactorization_tract.py:26-45), likewise a rule (dge_nmf_coo, dge_nmf_flows) instead of nimfa's randomised runs; and their "LINE" baseline
 (P/flowFeatureGeneration_tract.py:54-73), a rule as well (dge_line_coo, dge_line_flows) instead of a third-party tool's racing threads; and their third figure, the cross-validated accuracy of a decision
-tree on median labels (:201-232, :34-47), again a rule (dge_tree_fit, dge_tree_cv) instead of scikit-learn's randomly tie-broken one.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
+tree on median labels (:201-232, :34-47), again a rule (dge_tree_fit, dge_tree_cv) instead of scikit-learn's randomly tie-broken one; and the fourth, the leave-one-out
+regression error of regression-eval.sh:43-49 (P/tf_linear_regression.py:61-83), a rule too (dge_ridge_loo: closed-form ridge, the leverage identity) instead of ten steps of TensorFlow's FTRL.  The float64 host restatement these kernels are checked against is test infrastructure: oracle/quality.py."""
 import numpy as np
 
 
@@ -275,3 +276,39 @@ def tree_cv_gpu(features, y, n_folds=10, fold=None, select=None, max_depth=0, mi
     inf = TreeInfo()
     check(lib.dge_tree_cv(int(device), p(f), n, dim, p(y), p(fold), F, C.byref(cfg), p(correct), p(tested), p(nodes), p(depth), C.byref(inf)))
     return dict(cv_scores(correct, tested), n_nodes=nodes, depth=depth, info={fl[0]: getattr(inf, fl[0]) for fl in TreeInfo._fields_})
+
+
+def _ridge_args(n, y, lambdas, select):
+    """y [n] or [n x T] -> float64 [n x T]; lambdas -> float64 [L]; select -> uint8 [n] or None.  The shapes are checked here, the values by the library."""
+    y = np.asarray(y, np.float64)
+    if y.ndim == 1:
+        y = y[:, None]
+    if y.ndim != 2 or y.shape[0] != n:
+        raise ValueError("y must hold one row of targets per row: [%d] or [%d x n_targets], not %s" % (n, n, list(y.shape)))
+    lam = np.ascontiguousarray(np.atleast_1d(np.asarray(lambdas, np.float64)))
+    if lam.ndim != 1:
+        raise ValueError("lambdas must be a number or one-dimensional")
+    if select is not None:
+        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+        if select.shape != (n,):
+            raise ValueError("select must hold one entry per row")
+    return np.ascontiguousarray(y), lam, select
+
+
+def ridge_loo_gpu(features, y, lambdas, select=None, device=0):
+    """Leave-one-out ridge regression of the targets y on host rows [n x dim], on the device as the rule of include/dge.h (dge_ridge_loo): the reference's
+    regression figure (np.mean(mae), and that over mean(target)) per penalty and target.
+    -> dict(mae, mre [n_lambda x n_targets]; beta [n_lambda x n_targets x (dim + 1)]; loo_pred [n_lambda x n_targets x n], NaN on rows select leaves out; info)."""
+    import ctypes as C
+    from ._native import RidgeInfo, check, lib
+    f = np.ascontiguousarray(features, np.float32)
+    if f.ndim != 2:
+        raise ValueError("features must be [n x dim]")
+    n, dim = f.shape
+    y, lam, select = _ridge_args(n, y, lambdas, select)
+    T, L = y.shape[1], len(lam)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    mae = np.empty((L, T), np.float64); mre = np.empty((L, T), np.float64); beta = np.empty((L, T, dim + 1), np.float64); pred = np.empty((L, T, n), np.float64)
+    inf = RidgeInfo()
+    check(lib.dge_ridge_loo(int(device), p(f), n, dim, p(y), T, p(select), p(lam), L, p(mae), p(mre), p(beta), p(pred), C.byref(inf)))
+    return dict(mae=mae, mre=mre, beta=beta, loo_pred=pred, info={fl[0]: getattr(inf, fl[0]) for fl in RidgeInfo._fields_})

@@ -1160,6 +1160,68 @@ int  dge_tree_cv(int device, const float* features, int64_t n_rows, int32_t dim,
                  int64_t* correct, int64_t* tested, int32_t* n_nodes, int32_t* depth, dge_tree_info* info);
 
 /* ------------------------------------------------------------------------------------------------
+ * Leave-one-out ridge regression (new; additions only, DGE_VERSION unchanged): the reference's fourth figure of merit, the regression error that closes
+ * regression-eval.sh (:43-49): P/tf_linear_regression.py:61-83 leaves one region out, fits a linear model with an L2 penalty on the rest, predicts the region
+ * left out and prints np.mean(mae) and np.mean(mae) / mean(target).  The reference's fit is 10 steps of TensorFlow's FTRL from TensorFlow's initialisation: not
+ * a converged fit, and not reproducible by the reference itself.  Here it is a RULE (csrc/ridge.hip; the per-element pieces and a one-thread host solver:
+ * csrc/ridge_rule.h): ridge regression solved in closed form, the left-out errors from the leverage identity e_i = r_i / (1 - h_i) instead of n refits.  The
+ * result is a pure function of the used rows in row order, the targets and the penalties, bit for bit, whatever the launch geometry, the chunk size or the
+ * schedule of the factorisation: only rounded + * / and fma take part, each element's chain in the order fixed below.  tests/ridge_ref.py is this text in Python.
+ *   - INPUTS.  Resident float32 rows [rows x dim] with one present byte per row, 1 <= dim <= 256; an optional host array `select`, one byte per row (NULL: every
+ *     present row); host targets y, binary64 [rows x n_targets] row-major, 1 <= n_targets <= 64; host lambda[n_lambda], binary64, each finite and >= 0,
+ *     1 <= n_lambda <= 64.  The USED rows are the present rows with a non-zero select byte, in ascending row order; n is their count, 2 <= n <= 2^31 - 1, and
+ *     "row i" below is the i-th of them.  Anything outside the limits: DGE_ERR_ARG with the reason.  A feature or a target that is not finite in a used row:
+ *     DGE_ERR_ARG naming the least such row (by its number among all rows); rows that are not used are never read, neither their features nor their targets.
+ *     Null arguments and the limits on dim, n_targets, n_lambda and lambda: DGE_ERR_ARG before a device is looked for.  On any error the outputs are untouched.
+ *   - DESIGN ROW.  P = dim + 1; z[i][0] = 1.0, z[i][j] = (double)x[i][j-1].
+ *   - MOMENTS, in the blocked order of k-means: the used rows, in order, are cut into blocks of 256.  For 0 <= a <= b < P a block's partial of G[a][b] starts at
+ *     +0.0 and adds z[i][a] * z[i][b] row by row — the product of two float32 values is exact in binary64, so a step is one rounding — and the block partials
+ *     are added, from +0.0, in block order.  c[t][a] has the same shape with acc = fma(z[i][a], y[i][t], acc).  ysum[t] is the blocked sum of y[i][t] (c[t][0]
+ *     holds the same bits).
+ *   - SYSTEM.  For each lambda: A = G (symmetric) with lambda added once, one rounded addition, to every A[j][j], j >= 1.  The intercept is not penalised.
+ *   - FACTORISATION.  A = L D L' with L unit lower triangular, no pivoting, no square root.  For j ascending: acc = A[j][j]; for k = 0 .. j-1 ascending:
+ *     t = L[j][k] * d[k] (rounded), acc = fma(-L[j][k], t, acc); d[j] = acc.  For every i > j: acc = A[i][j], the same chain with fma(-L[i][k], L[j][k] * d[k], acc),
+ *     then L[i][j] = acc / d[j], one division.  Every element's chain runs over k ascending, so any column-parallel schedule gives the same bits.  A d[j] that
+ *     is not > 0 — what lambda = 0 gives on collinear columns — refuses the call: DGE_ERR_ARG naming j and the index of the lambda.
+ *   - COEFFICIENTS, per lambda l and target t.  w[j] starts at c[t][j]; forward: w[j] = fma(-L[j][k], w[k], w[j]) for k = 0 .. j-1 ascending; then one division
+ *     w[j] = w[j] / d[j]; backward: w[j] = fma(-L[k][j], w[k], w[j]) for k = P-1 .. j+1 descending.  beta[l][t][0 .. P) = w, the intercept first.
+ *   - LEVERAGE, per lambda and row.  u = L^-1 z[i]: u[j] starts at z[i][j], then u[j] = fma(-L[j][k], u[k], u[j]) for k ascending.  inv[j] = 1.0 / d[j], computed
+ *     once.  h[i] = the chain acc = fma(u[j], u[j] * inv[j], acc) (the inner product rounded), j ascending from +0.0.
+ *   - LEFT-OUT ERROR, per lambda, target and row.  p = beta[0], then p = fma(z[i][j], beta[j], p) for j = 1 .. P-1 ascending; r = y[i][t] - p; g = 1.0 - h[i].  A g
+ *     that is not > 0 (a row nothing else can predict) refuses the call: DGE_ERR_ARG naming the row (among all rows) and the index of the lambda.  Otherwise
+ *     e = r / g, and the left-out prediction is y[i][t] - e.
+ *   - REFUSALS IN ORDER.  Every factorisation comes before the first leverage: a pivot's refusal goes before a leverage's; among pivots the least lambda index
+ *     and its first j; among leverages the least lambda index and its least row.
+ *   - FIGURES.  mae[l][t] = the blocked sum of |e| divided by (double)n; mre[l][t] = mae[l][t] / (ysum[t] / (double)n), the reference's second printed number;
+ *     it is +-inf or NaN where the targets' mean is 0.
+ *   - PREDICTION (dge_ridge_predict_vectors): for every present row of any resident rows of the same dim, the p chain above; NaN on an absent row, which is not
+ *     read.  For a fit on one select mask applied to the other rows.
+ *   - NOT TensorFlow's FTRL regressor.  NOT a standardising pipeline: the columns are taken as they are, and a host that wants them scaled scales them.  NOT
+ *     order-free: it is a function of the used rows in row order, as k-means is.  No search for lambda, no k-fold, no wide-and-deep model
+ *     (P/tf_hybrid_regression.py); reading the target tables stays with the host.
+ *   - Device memory for the moments' block partials is bounded by a chunk of blocks (64; the knob DGE_TUNE_RIDGE_CHUNK sets it by hand), not by n; the result
+ *     is the same for every chunk size.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_ridge_info {
+    int64_t rows;              /* n: the used rows                                                         */
+    int64_t blocks;            /* blocks of 256 used rows                                                  */
+    int64_t chunks;            /* chunks of blocks the moments were taken in                               */
+    double  min_pivot;         /* the least d[j] of all factorisations                                     */
+    double  max_leverage;      /* the greatest h[i] of all lambdas                                         */
+    double  kernel_ms;         /* HIP-event time from the first kernel of the call to its last             */
+} dge_ridge_info;              /* 48 bytes */
+/* y: host binary64 [rows x n_targets]; mae, mre: host binary64 [n_lambda x n_targets]; beta: host [n_lambda x n_targets x (dim + 1)]; loo_pred: host
+   [n_lambda x n_targets x rows], NaN on rows that are not used; select, beta, loo_pred and info may be NULL */
+int  dge_ridge_loo_vectors(const dge_vectors* v, const double* y, int32_t n_targets, const uint8_t* select, const double* lambda, int32_t n_lambda, double* mae, double* mre,
+                           double* beta, double* loo_pred, dge_ridge_info* info);
+/* the same on host rows float32 [n_rows x dim], every row present (through dge_vectors_from_host); fewer than 2 used rows and a target that is not finite are
+   refused before a device is looked for */
+int  dge_ridge_loo(int device, const float* features, int64_t n_rows, int32_t dim, const double* y, int32_t n_targets, const uint8_t* select, const double* lambda,
+                   int32_t n_lambda, double* mae, double* mre, double* beta, double* loo_pred, dge_ridge_info* info);
+/* beta: host binary64 [n_models x (dim + 1)], 1 <= n_models <= 4096; out: host binary64 [n_models x rows] */
+int  dge_ridge_predict_vectors(const dge_vectors* v, const double* beta, int32_t n_models, double* out);
+
+/* ------------------------------------------------------------------------------------------------
  * Ablation / test knobs of the trainer (process-wide relaxed atomics; nothing in a normal run sets them).  value < 0 puts
  * a knob back to the library's own rule.
  * ---------------------------------------------------------------------------------------------- */
@@ -1186,7 +1248,8 @@ enum {
     DGE_TUNE_HS_COPIES = 18,      /* k_sgns_train_hsw, copies form: the root's number of copies (a node's copies = ceil(its share of the paths x value), at most 16); default 16 */
     DGE_TUNE_SMALL_ROWS = 19,     /* rows of 17 .. 32 floats under the atomics policy: 1 = k_sgns_train_small (32 lanes a worker, a row = one request), 0 = k_sgns_train's 16-lane groups; default: the small-row kernel wherever it applies (v106) */
     DGE_TUNE_TREE_BATCH = 20,     /* dge_tree_cv*: at most this many trees grow together (1: one after another); default: as many as half the free device memory holds */
-    DGE_TUNE_COUNT = 21
+    DGE_TUNE_RIDGE_CHUNK = 21,    /* dge_ridge_loo*: blocks of 256 used rows whose partial moments are held at once (default 64); the result is the same for every value */
+    DGE_TUNE_COUNT = 22
 };
 int  dge_set_tuning(int32_t knob, int64_t value);
 int  dge_get_tuning(int32_t knob, int64_t* value);   /* -1 = the library's own rule */
