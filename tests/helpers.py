@@ -173,6 +173,71 @@ def saturated_state(V, D, side, sign, seed, mag=3, use_hs=False):
     return out
 
 
+# ---- the balanced, exactly summable regime (tests/test_oracle_kats.py, tests/test_gpu_conservation_balanced.py)
+# Column 0 of every row puts every score into the middle bin of the sigmoid table: syn0[:, 0] = 1/4 and syn1neg[:, 0] = syn1[:, 0] = 1/8, so f = 2^-5 (+ something
+# tiny) for every term; idx = (int)((f + 6) * 83) = 500 for f in [0.024096, 0.036145) and exp_table[500] is exactly 0.5f.  The tree term is then
+# g = (1 - code - 0.5) * alpha = +/- alpha/2 and the negative-sampling term g = (label - 0.5) * alpha = +/- alpha/2: no clamp, no skip, the table look-up on every
+# term.  With alpha = min_alpha = 2^-60 the accumulating table holds 2^-61 x (a signed sum of small integers) — exact in any order below 2^24 — and what flows back
+# into the standing table (~2^-122 x integers) is absorbed by its entries, none of which is 0; a score moves by less than 1.2e-8, the bin has 0.0048 to spare.
+BAL_ALPHA = 2.0 ** -60
+
+
+def balanced_state(V, D, side, seed, mag=3, use_hs=False):
+    """Initial tables of the balanced regime -> {"syn0", "syn1neg"[, "syn1"]}, float32 [V x D] (syn1: [V-1 x D]).
+    side "A": syn0[:, 1:] holds the integer codes (column 1 = 1, the net-count channel; the others +/- 1 .. mag, never 0), syn1neg[:, 1:] and syn1[:, 1:] = 0 accumulate;
+    side "B": the mirror image — syn1neg and syn1 hold codes (different ones), syn0[:, 1:] = 0 accumulates through a pair's neu1e."""
+    assert side in ("A", "B") and D >= 2 and mag >= 1
+    rng = np.random.default_rng([int(seed), V, D, 60])
+
+    def codes(rows):
+        c = (rng.integers(1, mag + 1, (rows, D)) * rng.choice([-1, 1], (rows, D))).astype(np.float32)
+        c[:, 1] = 1.0
+        return c
+    s0 = np.zeros((V, D), np.float32); s1 = np.zeros((V, D), np.float32); s2 = np.zeros((max(V - 1, 0), D), np.float32)
+    if side == "A":
+        s0[:] = codes(V)
+    else:
+        s1[:] = codes(V); s2[:] = codes(len(s2))
+    s0[:, 0] = 0.25; s1[:, 0] = 0.125; s2[:, 0] = 0.125
+    out = {"syn0": s0, "syn1neg": s1}
+    if use_hs:
+        out["syn1"] = s2
+    return out
+
+
+class Balanced:
+    """What balanced_diff returns: per row `diff`, the largest |got - want| over the row's columns in units of alpha/2, and `whole`, whether the row of `got` holds
+    whole multiples of alpha/2 only."""
+
+    def __init__(self, diff, whole, net_want, net_got):
+        self.diff, self.whole, self.net_want, self.net_got = diff, whole, net_want, net_got
+
+    @property
+    def exact(self):
+        return not self.diff.any()
+
+    def worst(self):
+        r = int(np.argmax(self.diff))
+        return "row %d: off by %.3f units of alpha/2 (net count %.3f, expected %d); %d of %d rows differ, %d hold a fraction of a unit" % (
+            r, self.diff[r], self.net_got[r], self.net_want[r], int((self.diff != 0).sum()), len(self.diff), int((~self.whole).sum()))
+
+
+def balanced_diff(got, want, init, bound, alpha=BAL_ALPHA):
+    """Trained table `got` against the expected one `want` (both [rows x D], an ACCUMULATING table of a balanced run that began as `init`) -> Balanced.
+    Asserts first, on `want` alone, the conditions of the method: column 0 is unchanged, every accumulated value is a whole multiple of alpha/2, and `bound` — the
+    largest code magnitude times an upper bound on the terms one row can take, from host quantities — is below 2^24, so that every partial sum in ANY order is
+    exact (and the reference's own sums are inside it)."""
+    unit = alpha / 2
+    assert 0 <= bound < SAT_CAP, "a row can take %d units: partial sums may leave the exactly summable range (2^24) — shorten the corpus or lower `mag`" % bound
+    assert np.array_equal(bits(want[:, 0]), bits(init[:, 0])), "the reference's column 0 moved: it is outside the balanced regime"
+    w = want[:, 1:].astype(np.float64) / unit
+    assert (w == np.rint(w)).all(), "the expected table is not a table of whole multiples of alpha/2: the reference is outside the balanced regime"
+    assert np.abs(w).max(initial=0.0) <= bound, "the expected table exceeds the stated term bound: |sum| = %.0f > %d" % (np.abs(w).max(initial=0.0), bound)
+    g = got[:, 1:].astype(np.float64) / unit
+    diff = np.maximum(np.abs(g - w).max(1), np.abs(got[:, 0].astype(np.float64) - init[:, 0]) / unit)
+    return Balanced(diff, (g == np.rint(g)).all(1), np.rint(w[:, 0]).astype(np.int64), g[:, 0])
+
+
 def device_rows(a, stride, rows=None):
     """[V x D] -> the C ABI's import shape [rows x stride] (rows: the table's V; zero padding columns, zero rows behind a shorter table such as syn1)."""
     out = np.zeros((a.shape[0] if rows is None else rows, stride), np.float32)

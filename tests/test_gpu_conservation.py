@@ -10,7 +10,8 @@ updates the row took.  Run A lets syn1neg accumulate, run B syn0 (the path throu
 
 Expected tables: the sequential oracle from the same state (its own witness is the int64 enumeration of tests/test_oracle_kats.py::test_saturated_regime_equals_int64_sums).
 Every case asserts the kernel / schedule that ran, so that each instantiation plan_train can choose (sgns_kernels.h: launch_train_b; sgns_sorted.hip) is reached.
-The tree term's own arithmetic is out of scope (with use_hs, syn1 saturates too: the tree step is skipped and syn1 must come back unchanged).
+With use_hs, syn1 saturates too: the tree step is skipped and syn1 must come back unchanged.  The tree term's own arithmetic, and the sigmoid-table path that
+saturation never takes, are held to the same exactness in the balanced regime of tests/test_gpu_conservation_balanced.py.
 SGNS half of the oracle: a restatement of word2vec.c / DL4J (J/DeepWalk.java:73-79), parity unpinned — DESIGN.md §3."""
 import concurrent.futures as cf
 import ctypes

@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import SAT_ALPHA, bits, conservation_diff, cosine_rows, layered_graph, saturated_state
+from helpers import BAL_ALPHA, SAT_ALPHA, balanced_diff, balanced_state, bits, conservation_diff, cosine_rows, layered_graph, saturated_state
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 M64 = (1 << 64) - 1
@@ -317,6 +317,133 @@ def test_saturated_regime_equals_int64_sums(oracle, K):
             assert np.array_equal(bits(hs.syn1), bits(saturated_state(V, D, side, sign, seed=9, mag=7, use_hs=True)["syn1"]))
             if sign < 0:
                 assert int(np.rint(getattr(runs["arith0"], moving)[:, 1].astype(np.float64) / SAT_ALPHA).sum()) == runs["arith0"].pairs      # the count channel's sum: every positive pair once
+
+
+def tree_terms(ctx, tgt, lab, paths, part_n=0):
+    """The tree's (context row, inner node, code bit) terms of a run whose positive pairs are the label-1 terms of enumerate_terms: every pair meets every inner
+    node on its centre's Huffman path (paths[row] = (nodes, bits)).  With part_n > 1 the block rule, restated: the blocks in turn, a (pair, node) term in the block of
+    (its context's partition, the NODE's partition — inner nodes are split by node % n), whatever partition the centre is in."""
+    pos = lab == 1
+    c_all, w_all = ctx[pos], tgt[pos]
+    PN = part_n if part_n > 1 else 1
+    c_out, n_out, b_out = [], [], []
+    for blk in range(PN * PN):
+        part_ctx, part_tgt = blk % PN, (blk % PN + blk // PN) % PN
+        for c, w in zip(c_all.tolist(), w_all.tolist()):
+            if c % PN != part_ctx:
+                continue
+            for node, bit in zip(*paths[w]):
+                if node % PN == part_tgt:
+                    c_out.append(c); n_out.append(int(node)); b_out.append(int(bit))
+    return np.array(c_out, np.int64), np.array(n_out, np.int64), np.array(b_out, np.int64)
+
+
+def _balanced_sums(state, side, ns, tree):
+    """what the accumulating tables of a balanced run hold, in units of alpha/2: int64 sums over the terms, s = +1 for a positive pair / a code bit 0 and -1 for a
+    negative draw / a code bit 1 -> {table: [rows x D-1]}"""
+    ctx, tgt, lab = ns
+    s = np.where(lab == 1, 1, -1)[:, None]
+    tc, tn, tb = tree if tree is not None else (np.zeros(0, np.int64),) * 3
+    st = np.where(tb == 0, 1, -1)[:, None]
+    out = {}
+    if side == "A":
+        c0 = state["syn0"].astype(np.int64)
+        out["syn1neg"] = np.zeros(c0.shape, np.int64); np.add.at(out["syn1neg"], tgt, s * c0[ctx])                 # syn1neg[target] += s * codes0[context]
+        if tree is not None:
+            out["syn1"] = np.zeros((len(c0) - 1, c0.shape[1]), np.int64); np.add.at(out["syn1"], tn, st * c0[tc])  # syn1[node] += s * codes0[context]
+    else:
+        c1 = state["syn1neg"].astype(np.int64)
+        out["syn0"] = np.zeros(c1.shape, np.int64); np.add.at(out["syn0"], ctx, s * c1[tgt])                       # syn0[context] += sum of s * codes1neg[target]
+        if tree is not None:
+            np.add.at(out["syn0"], tc, st * state["syn1"].astype(np.int64)[tn])                                    #                + sum of s * codes1[node]
+    return {k: v[:, 1:] for k, v in out.items()}
+
+
+def _as_table(init, sums):
+    """int64 sums in units of alpha/2 -> the float32 table they stand for"""
+    return np.concatenate([init[:, :1], (sums.astype(np.float64) * (BAL_ALPHA / 2)).astype(np.float32)], 1)
+
+
+@pytest.mark.parametrize("K", [0, 5, 17])
+def test_balanced_regime_equals_int64_sums(oracle, K):
+    """The expected tables of tests/test_gpu_conservation_balanced.py come from the sequential oracle; here the oracle meets an independent witness.  In the balanced
+    regime (helpers.balanced_state) every score sits in the bin of exp_table[500] = 0.5 exactly, every tree and negative-sampling term is +/- alpha/2, and a run's
+    result is alpha/2 x (a signed integer sum over its terms): the Python enumeration — negative-sampling terms as above, the tree's (context, node, code) terms from
+    the Huffman paths of an epochs=0 model — predicts syn1, syn1neg (run A) and syn0 (run B) EXACTLY.  Two epochs, out-of-vocabulary tokens; word2vec order, lane
+    order and the plain loop; the block schedule (part_n = 3, inner nodes split by node % n); with and without the tree term.  Last, balanced_diff is shown to catch
+    one term dropped, doubled, given the other code bit or sent to the neighbouring row: the assertion the GPU file stands on."""
+    assert oracle.exp_table()[500] == np.float32(0.5) and bits(oracle.exp_table()[500:501])[0] == bits(np.float32([0.5]))[0]
+    ids, NV = _saturated_corpus()
+    D, W, T, seed, EP, MAG = 7, 3, 997, 23, 2, 3
+    cnt = np.bincount(ids[ids >= 0], minlength=NV)
+    order = sorted([v for v in range(NV) if cnt[v] >= 2], key=lambda v: (-cnt[v], v))
+    V = len(order)
+    assert 8 < V < NV and (ids < 0).any()
+    kw = dict(negative=K, min_count=2, epochs=EP, seed=seed, table_size=T, alpha=BAL_ALPHA, min_alpha=BAL_ALPHA)
+    m0 = oracle.train_sgns(ids, NV, D, W, **dict(kw, epochs=0, use_hs=True))
+    table = m0.table(T)
+    paths = [m0.code(r) for r in range(V)]
+    assert all(len(p[0]) >= 1 and ((0 <= p[0]) & (p[0] < V - 1)).all() for p in paths) and paths[0][0][0] == V - 2          # every path starts at the root
+    ns = {pn: enumerate_terms(ids, order, table, W, K, seed, epochs=EP, part_n=pn) for pn in (0, 3)}
+    tree = {pn: tree_terms(*ns[0], paths, part_n=pn) for pn in (0, 3)}
+    pairs = int(ns[0][2].sum())
+    assert pairs == int(ns[3][2].sum()) and len(tree[0][0]) == len(tree[3][0]) == sum(len(paths[w][0]) for w in ns[0][1][ns[0][2] == 1])
+    assert (tree[0][2] == 0).any() and (tree[0][2] == 1).any()
+    bound = MAG * pairs * (K + 1 + max(len(p[0]) for p in paths))          # no row takes more terms than the run has
+    for side in "AB":
+        for hs in (False, True):
+            st = balanced_state(V, D, side, seed=9, mag=MAG, use_hs=hs)
+            init = dict(syn0_init=st["syn0"], syn1neg_init=st["syn1neg"], syn1_init=st.get("syn1"), use_hs=hs)
+            runs = {}
+            for name, extra in (("arith0", dict(arith=0)), ("arith1", dict(arith=1)), ("plain", dict(arith=0)), ("blocks", dict(arith=1, part_n=3))):
+                oracle.set_plain(name == "plain")
+                try:
+                    runs[name] = oracle.train_sgns(ids, NV, D, W, **kw, **init, **extra)
+                finally:
+                    oracle.set_plain(False)
+            for name, m in runs.items():
+                pn = 3 if name == "blocks" else 0
+                assert m.vocab_ids.tolist() == order and m.pairs == pairs
+                want = _balanced_sums(st, side, ns[pn], tree[pn] if hs else None)
+                assert set(want) == ({"syn1neg", "syn1"} if hs else {"syn1neg"}) if side == "A" else set(want) == {"syn0"}
+                for t in st:
+                    got = getattr(m, t)
+                    if t not in want:
+                        assert np.array_equal(bits(got), bits(st[t])), (side, hs, name, t)          # a standing table comes back bit-unchanged
+                        continue
+                    assert np.array_equal(bits(got[:, 0]), bits(st[t][:, 0])), (side, hs, name, t)
+                    assert np.array_equal(got[:, 1:].astype(np.float64) / (BAL_ALPHA / 2), want[t].astype(np.float64)), (side, hs, name, t)
+                    assert np.abs(want[t]).max() > 0
+                    d = balanced_diff(got, _as_table(st[t], want[t]), st[t], bound)
+                    assert d.exact and d.whole.all(), d.worst()
+            for name in ("arith1", "plain"):
+                for t in st:
+                    assert np.array_equal(bits(getattr(runs[name], t)), bits(getattr(runs["arith0"], t))), (side, hs, name, t)
+    # ---- balanced_diff against single mutations of the int64 sums (the tree term; run A: syn1, run B: syn0)
+    rng = np.random.default_rng(K)
+    tc, tn, tb = tree[0]
+    for side, t in (("A", "syn1"), ("B", "syn0")):
+        st = balanced_state(V, D, side, seed=9, mag=MAG, use_hs=True)
+        want = _as_table(st[t], _balanced_sums(st, side, ns[0], tree[0])[t])
+        i = int(rng.integers(len(tc)))
+        row = int(tn[i] if side == "A" else tc[i])
+        other = row + 1 if row + 1 < len(st[t]) else row - 1
+        keep = np.arange(len(tc)) != i
+        moved_n, moved_c = tn.copy(), tc.copy()
+        (moved_n if side == "A" else moved_c)[i] = other
+        if side == "B":          # (run B reads the node's codes: a term sent to the neighbouring ROW of syn0 keeps its node)
+            moved_n = tn
+        mutations = {"dropped": (tc[keep], tn[keep], tb[keep]), "doubled": (np.append(tc, tc[i]), np.append(tn, tn[i]), np.append(tb, tb[i])),
+                     "code bit flipped": (tc, tn, np.where(np.arange(len(tc)) == i, 1 - tb, tb)), "sent to the neighbouring row": (moved_c, moved_n, tb)}
+        for what, mut in mutations.items():
+            got = _as_table(st[t], _balanced_sums(st, side, ns[0], mut)[t])
+            d = balanced_diff(got, want, st[t], bound)
+            hit = {row, other} if what.startswith("sent") else {row}
+            assert not d.exact and set(np.flatnonzero(d.diff).tolist()) == hit and d.whole.all(), (side, what, d.worst())
+            n = 2 if what.startswith("code") else 1          # a flipped code bit moves the row by twice the term
+            assert all(n <= d.diff[r] <= n * MAG and d.diff[r] == np.rint(d.diff[r]) for r in hit), (side, what, d.worst())
+            assert "row %d" % int(np.argmax(d.diff)) in d.worst() and "%d of %d rows differ" % (len(hit), len(st[t])) in d.worst()
+            assert (np.abs(d.net_got - d.net_want)[sorted(hit)] == (2 if what.startswith("code") else 1)).all(), (side, what)          # column 1: the net count, off by the term
 
 
 def test_sigmoid_table_and_lane_order_agreement(oracle):
