@@ -275,3 +275,61 @@ def conservation_diff(got, want, alpha=SAT_ALPHA):
     g = got[:, 1:].astype(np.float64) / alpha
     other = np.abs(g[:, 1:] - w[:, 1:]).max(1) if w.shape[1] > 1 else np.zeros(len(w))
     return Conservation(np.rint(w[:, 0]).astype(np.int64), g[:, 0], other)
+
+
+# ---- graded rates: the per-walk learning rate on an exact dyadic lattice (tests/test_oracle_kats.py, tests/test_gpu_conservation_rates.py)
+# alpha0 = 2^-e, min_alpha = 2^-(e+2) and a vocabulary whose token sum T has epochs * T + 1 = 2^m: a walk that `done` tokens precede trains at
+# 2^-e * (2^m - done) / 2^m — every step of the formula exact in binary64, the cast exact in float32 — a whole multiple of u = 2^-(e+b) wherever 2^(m-b) divides
+# every `done` that occurs.  In the saturated state a live term is then +/- level x code units of u, in the balanced state units of u/2: sums still do not depend on
+# the order of the additions, but they do depend on the rate each term carried.
+def rate_level(wb, words_before, epoch, T, epochs, b, words_scale=(1, 1), clamp=2):
+    """The learning rate, in units of alpha0 / 2^b, of a walk that `wb` in-vocabulary tokens of its launch precede: `words_before` tokens of the epoch lie before the
+    launch, `T` tokens make an epoch (epochs * T + 1 must be a power of two, 2^m, m >= b), words_scale = (numerator, denominator) is the launch's scale on wb
+    (truncated, as the cast to int64 truncates), clamp = c puts the floor at alpha0 / 2^c (None: no floor).  Integers only."""
+    wb, words_before, epoch, T, epochs, b = int(wb), int(words_before), int(epoch), int(T), int(epochs), int(b)
+    num, den = int(words_scale[0]), int(words_scale[1])
+    full = epochs * T + 1
+    m = full.bit_length() - 1
+    assert full == 1 << m and 0 <= b <= m and num > 0 and den > 0 and wb >= 0 and words_before >= 0 and 0 <= epoch
+    done = epoch * T + words_before + (wb * num) // den
+    left, step = full - done, 1 << (m - b)
+    assert 0 < left < 1 << 24, "2^m - done = %d does not fit a float32 significand (or the schedule has run out)" % left
+    assert left % step == 0, "%d tokens done: the rate is no whole multiple of alpha0 / 2^%d" % (done, b)
+    level = left // step
+    if clamp is not None:
+        assert 0 <= clamp <= b
+        level = max(level, 1 << (b - clamp))
+    return level
+
+
+class Graded:
+    """What graded_diff returns: per row `diff`, the largest |got - want| over the row's columns in lattice units, `whole`, whether the row of `got` holds whole
+    multiples of the unit only, and column 1 — the sum of the levels of the row's terms, signed — as `level_want` / `level_got`."""
+
+    def __init__(self, diff, whole, level_want, level_got):
+        self.diff, self.whole, self.level_want, self.level_got = diff, whole, level_want, level_got
+
+    @property
+    def exact(self):
+        return not self.diff.any()
+
+    def worst(self):
+        r = int(np.argmax(self.diff))
+        return "row %d: off by %.3f lattice units (sum of its terms' levels: expected %d, got %.3f); %d of %d rows differ, %d hold a fraction of a unit" % (
+            r, self.diff[r], self.level_want[r], self.level_got[r], int((self.diff != 0).sum()), len(self.diff), int((~self.whole).sum()))
+
+
+def graded_diff(got, want, init, unit, levels, bound):
+    """Trained table `got` against the expected one `want` (both [rows x D], an ACCUMULATING table of a graded-rates run that began as `init`) -> Graded.
+    `unit`: what one lattice unit is worth in the table (saturated: alpha0 / 2^b, balanced: alpha0 / 2^(b+1)); `levels`: the largest level a walk can train at (2^b);
+    `bound`: the largest code magnitude times an upper bound on the terms one row can take, from host quantities.  Asserts first, on `want` alone, the conditions of
+    the method: bound x levels < 2^24 (every partial sum in ANY order is exact), column 0 unchanged, every accumulated value a whole multiple of the unit and inside
+    the bound."""
+    assert levels >= 1 and 0 <= bound * levels < SAT_CAP, "a row can take %d x %d units: partial sums may leave the exactly summable range (2^24) — shorten the corpus, coarsen the lattice or lower `mag`" % (bound, levels)
+    assert np.array_equal(bits(want[:, 0]), bits(init[:, 0])), "the reference's column 0 moved: it is outside the regime"
+    w = want[:, 1:].astype(np.float64) / unit
+    assert (w == np.rint(w)).all(), "the expected table is not a table of whole multiples of the lattice unit: the reference is outside the graded regime"
+    assert np.abs(w).max(initial=0.0) <= bound * levels, "the expected table exceeds the stated term bound: |sum| = %.0f > %d" % (np.abs(w).max(initial=0.0), bound * levels)
+    g = got[:, 1:].astype(np.float64) / unit
+    diff = np.maximum(np.abs(g - w).max(1), np.abs(got[:, 0].astype(np.float64) - init[:, 0]) / unit)
+    return Graded(diff, (g == np.rint(g)).all(1), np.rint(w[:, 0]).astype(np.int64), g[:, 0])

@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import BAL_ALPHA, SAT_ALPHA, balanced_diff, balanced_state, bits, conservation_diff, cosine_rows, layered_graph, saturated_state
+from helpers import BAL_ALPHA, SAT_ALPHA, balanced_diff, balanced_state, bits, conservation_diff, cosine_rows, graded_diff, layered_graph, rate_level, saturated_state
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 M64 = (1 << 64) - 1
@@ -198,16 +198,16 @@ def test_vocabulary_table_init_and_pair_enumeration(oracle):
     assert int(lab.sum()) == pairs and pairs * (K - 1) < int((lab == 0).sum()) <= pairs * K
 
 
-def enumerate_terms(walks, order, table, W, K, seed, epochs=1, part_n=0):
+def enumerate_terms(walks, order, table, W, K, seed, epochs=1, part_n=0, with_walk=False):
     """The (context row, target row, label) terms of a training run in the sequential order, restated in Python: per-(walk, centre) streams, DL4J's window
     loop, the negative draws — table[(s >> 16) % T], row 0 redrawn as s % (V-1) + 1, a draw equal to the centre skipped — and, with part_n > 1, the block
     schedule's rule: the blocks in turn, a pair in the block of (its context's, its centre's) partition, one stream a pair, negatives moved into the target
-    partition."""
+    partition.  with_walk: each term's (epoch, walk) as two more arrays — what the learning rate of the term depends on."""
     MULT = 25214903917
     remap = {v: r for r, v in enumerate(order)}
     V, T, L = len(order), len(table), walks.shape[1]
     PN = part_n if part_n > 1 else 1
-    ctx, tgt, lab = [], [], []
+    ctx, tgt, lab, eps, wis = [], [], [], [], []
     for ep in range(epochs):
         for blk in range(PN * PN):
             part_ctx, part_tgt = blk % PN, (blk % PN + blk // PN) % PN
@@ -230,7 +230,7 @@ def enumerate_terms(walks, order, table, W, K, seed, epochs=1, part_n=0):
                             if last % PN != part_ctx:
                                 continue
                             s = mix64((s_centre + c) & M64)
-                        ctx.append(last); tgt.append(word); lab.append(1)
+                        ctx.append(last); tgt.append(word); lab.append(1); eps.append(ep); wis.append(wi)
                         for _ in range(K):
                             s = (s * MULT + 11) & M64
                             t = int(table[(s >> 16) % T])
@@ -242,8 +242,9 @@ def enumerate_terms(walks, order, table, W, K, seed, epochs=1, part_n=0):
                                     t -= PN
                             if t == word:
                                 continue
-                            ctx.append(last); tgt.append(t); lab.append(0)
-    return np.array(ctx, np.int64), np.array(tgt, np.int64), np.array(lab, np.int64)
+                            ctx.append(last); tgt.append(t); lab.append(0); eps.append(ep); wis.append(wi)
+    out = np.array(ctx, np.int64), np.array(tgt, np.int64), np.array(lab, np.int64)
+    return out + (np.array(eps, np.int64), np.array(wis, np.int64)) if with_walk else out
 
 
 def _saturated_corpus(seed=4, NV=40, n=70, L=9):
@@ -444,6 +445,142 @@ def test_balanced_regime_equals_int64_sums(oracle, K):
             assert all(n <= d.diff[r] <= n * MAG and d.diff[r] == np.rint(d.diff[r]) for r in hit), (side, what, d.worst())
             assert "row %d" % int(np.argmax(d.diff)) in d.worst() and "%d of %d rows differ" % (len(hit), len(st[t])) in d.worst()
             assert (np.abs(d.net_got - d.net_want)[sorted(hit)] == (2 if what.startswith("code") else 1)).all(), (side, what)          # column 1: the net count, off by the term
+
+
+def _graded_corpus(T, min_count=2):
+    """the small ragged corpus again, longer, cut behind its T-th in-vocabulary token: the vocabulary is that of the uncut corpus (its counts go to the oracle),
+    an epoch has exactly T tokens -> (walks, NV, counts, rows by rank, tokens before each walk)"""
+    ids, NV = _saturated_corpus(n=160)
+    cnt = np.bincount(ids[ids >= 0], minlength=NV).astype(np.int64)
+    order = sorted([v for v in range(NV) if cnt[v] >= min_count], key=lambda v: (-cnt[v], v))
+    inv = np.isin(ids, order)
+    seen = np.cumsum(inv.reshape(-1)).reshape(ids.shape)
+    assert seen[-1, -1] > T
+    ids = np.where(seen > T, -1, ids).astype(np.int32)
+    ids = ids[:int(np.flatnonzero((ids >= 0).any(1)).max()) + 1]
+    inv = np.isin(ids, order)
+    assert int(inv.sum()) == T and (ids < 0).any() and (~inv & (ids >= 0)).any()
+    wb = np.concatenate([[0], np.cumsum(inv.sum(1))[:-1]]).astype(np.int64)
+    return ids, NV, cnt, order, wb
+
+
+def _graded_sums(state, side, regime, terms, lev):
+    """what the accumulating table of a graded-rates run holds, in lattice units: int64 sums of level(epoch, walk) x g x code over the terms.  regime +1 / -1: the
+    saturated state of that sign (g = -1 on negatives / +1 on positives, units of alpha0 / 2^b); 0: the balanced state (g = +/- 1, units of alpha0 / 2^(b+1))."""
+    ctx, tgt, lab, ep, wi = terms
+    g = np.where(lab == 1, 1, -1) if regime == 0 else np.where(lab == 0, -1, 0) if regime > 0 else np.where(lab == 1, 1, 0)
+    g = g * lev[ep, wi]
+    codes = (state["syn0"] if side == "A" else state["syn1neg"]).astype(np.int64)
+    out = np.zeros(codes.shape, np.int64)
+    if side == "A":
+        np.add.at(out, tgt, g[:, None] * codes[ctx])
+    else:
+        np.add.at(out, ctx, g[:, None] * codes[tgt])
+    return out[:, 1:]
+
+
+def test_graded_rates_equal_int64_sums(oracle):
+    """The learning-rate schedule of the oracle against integers.  alpha0 = 2^-e, an epoch of T tokens with epochs * T + 1 = 2^m: the rate of a walk is a whole
+    number of lattice units alpha0 / 2^m (helpers.rate_level: integers only, no code shared with alpha_for), and in the saturated and the balanced state the trained
+    table is an int64 sum of level(epoch, walk) x g x code over the terms of enumerate_terms.  Both states, sides A and B; one epoch and three; the floor alpha0 / 4
+    reached (the last quarter of the schedule) and — floor one unit — never reached; word2vec order, lane order and the plain loop; a run in two slices through
+    words_before and walk_index_base; the block schedule (part_n = 3: every block trains a walk at the walk's rate); owner-computes mini-batches (sorted_walks: a
+    mini-batch trains at the rate of its FIRST walk).  Every run differs from the constant-rate run.  Last, on the witness alone: one walk's level shifted by one,
+    the floor dropped, epoch * T dropped, every walk given its neighbour's tokens-before — each shows on exactly the rows those walks' live terms touch."""
+    D, W, K, TAB, seed, MAG = 7, 3, 5, 997, 23, 3
+    states = [(+1, SAT_ALPHA, 1.0), (-1, SAT_ALPHA, 1.0), (0, BAL_ALPHA, 0.5)]          # (regime, alpha0, a term's weight in units of alpha0 x level / 2^b)
+    teeth = 0
+    for EP, T in ((1, 255), (3, 341)):
+        ids, NV, cnt, order, wb = _graded_corpus(T)
+        n, V, m = len(ids), len(order), (EP * T + 1).bit_length() - 1
+        assert EP * T + 1 == 1 << m and (EP == 1 or m % 2 == 0) and 8 < V < NV
+        table = oracle.train_sgns(ids, NV, D, W, negative=K, min_count=2, epochs=0, seed=seed, table_size=TAB, counts=cnt).table(TAB)
+        terms = {pn: enumerate_terms(ids, order, table, W, K, seed, epochs=EP, part_n=pn, with_walk=True) for pn in (0, 3)}
+        for clamp in (2, m):
+            lev = np.array([[rate_level(wb[w], 0, ep, T, EP, m, clamp=clamp) for w in range(n)] for ep in range(EP)], np.int64)
+            floor = 1 << (m - clamp)
+            assert ((lev == floor).any() and (lev > floor).any()) if clamp == 2 else (lev > floor).all()          # the floor reached / never reached
+            assert (np.diff(lev.reshape(-1)) <= 0).all() and len(np.unique(lev)) > n // 2
+            PER = 5
+            lev_first = lev[:, (np.arange(n) // PER) * PER]                                # owner-computes: the mini-batch's first walk
+            assert (lev_first != lev).any()
+            for regime, a0, weight in states:
+                unit = a0 / (1 << m) * weight
+                kw = dict(negative=K, min_count=2, epochs=EP, seed=seed, table_size=TAB, alpha=a0, min_alpha=a0 / (1 << clamp), counts=cnt, total_words=T)
+                for side in "AB":
+                    st = saturated_state(V, D, side, regime, seed=9, mag=MAG) if regime else balanced_state(V, D, side, seed=9, mag=MAG)
+                    init = dict(syn0_init=st["syn0"], syn1neg_init=st["syn1neg"])
+                    moving, standing = ("syn1neg", "syn0") if side == "A" else ("syn0", "syn1neg")
+                    live = {pn: (np.ones(len(t[2]), bool) if regime == 0 else t[2] == 0 if regime > 0 else t[2] == 1) for pn, t in terms.items()}
+                    bound = MAG * max(int(np.bincount((t[1] if side == "A" else t[0])[live[pn]], minlength=V).max()) for pn, t in terms.items())
+                    runs = {}
+                    for name, extra in (("arith0", dict(arith=0)), ("arith1", dict(arith=1)), ("plain", dict(arith=0)), ("blocks", dict(arith=1, part_n=3)),
+                                        ("sorted", dict(arith=1, sorted_chunk=7, sorted_walks=PER))):
+                        oracle.set_plain(name == "plain")
+                        try:
+                            runs[name] = oracle.train_sgns(ids, NV, D, W, **kw, **init, **extra)
+                        finally:
+                            oracle.set_plain(False)
+                    if EP == 1:          # the same run in two launches: the second is told what lies before it
+                        h = n // 2 + 1
+                        h1 = oracle.train_sgns(ids[:h], NV, D, W, **kw, **init, arith=1, total_walks=n)
+                        runs["slices"] = oracle.train_sgns(ids[h:], NV, D, W, **kw, arith=1, total_walks=n, walk_index_base=h, words_before=int(wb[h]),
+                                                           syn0_init=h1.syn0, syn1neg_init=h1.syn1neg)
+                        assert h1.pairs + runs["slices"].pairs == runs["arith1"].pairs and 0 < wb[h] < T
+                    flat = oracle.train_sgns(ids, NV, D, W, **dict(kw, alpha=a0 / 2, min_alpha=a0 / 2), **init, arith=1)          # a constant-rate run
+                    for name, r in runs.items():
+                        what = (EP, clamp, regime, side, name)
+                        pn = 3 if name == "blocks" else 0
+                        assert r.vocab_ids.tolist() == order and (name == "slices" or r.pairs == int(terms[pn][2].sum())), what
+                        want = _graded_sums(st, side, regime, terms[pn], lev_first if name == "sorted" else lev)
+                        got = getattr(r, moving)
+                        assert np.array_equal(bits(getattr(r, standing)), bits(st[standing])), what
+                        assert np.array_equal(got[:, 1:].astype(np.float64) / unit, want.astype(np.float64)), what
+                        d = graded_diff(got, np.concatenate([st[moving][:, :1], (want.astype(np.float64) * unit).astype(np.float32)], 1), st[moving], unit, 1 << m, bound)
+                        assert d.exact and d.whole.all() and np.abs(d.level_want).max() > 0, (what, d.worst())
+                        assert not np.array_equal(bits(got), bits(getattr(flat, moving))), what          # graded, not constant
+                    for name in ("arith1", "plain") + (("slices",) if EP == 1 else ()):
+                        assert np.array_equal(bits(getattr(runs[name], moving)), bits(getattr(runs["arith0"], moving))), (EP, clamp, regime, side, name)
+                    assert not np.array_equal(bits(getattr(runs["sorted"], moving)), bits(getattr(runs["arith0"], moving)))          # the mini-batch rule is another schedule
+                    # ---- the method's teeth, on the witness alone (the saturated states: every live term of a row has one sign, nothing cancels in column 1)
+                    if regime == 0 or clamp != 2:
+                        continue
+                    ctx, tgt, lab, tep, twi = terms[0]
+                    rows_of = tgt if side == "A" else ctx
+                    table_of = lambda sums: np.concatenate([st[moving][:, :1], (sums.astype(np.float64) * unit).astype(np.float32)], 1)
+                    want = table_of(_graded_sums(st, side, regime, terms[0], lev))
+                    wstar = int(np.flatnonzero(np.bincount(twi[live[0] & (tep == EP - 1)], minlength=n))[3])
+                    shifted = lev.copy(); shifted[EP - 1, wstar] += 1
+                    no_floor = np.array([[rate_level(wb[w], 0, ep, T, EP, m, clamp=None) for w in range(n)] for ep in range(EP)], np.int64)
+                    no_epoch = np.array([[rate_level(wb[w], 0, 0, T, EP, m, clamp=2) for w in range(n)] for ep in range(EP)], np.int64)
+                    neighbour = np.array([[rate_level(wb[min(w + 1, n - 1)], 0, ep, T, EP, m, clamp=2) for w in range(n)] for ep in range(EP)], np.int64)
+                    for what, bad in (("one walk's level shifted by one", shifted), ("the floor dropped", no_floor), ("epoch * T dropped", no_epoch),
+                                      ("the neighbour's tokens-before", neighbour)):
+                        if what.startswith("epoch") and EP == 1:
+                            assert np.array_equal(bad, lev)
+                            continue
+                        d = graded_diff(table_of(_graded_sums(st, side, regime, terms[0], bad)), want, st[moving], unit, 1 << m, bound)
+                        hit = np.unique(rows_of[live[0] & (bad[tep, twi] != lev[tep, twi])])
+                        assert len(hit) > 0 and not d.exact and np.array_equal(np.flatnonzero(d.diff), hit) and d.whole.all(), (EP, regime, side, what, d.worst())
+                        assert "row %d" % int(np.argmax(d.diff)) in d.worst() and "%d of %d rows differ" % (len(hit), V) in d.worst()
+                        if what.startswith("one"):
+                            cnt_w = np.bincount(rows_of[live[0] & (tep == EP - 1) & (twi == wstar)], minlength=V)
+                            assert np.array_equal(np.abs(d.level_got - d.level_want), cnt_w), (side, what)          # column 1: one unit a term of that walk
+                        teeth += 1
+    assert teeth == 2 * 2 * (3 + 4)
+
+
+def test_rate_level_is_the_formula_in_integers():
+    """helpers.rate_level by hand: m = 4 (T = 15, one epoch), b = 4 -> 16 - done units; b = 2 -> (16 - done) / 4 where 4 divides it; the floor at a quarter; a launch
+    scale of 1/2 truncates; three epochs of T = 5."""
+    assert [rate_level(w, 0, 0, 15, 1, 4) for w in (0, 1, 11, 12, 13, 14)] == [16, 15, 5, 4, 4, 4]
+    assert [rate_level(w, 0, 0, 15, 1, 4, clamp=None) for w in (12, 13, 14)] == [4, 3, 2]
+    assert [rate_level(w, 4, 0, 15, 1, 2) for w in (0, 4, 8)] == [3, 2, 1] and rate_level(3, 0, 0, 15, 1, 4, words_scale=(1, 2)) == 15
+    assert rate_level(3, 0, 0, 15, 1, 4, words_scale=(2, 1)) == 10 and [rate_level(1, 1, ep, 5, 3, 4) for ep in range(3)] == [14, 9, 4]
+    with pytest.raises(AssertionError):
+        rate_level(1, 0, 0, 15, 1, 2)          # 15/16 is no multiple of 1/4
+    with pytest.raises(AssertionError):
+        rate_level(0, 0, 0, 14, 1, 2)          # T + 1 is no power of two
 
 
 def test_sigmoid_table_and_lane_order_agreement(oracle):
