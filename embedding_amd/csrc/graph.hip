@@ -566,6 +566,7 @@ int dge_graph_ensure_csr(dge_graph* g) {
         DGE_HIP(hipStreamSynchronize(g->stream));
     } else {
         DGE_HIP(hipMemsetAsync(g->d_row_ptr, 0, ((size_t)V + 1) * sizeof(int64_t), g->stream));
+        if (V > 0) DGE_HIP(hipMemsetAsync(g->d_outdeg, 0, (size_t)V * sizeof(double), g->stream));   // reserved vertices of an edgeless store: outDegree 0
         DGE_HIP(hipStreamSynchronize(g->stream));
     }
     DGE_HIP(hipGetLastError());
@@ -854,11 +855,21 @@ extern "C" int dge_graph_sample_next(const dge_graph* g, int32_t v, double x, in
 }
 
 // ------------------------------------------------------------------------------------------ walks API
+// k_walks stages a block's rows in LDS, WALK_BLOCK rows of (L | 1) words: 64 KiB hold walks of up to DGE_MAX_WALK_LEN tokens.  Every way into the
+// sampler — both stream layouts, the one-lane chain and the parallel resolver included — refuses a longer walk here, on the host, before any launch.
+static int walk_length_check(int32_t L) {
+    static_assert((size_t)WALK_BLOCK * (size_t)(DGE_MAX_WALK_LEN | 1) * sizeof(int32_t) <= 64 * 1024 &&
+                  (size_t)WALK_BLOCK * (size_t)((DGE_MAX_WALK_LEN + 1) | 1) * sizeof(int32_t) > 64 * 1024, "DGE_MAX_WALK_LEN is what k_walks' LDS rows hold");
+    if (L > DGE_MAX_WALK_LEN) DGE_FAIL(DGE_ERR_ARG, "walk length %d too long (max %d)", L, DGE_MAX_WALK_LEN);
+    return DGE_OK;
+}
+
 int dge_launch_walks_strided(const dge_graph* g, hipStream_t stream, int32_t* d_out, int64_t n, int32_t L, int64_t seed,
                              int64_t first_index, int32_t* d_deadend_count) {
+    int rc = walk_length_check(L);
+    if (rc) return rc;
     if (n == 0) return DGE_OK;
     size_t lds = (size_t)WALK_BLOCK * (size_t)(L | 1) * sizeof(int32_t);
-    if (lds > 64 * 1024) DGE_FAIL(DGE_ERR_ARG, "walk length %d too long (max %d)", L, (int)(64 * 1024 / WALK_BLOCK / 4 - 1));
     hipLaunchKernelGGL(k_walks, dim3(grid_for(n, WALK_BLOCK)), dim3(WALK_BLOCK), lds, stream, g->d_row_ptr, g->d_slots, g->d_src_slots,
                        g->S, d_out, n, L, dge_jr_scramble(seed), first_index * (int64_t)L, (int64_t)L, (const int64_t*)nullptr, (uint8_t*)nullptr, d_deadend_count);
     DGE_HIP(hipGetLastError());
@@ -869,10 +880,12 @@ static int sample_walks_impl(const dge_graph* g, int64_t n_walks, int32_t max_le
                              int32_t* d_out, int64_t* draws_consumed) {
     if (!g->alias_built) DGE_FAIL(DGE_ERR_STATE, "dge_sample_walks: call dge_graph_build_alias first (J/LayeredGraph.java:195)");
     if (rng_mode != 0 && rng_mode != 1) DGE_FAIL(DGE_ERR_ARG, "dge_sample_walks: rng_mode must be 0 or 1");
+    int rc = walk_length_check(max_len);
+    if (rc) return rc;
     DGE_HIP(hipSetDevice(g->device));
     if (n_walks == 0) { if (draws_consumed) *draws_consumed = 0; return DGE_OK; }
     dge_tmp<int32_t> d_dead;
-    int rc = d_dead.alloc(1);
+    rc = d_dead.alloc(1);
     if (rc) return rc;
     DGE_HIP(hipMemsetAsync(d_dead.p, 0, sizeof(int32_t), g->stream));
     int64_t walk0 = first_index;

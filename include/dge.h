@@ -445,7 +445,12 @@ int  dge_graph_add_spatial_points(dge_graph* g, const int64_t* ids, const double
  *            first_index = global index of the first walk (shards / batches).
  *            Both modes give identical walks on graphs where no walk dead-ends.
  * A dead end yields a shorter walk (pad -1), never an error (J/LayeredGraph.java:247-248).
+ * max_len is at most DGE_MAX_WALK_LEN: the sampler stages the walks of a block in on-chip memory, and 63 tokens per
+ *            walk is what fits.  A longer walk is DGE_ERR_ARG ("walk length N too long (max 63)") from all three entry
+ *            points, in both modes, whatever n_walks and first_index are — n_walks == 0 included — and nothing is
+ *            launched; dge_sample_walks_into refuses a corpus whose rows are longer (dge_walks_from_host takes any).
  * ---------------------------------------------------------------------------------------------- */
+#define DGE_MAX_WALK_LEN 63
 int  dge_sample_walks(const dge_graph* g, int64_t n_walks, int32_t max_len, int64_t seed, int rng_mode,
                       int64_t first_index, int32_t* out /* host [n_walks*max_len] */, int64_t* draws_consumed);
 int  dge_sample_walks_device(const dge_graph* g, int64_t n_walks, int32_t max_len, int64_t seed, int rng_mode,
