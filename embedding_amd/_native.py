@@ -145,6 +145,17 @@ class RidgeInfo(C.Structure):
     _fields_ = [("rows", C.c_int64), ("blocks", C.c_int64), ("chunks", C.c_int64), ("min_pivot", C.c_double), ("max_leverage", C.c_double), ("kernel_ms", C.c_double)]
 
 
+class SvmCfg(C.Structure):
+    """struct dge_svm_cfg (include/dge.h)."""
+    _fields_ = [("C", C.c_double), ("gamma", C.c_double), ("eps", C.c_double), ("max_iter", C.c_int64), ("state", C.c_int32), ("launch_iters", C.c_int32)]
+
+
+class SvmInfo(C.Structure):
+    """struct dge_svm_info (include/dge.h) — what dge_svm_fit* / dge_svm_cv* report."""
+    _fields_ = [("rows", C.c_int64), ("problems", C.c_int64), ("iterations", C.c_int64), ("max_iterations", C.c_int64), ("not_converged", C.c_int64),
+                ("support", C.c_int64), ("kernel_bytes", C.c_int64), ("launches", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 class HourWindow(C.Structure):
     """struct dge_hour_window (include/dge.h): the hours start, start + 1, .., start + hours - 1, each mod 24."""
     _fields_ = [("start", C.c_int32), ("hours", C.c_int32)]
@@ -309,6 +320,12 @@ SIGNATURES = {
     "dge_ridge_loo_vectors": (_int, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _P(RidgeInfo)]),
     "dge_ridge_loo": (_int, [_int, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _P(RidgeInfo)]),
     "dge_ridge_predict_vectors": (_int, [_vp, _vp, _i32, _vp]),
+    "dge_svm_fit_vectors": (_int, [_vp, _vp, _i32, _vp, _P(SvmCfg), _vp, _vp, _vp, _vp, _P(SvmInfo)]),
+    "dge_svm_decision_vectors": (_int, [_vp, _vp, _vp, _i32, C.c_double, _vp, _vp]),
+    "dge_svm_cv_vectors": (_int, [_vp, _vp, _i32, _vp, _i32, _P(SvmCfg), _vp, _vp, _vp, _vp, _vp, _vp, _P(SvmInfo)]),
+    "dge_svm_fit": (_int, [_int, _vp, _i64, _i32, _vp, _i32, _vp, _P(SvmCfg), _vp, _vp, _vp, _vp, _P(SvmInfo)]),
+    "dge_svm_decision": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i32, C.c_double, _vp, _i64, _vp]),
+    "dge_svm_cv": (_int, [_int, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _P(SvmCfg), _vp, _vp, _vp, _vp, _vp, _vp, _P(SvmInfo)]),
     "dge_selftest_locked_rows": (_int, [_int, _i32, _i64, _i32, C.c_uint64, _i32, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave": (_int, [_int, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),

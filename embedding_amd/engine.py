@@ -4,11 +4,14 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, SvmCfg, SvmInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
 
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+_byref = C.byref             # for the methods that have a parameter named C (the SVM's, as scikit-learn spells it)
 
 
 def _dev_ptr(t):
@@ -887,6 +890,72 @@ class Vectors:
         out = np.empty(beta.shape[:-1] + (n,), np.float64)
         check(lib.dge_ridge_predict_vectors(self._h, _ptr(beta), m, _ptr(out)))
         return out
+
+    def _label_columns(self, y):
+        """y [rows] or [n_labels x rows] -> uint8 [n_labels x rows]; anything but 0 and 1 becomes 255, which the library refuses where the row is used"""
+        y = np.asarray(y)
+        if y.ndim == 1:
+            y = y[None, :]
+        if y.ndim != 2 or y.shape[1] != self.shape[0] or y.shape[0] < 1:
+            raise ValueError("y must hold one label per row: [rows] or [n_labels x rows]")
+        if y.dtype != np.uint8:
+            y = np.where((y == 0) | (y == 1), y, 255).astype(np.uint8)
+        return np.ascontiguousarray(y)
+
+    def _svm_cfg(self, C, gamma, eps, max_iter, state, launch_iters):
+        return SvmCfg(float(C), 1.0 / max(self.shape[1], 1) if gamma is None else float(gamma), float(eps), int(max_iter), int(state), int(launch_iters))
+
+    def svm_fit(self, y, select=None, C=1.0, gamma=None, eps=1e-3, max_iter=10_000_000, state=0, launch_iters=0):
+        """An RBF C-SVC per label column on these rows as the rule of include/dge.h (dge_svm_fit_vectors): the same bits for the same used rows in row order,
+        labels and configuration.  y: [rows] or [n_labels x rows], 0 or 1; select: one entry per row, non-zero = take the row (default: every present row);
+        gamma: default 1 / dim.  -> dict(coef float64 [n_labels x rows]: s * alpha, 0 on used rows that are not support, NaN on rows not used; bias float64
+        [n_labels]; iterations int64, converged int32 [n_labels]; gamma; info: the fields of struct dge_svm_info)."""
+        n = self.shape[0]
+        y = self._label_columns(y)
+        L = y.shape[0]
+        if select is not None:
+            select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+            if select.shape != (n,):
+                raise ValueError("select must hold one entry per row")
+        cfg = self._svm_cfg(C, gamma, eps, max_iter, state, launch_iters)
+        coef = np.empty((L, n), np.float64); bias = np.empty(L, np.float64); iters = np.zeros(L, np.int64); conv = np.zeros(L, np.int32); inf = SvmInfo()
+        check(lib.dge_svm_fit_vectors(self._h, _ptr(y), L, _ptr(select), _byref(cfg), _ptr(coef), _ptr(bias), _ptr(iters), _ptr(conv), _byref(inf)))
+        return dict(coef=coef, bias=bias, iterations=iters, converged=conv, gamma=cfg.gamma, info={f[0]: getattr(inf, f[0]) for f in SvmInfo._fields_})
+
+    def svm_decision(self, coef, bias, gamma, x=None):
+        """f(x) of the models (coef [.. x rows], bias [..]: what svm_fit gives for these rows) for every row of x, another Vectors of the same dim, or of these
+        rows themselves (dge_svm_decision_vectors) -> float64 [n_models x rows(x)], NaN on an absent row."""
+        coef = np.ascontiguousarray(np.atleast_2d(np.asarray(coef, np.float64)))
+        bias = np.ascontiguousarray(np.atleast_1d(np.asarray(bias, np.float64)))
+        if coef.ndim != 2 or coef.shape[1] != self.shape[0] or bias.shape != (coef.shape[0],):
+            raise ValueError("coef must be [n_models x rows] and bias [n_models]")
+        x = self if x is None else x
+        out = np.empty((coef.shape[0], x.shape[0]), np.float64)
+        check(lib.dge_svm_decision_vectors(self._h, _ptr(coef), _ptr(bias), coef.shape[0], float(gamma), x._h, _ptr(out)))
+        return out
+
+    def svm_cv(self, y, fold, n_folds, C=1.0, gamma=None, eps=1e-3, max_iter=10_000_000, state=0, launch_iters=0, want_decision=False):
+        """Cross-validated accuracy of the SVM of svm_fit for every label column at once (dge_svm_cv_vectors): problem (l, f) trains column l on the present
+        rows with fold != f and is tested on those with fold == f; fold -1 takes a row out.  -> dict(scores float64 [n_labels x n_folds], NaN for a fold
+        without test rows; mean, std [n_labels] over the others (numpy's, what the reference prints); correct int64 [n_labels x n_folds]; tested int64
+        [n_folds]; iterations, support int64, converged int32 [n_labels x n_folds]; decision [n_labels x rows] where asked for; info)."""
+        n = self.shape[0]
+        y = self._label_columns(y)
+        L = y.shape[0]
+        fold = np.ascontiguousarray(fold, np.int32)
+        if fold.shape != (n,):
+            raise ValueError("fold must hold one entry per row")
+        F = int(n_folds)
+        cfg = self._svm_cfg(C, gamma, eps, max_iter, state, launch_iters)
+        shape = (L, max(F, 0))
+        correct = np.zeros(shape, np.int64); tested = np.zeros(max(F, 0), np.int64); iters = np.zeros(shape, np.int64); support = np.zeros(shape, np.int64)
+        conv = np.zeros(shape, np.int32); inf = SvmInfo()
+        decision = np.empty((L, n), np.float64) if want_decision else None
+        check(lib.dge_svm_cv_vectors(self._h, _ptr(y), L, _ptr(fold), F, _byref(cfg), _ptr(correct), _ptr(tested), _ptr(iters), _ptr(support), _ptr(conv), _ptr(decision),
+                                     _byref(inf)))
+        from .evaluate import svm_scores
+        return dict(svm_scores(correct, tested), iterations=iters, support=support, converged=conv, decision=decision, gamma=cfg.gamma,
+                    info={f[0]: getattr(inf, f[0]) for f in SvmInfo._fields_})
 
 
 def make_config(dim, window, n_vertices, negative=5, min_count=2, epochs=1, workers=0, alpha=0.025, min_alpha=1e-4,

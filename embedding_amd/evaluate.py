@@ -312,3 +312,79 @@ def ridge_loo_gpu(features, y, lambdas, select=None, device=0):
     inf = RidgeInfo()
     check(lib.dge_ridge_loo(int(device), p(f), n, dim, p(y), T, p(select), p(lam), L, p(mae), p(mre), p(beta), p(pred), C.byref(inf)))
     return dict(mae=mae, mre=mre, beta=beta, loo_pred=pred, info={fl[0]: getattr(inf, fl[0]) for fl in RidgeInfo._fields_})
+
+
+def svm_scores(correct, tested):
+    """Per-label, per-fold accuracies from counts: scores[l][f] = correct[l][f] / tested[f], NaN where a fold tested nothing; mean, std [n_labels]: numpy's over
+    the other folds (scores.mean(), scores.std() of the reference's printed line).  -> dict(scores, mean, std, correct, tested)."""
+    correct = np.asarray(correct, np.int64); tested = np.asarray(tested, np.int64)
+    scores = np.full(correct.shape, np.nan, np.float64)
+    ok = tested > 0
+    scores[:, ok] = correct[:, ok].astype(np.float64) / tested[ok].astype(np.float64)
+    if ok.any():
+        mean = scores[:, ok].mean(axis=1); std = scores[:, ok].std(axis=1)
+    else:
+        mean = np.full(len(correct), np.nan); std = np.full(len(correct), np.nan)
+    return dict(scores=scores, mean=mean, std=std, correct=correct, tested=tested)
+
+
+def _svm_args(features, y):
+    f = np.ascontiguousarray(features, np.float32)
+    if f.ndim != 2:
+        raise ValueError("features must be [n x dim]")
+    y = np.asarray(y)
+    if y.ndim == 1:
+        y = y[None, :]
+    if y.ndim != 2 or y.shape[1] != len(f) or y.shape[0] < 1:
+        raise ValueError("y must hold one label per row: [n] or [n_labels x n]")
+    if y.dtype != np.uint8:
+        y = np.where((y == 0) | (y == 1), y, 255).astype(np.uint8)
+    return f, np.ascontiguousarray(y)
+
+
+def svm_fit_gpu(features, y, select=None, C=1.0, gamma=None, eps=1e-3, max_iter=10_000_000, state=0, launch_iters=0, device=0):
+    """An RBF C-SVC per label column on host rows [n x dim] with labels y [n] or [n_labels x n] in {0, 1}, on the device as the rule of include/dge.h
+    (dge_svm_fit).  gamma: default 1 / dim.  -> dict(coef [n_labels x n], bias, iterations, converged [n_labels], gamma, info)."""
+    import ctypes as Ct
+    from ._native import SvmCfg, SvmInfo, check, lib
+    f, y = _svm_args(features, y)
+    n, dim = f.shape
+    L = y.shape[0]
+    p = lambda a: None if a is None else a.ctypes.data_as(Ct.c_void_p)      # noqa: E731
+    if select is not None:
+        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+        if select.shape != (n,):
+            raise ValueError("select must hold one entry per row")
+    cfg = SvmCfg(float(C), 1.0 / max(dim, 1) if gamma is None else float(gamma), float(eps), int(max_iter), int(state), int(launch_iters))
+    coef = np.empty((L, n), np.float64); bias = np.empty(L, np.float64); iters = np.zeros(L, np.int64); conv = np.zeros(L, np.int32); inf = SvmInfo()
+    check(lib.dge_svm_fit(int(device), p(f), n, dim, p(y), L, p(select), Ct.byref(cfg), p(coef), p(bias), p(iters), p(conv), Ct.byref(inf)))
+    return dict(coef=coef, bias=bias, iterations=iters, converged=conv, gamma=cfg.gamma, info={fl[0]: getattr(inf, fl[0]) for fl in SvmInfo._fields_})
+
+
+def svm_cv_gpu(features, y, n_folds=10, fold=None, select=None, C=1.0, gamma=None, eps=1e-3, max_iter=10_000_000, state=0, launch_iters=0, want_decision=False,
+               device=0):
+    """cross_val_score(svm.SVC(), features, y, cv=n_folds) of the reference (P/binaryClassification_CA.py:38,55-57) for every label column at once, as the rule
+    of include/dge.h (dge_svm_cv).  fold: one fold number per row, -1 = leave the row out (default: stratified_folds of the FIRST label column — one set of
+    folds serves all columns of a call).  -> dict(scores [n_labels x n_folds], mean, std [n_labels], correct, tested, iterations, support, converged,
+    decision, gamma, info)."""
+    import ctypes as Ct
+    from ._native import SvmCfg, SvmInfo, check, lib
+    f, y = _svm_args(features, y)
+    n, dim = f.shape
+    L, F = y.shape[0], int(n_folds)
+    if fold is None:
+        fold = stratified_folds(y[0], F, select)
+    elif select is not None:
+        raise ValueError("give fold or select, not both: fold -1 leaves a row out")
+    fold = np.ascontiguousarray(fold, np.int32)
+    if fold.shape != (n,):
+        raise ValueError("fold must hold one entry per row")
+    p = lambda a: None if a is None else a.ctypes.data_as(Ct.c_void_p)      # noqa: E731
+    cfg = SvmCfg(float(C), 1.0 / max(dim, 1) if gamma is None else float(gamma), float(eps), int(max_iter), int(state), int(launch_iters))
+    shape = (L, max(F, 0))
+    correct = np.zeros(shape, np.int64); tested = np.zeros(max(F, 0), np.int64); iters = np.zeros(shape, np.int64); support = np.zeros(shape, np.int64)
+    conv = np.zeros(shape, np.int32); inf = SvmInfo()
+    decision = np.empty((L, n), np.float64) if want_decision else None
+    check(lib.dge_svm_cv(int(device), p(f), n, dim, p(y), L, p(fold), F, Ct.byref(cfg), p(correct), p(tested), p(iters), p(support), p(conv), p(decision), Ct.byref(inf)))
+    return dict(svm_scores(correct, tested), iterations=iters, support=support, converged=conv, decision=decision, gamma=cfg.gamma,
+                info={fl[0]: getattr(inf, fl[0]) for fl in SvmInfo._fields_})

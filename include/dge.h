@@ -1227,6 +1227,98 @@ int  dge_ridge_loo(int device, const float* features, int64_t n_rows, int32_t di
 int  dge_ridge_predict_vectors(const dge_vectors* v, const double* beta, int32_t n_models, double* out);
 
 /* ------------------------------------------------------------------------------------------------
+ * SVM classification accuracy (new; additions only, DGE_VERSION unchanged): the SVM line of the reference's classification table,
+ * P/binaryClassification_CA.py:33-58 — for every label cross_val_score(svm.SVC(), F, l[k], cv=10) (:38,55-57) beside the tree's.  libsvm's result depends on its
+ * kernel cache, its shrinking heuristic and the platform's exp.  Here an RBF C-SVC solved by sequential minimal optimisation, its decision function and its
+ * F-fold cross-validated accuracy for many label columns at once are a RULE (csrc/svm.hip; the per-element pieces and a one-thread host solver:
+ * csrc/svm_rule.h): a pure function of the used rows in row order, the labels, the folds and the configuration, bit for bit, whatever the launch geometry,
+ * the place of the solver's state or the length of a launch.  Only rounded + - * / and fma take part, each element's chain in the order fixed below; RN(.)
+ * marks one rounding to binary64.  tests/svm_ref.py is this text in Python.
+ *   - INPUTS.  Resident float32 rows [rows x dim], 1 <= dim <= 4096, one present byte per row; host labels y, uint8 [n_labels x rows] in {0, 1},
+ *     1 <= n_labels <= 64.  A row is USED if it is present and, where a `select` mask is given, selected; in a cross-validation, if it is present and its fold
+ *     is not -1.  n is the number of used rows, taken in ascending row order, 2 <= n <= 65 536: fewer is DGE_ERR_ARG, more is DGE_ERR_RANGE (the kernel matrix
+ *     is held whole, there is no row cache).  A value that is not finite in a used row: DGE_ERR_ARG naming the least (row, column); a label other than 0 or 1
+ *     on a used row: DGE_ERR_ARG naming it.  Rows that are not used are never read.  s_t = +1 for label 1, -1 for label 0.
+ *   - CONFIGURATION, struct dge_svm_cfg (NULL: the defaults): C > 0 and finite (1); gamma > 0 and finite (1.0 / dim, scikit-learn's gamma='auto' of 2017);
+ *     eps > 0 (1e-3); max_iter >= 0 (10 000 000); state: 0 = the library chooses, 1 = the solver's state in LDS, 2 = in global memory (1 on more than 3 584
+ *     used rows: DGE_ERR_ARG with that bound); launch_iters >= 0: iterations per kernel launch, 0 = the library's default (1 024; at most 65 536 are run in
+ *     one launch whatever the value).  No kernel of the solver loops unbounded.  state and launch_iters change no bit of any result.  Anything outside these
+ *     limits: DGE_ERR_ARG before a device is looked for.
+ *   - KERNEL MATRIX.  d2(i, j) is k-means' distance chain: t = (double)x_i[c] - (double)x_j[c], acc = fma(t, t, acc), c ascending from +0.0.
+ *     K(i, j) = E(-(gamma * d2)): one rounded product, an exact negation, and E the exponential of the spatial graph's weight (csrc/spatial_weight.h).  K is
+ *     symmetric bit for bit (t only changes sign) and K(i, i) = 1.  It is computed once per call for all used rows, 8 n^2 bytes, and shared by every problem
+ *     of the call; device memory that does not hold it: DGE_ERR_CAP.
+ *   - ONE PROBLEM = a set of training rows (a subset of the used rows, ascending) and one label column.  State: alpha_t = 0, G_t = -1 for every training
+ *     row.  v_t = -s_t * G_t (exact).  I_up = {s_t = +1 and alpha_t < C} u {s_t = -1 and alpha_t > 0}; I_low = {s_t = +1 and alpha_t > 0} u {s_t = -1 and
+ *     alpha_t < C}.  "At a bound" always means alpha == 0 or alpha == C exactly.  Iteration k = 0, 1, ...:
+ *       1. m = max v_t over I_up, attained at i = the least such row; M = min v_t over I_low.
+ *       2. If either set is empty, or RN(m - M) < eps: stop, converged = 1.  Else if k == max_iter: stop, converged = 0.
+ *       3. For every t in I_low with v_t < m: b_t = RN(m - v_t); a_t = RN(2.0 - 2.0 * K(i, t)), replaced by 0x1p-40 where it is not > 0;
+ *          score_t = RN(RN(b_t * b_t) / a_t).  j = the row of the greatest score, the least row among equals.  Both selections are exact comparisons under
+ *          a total order: any reduction tree gives the same i, j.
+ *       4. delta = RN(b_j / a_j); lim_i = (s_i > 0 ? RN(C - alpha_i) : alpha_i); lim_j = (s_j > 0 ? alpha_j : RN(C - alpha_j)); delta = min(delta, lim_i, lim_j).
+ *       5. alpha_i' = its bound (C if s_i > 0, else 0) when delta == lim_i, otherwise RN(alpha_i + s_i * delta) clamped into [0, C]; alpha_j' = its bound
+ *          (0 if s_j > 0, else C) when delta == lim_j, otherwise RN(alpha_j - s_j * delta) clamped.
+ *       6. D_i = RN(alpha_i' - alpha_i), D_j likewise; for every training row t: G_t = fma(s_t s_j K(t, j), D_j, fma(s_t s_i K(t, i), D_i, G_t)); the sign
+ *          flips are exact.  Each element's chain is fixed, so any geometry gives the same bits.
+ *     After the loop: bias = RN(RN(m + M) * 0.5) from the last m, M; where one set was empty, the other value twice.  iterations = the updates made.  A
+ *     one-class training set: alpha = 0, iterations = 0, converged = 1, bias = +1 (all labels 1) or -1 (what the loop gives by itself).  An empty training
+ *     set: DGE_ERR_ARG naming the fold.
+ *   - DECISION.  The SUPPORT rows are the training rows with alpha > 0, in ascending row order; coef_u = s_u * alpha_u.  For a row x the terms
+ *     RN(coef_u * K(x_u, x)) over the support rows are added in k-means' blocked order: blocks of 256 support rows are each summed from +0.0 in order, and the
+ *     block sums are added, from +0.0, in block order.  f(x) = RN(bias + sum); the label is 1 iff f(x) > 0.  It depends on the support rows and their
+ *     coefficients only: a stand-alone decision call on the coef a fit returned gives the bits the cross-validation used.
+ *   - CROSS-VALIDATION.  fold[i] in -1 .. F-1, 1 <= F <= 64, as dge_tree_cv*.  Problem (l, f) trains label column l on the used rows with fold != f and is
+ *     tested on those with fold == f; the call runs all n_labels x F problems, one workgroup each, in one grid.  A fold without test rows reports 0 of 0.
+ *   - NOT libsvm: no shrinking, no cache, an exponential of its own; the bias is the midpoint of the final gap, not an average over the free rows; ties are
+ *     decided by row; the folds are the caller's (embedding_amd.evaluate.stratified_folds is the rule the Python view offers), not StratifiedKFold's.  RBF
+ *     only.  Binary labels.  No probabilities.  No class weights.  No search over C or gamma.
+ *   - Null and negative arguments: DGE_ERR_ARG naming the entry and "null", before a device is looked for.  On any error the outputs are untouched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_svm_cfg {
+    double  C;                 /* > 0, finite; default 1                                                   */
+    double  gamma;             /* > 0, finite; default 1.0 / dim                                           */
+    double  eps;               /* > 0; default 1e-3                                                        */
+    int64_t max_iter;          /* >= 0; default 10 000 000                                                 */
+    int32_t state;             /* 0 = the library chooses, 1 = LDS, 2 = global memory                      */
+    int32_t launch_iters;      /* iterations per kernel launch, 0 = the library's default                  */
+} dge_svm_cfg;                 /* 40 bytes */
+typedef struct dge_svm_info {
+    int64_t rows;              /* n: the used rows                                                         */
+    int64_t problems;          /* n_labels, or n_labels x n_folds                                          */
+    int64_t iterations;        /* summed over the problems                                                 */
+    int64_t max_iterations;    /* the longest problem's                                                    */
+    int64_t not_converged;     /* problems that stopped at max_iter                                        */
+    int64_t support;           /* support rows, summed over the problems                                   */
+    int64_t kernel_bytes;      /* 8 n^2                                                                    */
+    int64_t launches;          /* of the solver                                                            */
+    double  kernel_ms;         /* HIP-event time from the kernel matrix to the call's last kernel (the     */
+                               /* check of the values runs before it, ahead of the large allocations)      */
+} dge_svm_info;                /* 72 bytes */
+/* One model per label column on all used rows.  y: host uint8 [n_labels x rows]; coef: host binary64 [n_labels x rows], s * alpha, 0 on used rows that are not
+   support, NaN on rows not used; bias: host binary64 [n_labels]; iterations: host int64 [n_labels], converged: host int32 [n_labels]; select, cfg, iterations,
+   converged and info may be NULL */
+int  dge_svm_fit_vectors(const dge_vectors* v, const uint8_t* y, int32_t n_labels, const uint8_t* select, const dge_svm_cfg* cfg, double* coef, double* bias,
+                         int64_t* iterations, int32_t* converged, dge_svm_info* info);
+/* f(x) of n_models models for every row of x (which may be sv itself; same dim, same device).  coef: host binary64 [n_models x rows(sv)] — rows of sv with
+   coef 0 or NaN are not support and are not read, a coefficient on an absent row is DGE_ERR_ARG; bias: host [n_models], 1 <= n_models <= 4096;
+   out: host binary64 [n_models x rows(x)], NaN on absent rows of x.  The values of sv and x are taken as they are */
+int  dge_svm_decision_vectors(const dge_vectors* sv, const double* coef, const double* bias, int32_t n_models, double gamma, const dge_vectors* x, double* out);
+/* fold: host int32 [rows]; correct, iterations, support: host int64 [n_labels x n_folds], converged: host int32 [n_labels x n_folds]; tested: host int64
+   [n_folds]; decision: host binary64 [n_labels x rows], the held-out f(x) of every used row, NaN elsewhere.  cfg, iterations, support, converged, decision and
+   info may be NULL */
+int  dge_svm_cv_vectors(const dge_vectors* v, const uint8_t* y, int32_t n_labels, const int32_t* fold, int32_t n_folds, const dge_svm_cfg* cfg, int64_t* correct,
+                        int64_t* tested, int64_t* iterations, int64_t* support, int32_t* converged, double* decision, dge_svm_info* info);
+/* the same on host rows float32 [n_rows x dim], every row present (through dge_vectors_from_host); x_features NULL: the rows of sv themselves,
+   and n_x is not looked at */
+int  dge_svm_fit(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* y, int32_t n_labels, const uint8_t* select, const dge_svm_cfg* cfg,
+                 double* coef, double* bias, int64_t* iterations, int32_t* converged, dge_svm_info* info);
+int  dge_svm_decision(int device, const float* sv_features, int64_t n_sv, int32_t dim, const double* coef, const double* bias, int32_t n_models, double gamma,
+                      const float* x_features, int64_t n_x, double* out);
+int  dge_svm_cv(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* y, int32_t n_labels, const int32_t* fold, int32_t n_folds,
+                const dge_svm_cfg* cfg, int64_t* correct, int64_t* tested, int64_t* iterations, int64_t* support, int32_t* converged, double* decision, dge_svm_info* info);
+
+/* ------------------------------------------------------------------------------------------------
  * Ablation / test knobs of the trainer (process-wide relaxed atomics; nothing in a normal run sets them).  value < 0 puts
  * a knob back to the library's own rule.
  * ---------------------------------------------------------------------------------------------- */
