@@ -19,33 +19,6 @@
 #include "cluster_match.h"
 
 #define KM_TILE 64
-#define KM_NONE (~0ULL)
-
-// max |x| over the selected rows as float bits (the bits of non-negative floats order as unsigned integers) and the least selected row that holds a
-// non-finite value (as its number among the selected rows)
-__global__ void k_km_scan(const float* __restrict__ x, const int64_t* __restrict__ sel, int64_t n, int dim, unsigned* __restrict__ max_bits,
-                          unsigned long long* __restrict__ bad) {
-    const size_t total = (size_t)n * (size_t)dim, step = (size_t)gridDim.x * blockDim.x;
-    unsigned m = 0;
-    unsigned long long b = KM_NONE;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
-        const size_t i = e / (size_t)dim, j = e - i * (size_t)dim;
-        const size_t row = sel ? (size_t)sel[i] : i;
-        const unsigned bits = __float_as_uint(x[row * (size_t)dim + j]) & 0x7fffffffu;
-        if (bits >= 0x7f800000u) { if ((unsigned long long)i < b) b = i; }
-        else if (bits > m) m = bits;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned m2 = __shfl_xor(m, o);
-        const unsigned long long b2 = __shfl_xor(b, o);
-        if (m2 > m) m = m2;
-        if (b2 < b) b = b2;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        if (m) atomicMax(max_bits, m);
-        if (b != KM_NONE) atomicMin(bad, b);
-    }
-}
 
 // seeding: d of every selected row to the centre chosen last, dmin = min(dmin, d), and the sum of every block of KM_BLOCK rows' dmin.  A workgroup is one
 // block of the blocked sum; the rows go through LDS 32 columns at a time (32 lanes read 128 consecutive bytes of a row), a lane owns a row.
@@ -271,49 +244,32 @@ static int assign_pass(const float* x, const int64_t* sel, int64_t n, int dim, i
 }
 
 static int kmeans_cfg_check(const char* who, const dge_kmeans_cfg* cfg) {
-    if (cfg->k < 1 || cfg->k > KM_MAX_K) DGE_FAIL(DGE_ERR_ARG, "%s: k = %d is outside 1 .. %d", who, cfg->k, KM_MAX_K);
+    if (int rc = dge_range_check(who, "k", cfg->k, KM_MAX_K)) return rc;
     if (cfg->n_init < 1) DGE_FAIL(DGE_ERR_ARG, "%s: n_init = %d must be at least 1", who, cfg->n_init);
     if (cfg->max_iter < 1) DGE_FAIL(DGE_ERR_ARG, "%s: max_iter = %d must be at least 1", who, cfg->max_iter);
     return DGE_OK;
 }
 
-static int kmeans_run(const char* who, const dge_vectors* v, const uint8_t* select, const dge_kmeans_cfg* cfg, const float* init, int32_t* labels, float* centres,
+// u: the used rows (present and, with a mask, selected)
+static int kmeans_run(const char* who, const dge_vectors* v, const ur_rows& u, const dge_kmeans_cfg* cfg, const float* init, int32_t* labels, float* centres,
                       dge_kmeans_info* info) {
-    int rc = kmeans_cfg_check(who, cfg);
-    if (rc) return rc;
-    if (v->dim < 1 || v->dim > KM_MAX_DIM) DGE_FAIL(DGE_ERR_ARG, "%s: dim = %d is outside 1 .. %d", who, v->dim, KM_MAX_DIM);
-    if (select == nullptr && v->n_present < cfg->k) DGE_FAIL(DGE_ERR_ARG, "%s: k = %d exceeds the %lld selected rows", who, cfg->k, (long long)v->n_present);
-    if ((rc = dge_require_device(v->device))) return rc;
+    int rc;
     const int dim = v->dim, k = cfg->k;
-    const int64_t rows = v->rows;
-
-    // the selected rows: present and, with a mask, selected; in ascending order
-    std::vector<int64_t> sel;
-    bool all = select == nullptr && v->n_present == rows;
-    if (!all) {
-        std::vector<uint8_t> pres((size_t)rows);
-        if (rows) DGE_HIP(hipMemcpy(pres.data(), v->d_present, (size_t)rows, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < rows; i++) if (pres[(size_t)i] && (!select || select[i])) sel.push_back(i);
-        all = (int64_t)sel.size() == rows;
-    }
-    const int64_t n = all ? rows : (int64_t)sel.size();
+    const int64_t n = u.n;
     if (n < k) DGE_FAIL(DGE_ERR_ARG, "%s: k = %d exceeds the %lld selected rows", who, k, (long long)n);
     if (n > 0x7fffffffLL) DGE_FAIL(DGE_ERR_ARG, "%s: %lld selected rows exceed 2^31 - 1", who, (long long)n);
     const int64_t n_blocks = (n + KM_BLOCK - 1) / KM_BLOCK;
     const size_t kd = (size_t)k * (size_t)dim;
 
-    dge_tmp<int64_t> d_sel;
-    dge_tmp<unsigned> d_max, d_changed;
+    dge_used_rows d_sel;
+    dge_tmp<unsigned> d_changed;
     dge_tmp<unsigned long long> d_bad, d_S, d_count;
     dge_tmp<double> d_dmin, d_bs, d_dist[2];
     dge_tmp<int32_t> d_lab[2];
     dge_tmp<float> d_cen[2];
-    if (!all) {
-        if ((rc = d_sel.alloc((size_t)n))) return rc;
-        DGE_HIP(hipMemcpy(d_sel.p, sel.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    const int64_t* dsel = all ? nullptr : d_sel.p;
-    if ((rc = d_max.alloc(1)) || (rc = d_changed.alloc(1)) || (rc = d_bad.alloc(1)) || (rc = d_S.alloc(kd)) || (rc = d_count.alloc((size_t)k)) ||
+    if ((rc = d_sel.upload(u, nullptr))) return rc;
+    const int64_t* dsel = d_sel.p;
+    if ((rc = d_changed.alloc(1)) || (rc = d_bad.alloc(2)) || (rc = d_S.alloc(kd)) || (rc = d_count.alloc((size_t)k)) ||
         (rc = d_dmin.alloc((size_t)n)) || (rc = d_bs.alloc((size_t)n_blocks)) || (rc = d_dist[0].alloc((size_t)n)) || (rc = d_dist[1].alloc((size_t)n)) ||
         (rc = d_lab[0].alloc((size_t)n)) || (rc = d_lab[1].alloc((size_t)n)) || (rc = d_cen[0].alloc(kd)) || (rc = d_cen[1].alloc(kd))) return rc;
 
@@ -321,19 +277,10 @@ static int kmeans_run(const char* who, const dge_vectors* v, const uint8_t* sele
     if ((rc = watch.start(0))) return rc;
 
     // max |x| and the finite check
-    DGE_HIP(hipMemsetAsync(d_max.p, 0, sizeof(unsigned), 0));
-    DGE_HIP(hipMemsetAsync(d_bad.p, 0xff, sizeof(unsigned long long), 0));
-    {
-        const size_t total = (size_t)n * (size_t)dim;
-        const size_t blocks = (total + 255) / 256;
-        hipLaunchKernelGGL(k_km_scan, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, 0, v->d, dsel, n, dim, d_max.p, d_bad.p);
-        DGE_HIP(hipGetLastError());
-    }
     unsigned max_bits = 0;
-    unsigned long long bad = KM_NONE;
-    DGE_HIP(hipMemcpy(&max_bits, d_max.p, sizeof max_bits, hipMemcpyDeviceToHost));
-    DGE_HIP(hipMemcpy(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad != KM_NONE) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld holds a value that is not finite", who, (long long)(all ? (int64_t)bad : sel[(size_t)bad]));
+    int64_t bad = -1;
+    if ((rc = dge_scan_rows<true>(v->d, dsel, n, dim, d_bad.p, 0, &max_bits, &bad))) return rc;
+    if (bad >= 0) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld holds a value that is not finite", who, (long long)u.at(bad / dim));
     float max_abs;
     memcpy(&max_abs, &max_bits, sizeof max_abs);
     const int s = km_scale_bits(max_abs, n);
@@ -391,11 +338,7 @@ static int kmeans_run(const char* who, const dge_vectors* v, const uint8_t* sele
     std::vector<float> cen(kd);
     DGE_HIP(hipMemcpy(lab.data(), d_lab[best_slot].p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     DGE_HIP(hipMemcpy(cen.data(), d_cen[best_slot].p, kd * sizeof(float), hipMemcpyDeviceToHost));
-    if (all) memcpy(labels, lab.data(), (size_t)n * sizeof(int32_t));
-    else {
-        for (int64_t i = 0; i < rows; i++) labels[i] = -1;
-        for (int64_t i = 0; i < n; i++) labels[sel[(size_t)i]] = lab[(size_t)i];
-    }
+    ur_scatter_back<int32_t>(labels, u, -1, lab.data());
     memcpy(centres, cen.data(), kd * sizeof(float));
     if (info) {
         info->rows = n; info->best_restart = best; info->iterations = best_iter; info->total_iterations = total_iter; info->scale_bits = s;
@@ -404,31 +347,44 @@ static int kmeans_run(const char* who, const dge_vectors* v, const uint8_t* sele
     return DGE_OK;
 }
 
+// what both entries refuse before they look for a device
+static int kmeans_limits(const char* who, const dge_kmeans_cfg* cfg, int32_t dim) {
+    if (int rc = kmeans_cfg_check(who, cfg)) return rc;
+    return dge_range_check(who, "dim", dim, KM_MAX_DIM);
+}
+
 extern "C" int dge_kmeans_vectors(const dge_vectors* v, const uint8_t* select, const dge_kmeans_cfg* cfg, const float* init_centres, int32_t* labels, float* centres,
                                   dge_kmeans_info* info) {
-    if (!v || !cfg || !labels || !centres) DGE_FAIL(DGE_ERR_ARG, "dge_kmeans_vectors: null argument");
-    return kmeans_run("dge_kmeans_vectors", v, select, cfg, init_centres, labels, centres, info);
+    const char* who = "dge_kmeans_vectors";
+    if (!v || !cfg || !labels || !centres) DGE_FAIL(DGE_ERR_ARG, "%s: null argument", who);
+    int rc = kmeans_limits(who, cfg, v->dim);
+    if (rc) return rc;
+    if (select == nullptr && v->n_present < cfg->k) DGE_FAIL(DGE_ERR_ARG, "%s: k = %d exceeds the %lld selected rows", who, cfg->k, (long long)v->n_present);
+    if ((rc = dge_require_device(v->device))) return rc;
+    dge_present pres;
+    if ((rc = pres.load(v))) return rc;
+    ur_rows u;
+    ur_intake(ur_in{v->rows, pres.p, select}, &u);
+    return kmeans_run(who, v, u, cfg, init_centres, labels, centres, info);
 }
 
 extern "C" int dge_kmeans(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* select, const dge_kmeans_cfg* cfg, const float* init_centres,
                           int32_t* labels, float* centres, dge_kmeans_info* info) {
-    if (!features || !cfg || !labels || !centres || n_rows < 0 || dim < 0) DGE_FAIL(DGE_ERR_ARG, "dge_kmeans: null or negative argument");
-    int rc = kmeans_cfg_check("dge_kmeans", cfg);
+    const char* who = "dge_kmeans";
+    if (!features || !cfg || !labels || !centres || n_rows < 0 || dim < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
+    int rc = kmeans_limits(who, cfg, dim);
     if (rc) return rc;
-    if (dim < 1 || dim > KM_MAX_DIM) DGE_FAIL(DGE_ERR_ARG, "dge_kmeans: dim = %d is outside 1 .. %d", dim, KM_MAX_DIM);
-    int64_t n = n_rows;
-    if (select) { n = 0; for (int64_t i = 0; i < n_rows; i++) n += select[i] ? 1 : 0; }
-    if (n < cfg->k) DGE_FAIL(DGE_ERR_ARG, "dge_kmeans: k = %d exceeds the %lld selected rows", cfg->k, (long long)n);
-    dge_vectors* v = nullptr;
-    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &v))) return rc;
-    rc = kmeans_run("dge_kmeans", v, select, cfg, init_centres, labels, centres, info);
-    dge_vectors_free(v);
-    return rc;
+    ur_rows u;
+    ur_intake(ur_in{n_rows, nullptr, select}, &u);
+    if (u.n < cfg->k) DGE_FAIL(DGE_ERR_ARG, "%s: k = %d exceeds the %lld selected rows", who, cfg->k, (long long)u.n);
+    dge_vectors_guard g;
+    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &g.v))) return rc;
+    return kmeans_run(who, g.v, u, cfg, init_centres, labels, centres, info);
 }
 
 extern "C" int dge_cluster_accuracy(const int32_t* labels, const int32_t* gnd, int64_t n_rows, int32_t k, int64_t* cnt, int32_t* map, double* accuracy) {
     if (!labels || !gnd || !accuracy || n_rows < 0) DGE_FAIL(DGE_ERR_ARG, "dge_cluster_accuracy: null or negative argument");
-    if (k < 1 || k > KM_MAX_K) DGE_FAIL(DGE_ERR_ARG, "dge_cluster_accuracy: k = %d is outside 1 .. %d", k, KM_MAX_K);
+    if (int rc = dge_range_check("dge_cluster_accuracy", "k", k, KM_MAX_K)) return rc;
     std::vector<int64_t> table((size_t)k * (size_t)k);
     std::vector<int32_t> m((size_t)k, -1);
     int64_t n_gnd = 0;

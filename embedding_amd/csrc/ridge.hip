@@ -3,7 +3,6 @@
 // per-element pieces live in ridge_rule.h; this file is what runs them at full concurrency without changing a bit: every element's chain keeps the order the
 // rule fixes, whatever the schedule around it.  Plain binary64 VALU fma throughout — no MFMA (its accumulation order is not ours to fix), no floating-point
 // atomic.
-//   k_rg_scan      the least used row that holds a feature that is not finite
 //   k_rg_moments   a workgroup takes one block of 256 used rows and one 64 x 64 square of the moments of [Z | Y]: the rows go through LDS 32 at a time, a thread
 //                  holds a 4 x 4 register tile and runs each entry's 256-row chain; k_rg_fold adds a chunk's block partials, in block order, to the totals
 //   k_rg_factor    one workgroup per lambda: LDL' left-looking, column by column, L kept column-major (the lanes that own rows i read it coalesced) and
@@ -21,7 +20,6 @@
 #include "dge_device.h"
 #include "ridge_rule.h"
 
-#define RG_NONE (~0ULL)
 #define RG_TILE 64              // a workgroup's square of moment entries
 #define RG_STEP 32              // rows of a block in LDS at a time
 #define RG_ROWS 4               // rows of one wave-batch of the leverage kernel
@@ -29,19 +27,6 @@
 #define RG_MAX_MODELS (RG_MAX_LAMBDA * RG_MAX_TARGETS)
 
 extern std::atomic<int64_t> g_dge_tuning[DGE_TUNE_COUNT];      // sgns.hip: the knobs of dge_set_tuning, -1 = the library's own rule
-
-// the least used row (as its number among the used rows) that holds a value that is not finite
-__global__ void k_rg_scan(const float* __restrict__ x, const int64_t* __restrict__ sel, int64_t n, int dim, unsigned long long* __restrict__ bad) {
-    const size_t total = (size_t)n * (size_t)dim, step = (size_t)gridDim.x * blockDim.x;
-    unsigned long long b = RG_NONE;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
-        const size_t i = e / (size_t)dim, j = e - i * (size_t)dim;
-        const size_t row = sel ? (size_t)sel[i] : i;
-        if ((__float_as_uint(x[row * (size_t)dim + j]) & 0x7fffffffu) >= 0x7f800000u && (unsigned long long)i < b) b = i;
-    }
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long b2 = __shfl_xor(b, o); if (b2 < b) b = b2; }
-    if ((threadIdx.x & 63) == 0 && b != RG_NONE) atomicMin(bad, b);
-}
 
 // column c of [Z | Y] for one used row: 1, the features, the targets; 0 from column `lim` on
 __device__ __forceinline__ double rg_col(const float* xr, const double* yr, int P, int lim, int c) {
@@ -321,62 +306,34 @@ static void launch_leverage(const float* x, const int64_t* sel, int64_t n, int d
     }
 
 static int ridge_limits(const char* who, int dim, int n_targets, const double* lambda, int n_lambda) {
-    if (dim < 1 || dim > RG_MAX_DIM) DGE_FAIL(DGE_ERR_ARG, "%s: dim = %d is outside 1 .. %d", who, dim, RG_MAX_DIM);
-    if (n_targets < 1 || n_targets > RG_MAX_TARGETS) DGE_FAIL(DGE_ERR_ARG, "%s: n_targets = %d is outside 1 .. %d", who, n_targets, RG_MAX_TARGETS);
-    if (n_lambda < 1 || n_lambda > RG_MAX_LAMBDA) DGE_FAIL(DGE_ERR_ARG, "%s: n_lambda = %d is outside 1 .. %d", who, n_lambda, RG_MAX_LAMBDA);
+    int rc = dge_range_check(who, "dim", dim, RG_MAX_DIM);
+    if (rc || (rc = dge_range_check(who, "n_targets", n_targets, RG_MAX_TARGETS)) || (rc = dge_range_check(who, "n_lambda", n_lambda, RG_MAX_LAMBDA))) return rc;
     for (int l = 0; l < n_lambda; l++)
         if (!(lambda[l] >= 0.0) || !(lambda[l] <= 1.7976931348623157e308)) DGE_FAIL(DGE_ERR_ARG, "%s: lambda[%d] = %g is not a finite number >= 0", who, l, lambda[l]);
     return DGE_OK;
 }
 
-static inline bool rg_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN
-
-static int ridge_run(const char* who, const dge_vectors* v, const double* y, int T, const uint8_t* select, const double* lambda, int nl, double* mae, double* mre,
-                     double* beta, double* loo_pred, dge_ridge_info* info) {
-    int rc = ridge_limits(who, v->dim, T, lambda, nl);
-    if (rc) return rc;
-    if ((rc = dge_require_device(v->device))) return rc;
+// u: the used rows (present and, with a mask, selected) with the first of them that holds a target that is not finite
+static int ridge_run(const char* who, const dge_vectors* v, const ur_rows& u, const double* y, int T, const double* lambda, int nl, double* mae, double* mre, double* beta,
+                     double* loo_pred, dge_ridge_info* info) {
+    int rc;
     const int dim = v->dim, P = dim + 1, W = P + T, models = nl * T;
-    const int64_t rows = v->rows;
-
-    // the used rows: present and, with a mask, selected; in ascending order
-    std::vector<int64_t> sel;
-    bool all = select == nullptr && v->n_present == rows;
-    if (!all) {
-        std::vector<uint8_t> pres((size_t)rows);
-        if (rows) DGE_HIP(hipMemcpy(pres.data(), v->d_present, (size_t)rows, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < rows; i++) if (pres[(size_t)i] && (!select || select[i])) sel.push_back(i);
-        all = (int64_t)sel.size() == rows;
-    }
-    const int64_t n = all ? rows : (int64_t)sel.size();
+    const int64_t rows = v->rows, n = u.n;
     if (n < 2) DGE_FAIL(DGE_ERR_ARG, "%s: %lld used rows; leave-one-out needs at least 2", who, (long long)n);
     if (n > 0x7fffffffLL) DGE_FAIL(DGE_ERR_ARG, "%s: %lld used rows exceed 2^31 - 1", who, (long long)n);
     const int64_t n_blocks = (n + RG_BLOCK - 1) / RG_BLOCK;
     const int64_t knob = g_dge_tuning[DGE_TUNE_RIDGE_CHUNK];
     const int64_t chunk = std::min<int64_t>(knob > 0 ? knob : RG_DEFAULT_CHUNK, n_blocks);
     const int64_t n_chunks = (n_blocks + chunk - 1) / chunk;
-
-    // the used rows' targets, and the least used row with one that is not finite
-    std::vector<double> yu((size_t)n * (size_t)T);
-    int64_t bad_y = -1;
-    for (int64_t i = 0; i < n; i++) {
-        const double* yr = y + (size_t)(all ? i : sel[(size_t)i]) * (size_t)T;
-        for (int t = 0; t < T; t++) {
-            yu[(size_t)i * T + t] = yr[t];
-            if (bad_y < 0 && !rg_finite(yr[t])) bad_y = i;
-        }
-    }
+    const std::vector<double> yu = ur_gather_targets(u, y, T);
 
     const size_t PW = (size_t)P * W, PP = (size_t)P * P;
-    dge_tmp<int64_t> d_sel;
+    dge_used_rows d_sel;
     dge_tmp<unsigned long long> d_bad;                        // [0]: the scan's, [1 .. nl]: the leverage's, [nl + 1]: the greatest h
     dge_tmp<int> d_fail;
     dge_tmp<double> d_y, d_lambda, d_part, d_M, d_Lc, d_Lr, d_d, d_inv, d_beta, d_h, d_out, d_bs;
-    if (!all) {
-        if ((rc = d_sel.alloc((size_t)n))) return rc;
-        DGE_HIP(hipMemcpy(d_sel.p, sel.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    const int64_t* dsel = all ? nullptr : d_sel.p;
+    if ((rc = d_sel.upload(u, nullptr))) return rc;
+    const int64_t* dsel = d_sel.p;
     if ((rc = d_bad.alloc((size_t)nl + 2)) || (rc = d_fail.alloc((size_t)nl)) || (rc = d_y.alloc(yu.size())) || (rc = d_lambda.alloc((size_t)nl)) ||
         (rc = d_part.alloc((size_t)chunk * PW)) || (rc = d_M.alloc(PW)) || (rc = d_Lc.alloc((size_t)nl * PP)) || (rc = d_Lr.alloc((size_t)nl * PP)) ||
         (rc = d_d.alloc((size_t)nl * P)) || (rc = d_inv.alloc((size_t)nl * P)) || (rc = d_beta.alloc((size_t)models * P)) || (rc = d_h.alloc((size_t)nl * (size_t)n)) ||
@@ -386,19 +343,13 @@ static int ridge_run(const char* who, const dge_vectors* v, const double* y, int
 
     dge_stopwatch watch;
     if ((rc = watch.start(0))) return rc;
-    DGE_HIP(hipMemsetAsync(d_bad.p, 0xff, ((size_t)nl + 1) * sizeof(unsigned long long), 0));
     DGE_HIP(hipMemsetAsync(d_bad.p + nl + 1, 0, sizeof(unsigned long long), 0));
     DGE_HIP(hipMemsetAsync(d_fail.p, 0xff, (size_t)nl * sizeof(int), 0));
-    {
-        const size_t blocks = ((size_t)n * (size_t)dim + 255) / 256;
-        hipLaunchKernelGGL(k_rg_scan, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, 0, v->d, dsel, n, dim, d_bad.p);
-        DGE_HIP(hipGetLastError());
-    }
-    unsigned long long bad_x = RG_NONE;
-    DGE_HIP(hipMemcpy(&bad_x, d_bad.p, sizeof bad_x, hipMemcpyDeviceToHost));
-    if (bad_x != RG_NONE || bad_y >= 0) {
-        const int64_t i = bad_x == RG_NONE ? bad_y : (bad_y < 0 ? (int64_t)bad_x : std::min<int64_t>((int64_t)bad_x, bad_y));
-        DGE_FAIL(DGE_ERR_ARG, "%s: row %lld holds a feature or a target that is not finite", who, (long long)(all ? i : sel[(size_t)i]));
+    int64_t bad_x = -1;
+    if ((rc = dge_scan_rows<false>(v->d, dsel, n, dim, d_bad.p, nl, nullptr, &bad_x))) return rc;      // the leverage's nl words are armed with the scan's
+    if (bad_x >= 0 || u.kind == UR_TARGET) {
+        const int64_t ix = bad_x < 0 ? -1 : u.at(bad_x / dim);
+        DGE_FAIL(DGE_ERR_ARG, "%s: row %lld holds a feature or a target that is not finite", who, (long long)(ix < 0 || (u.kind == UR_TARGET && u.bad_row < ix) ? u.bad_row : ix));
     }
 
     // moments: chunk by chunk, the block partials folded in block order
@@ -425,11 +376,9 @@ static int ridge_run(const char* who, const dge_vectors* v, const double* y, int
     std::vector<unsigned long long> lev((size_t)nl + 1);
     DGE_HIP(hipMemcpy(lev.data(), d_bad.p + 1, ((size_t)nl + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     for (int l = 0; l < nl; l++)
-        if (lev[(size_t)l] != RG_NONE) {
-            const int64_t i = (int64_t)lev[(size_t)l];
+        if (lev[(size_t)l] != ~0ULL)
             DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has leverage 1 under lambda[%d] = %g: leaving it out leaves nothing to predict it from", who,
-                     (long long)(all ? i : sel[(size_t)i]), l, lambda[l]);
-        }
+                     (long long)u.at((int64_t)lev[(size_t)l]), l, lambda[l]);
 
     hipLaunchKernelGGL(k_rg_predict, dim3((unsigned)n_blocks, (unsigned)models), dim3(RG_BLOCK), 0, 0, v->d, dsel, (const uint8_t*)nullptr, n, dim, d_beta.p, d_y.p, T, d_h.p,
                        d_out.p, d_bs.p);
@@ -452,17 +401,8 @@ static int ridge_run(const char* who, const dge_vectors* v, const double* y, int
         mre[m] = mae[m] / (c0[(size_t)(m % T)] / (double)n);
     }
     if (beta) memcpy(beta, bet.data(), bet.size() * sizeof(double));
-    if (loo_pred) {
-        for (int m = 0; m < models; m++) {
-            double* o = loo_pred + (size_t)m * (size_t)rows;
-            const double* s = out.data() + (size_t)m * (size_t)n;
-            if (all) memcpy(o, s, (size_t)n * sizeof(double));
-            else {
-                for (int64_t i = 0; i < rows; i++) o[i] = (double)NAN;
-                for (int64_t i = 0; i < n; i++) o[sel[(size_t)i]] = s[i];
-            }
-        }
-    }
+    if (loo_pred)
+        for (int m = 0; m < models; m++) ur_scatter_back(loo_pred + (size_t)m * (size_t)rows, u, (double)NAN, out.data() + (size_t)m * (size_t)n);
     if (info) {
         info->rows = n; info->blocks = n_blocks; info->chunks = n_chunks;
         info->min_pivot = dd[0];
@@ -475,8 +415,15 @@ static int ridge_run(const char* who, const dge_vectors* v, const double* y, int
 
 extern "C" int dge_ridge_loo_vectors(const dge_vectors* v, const double* y, int32_t n_targets, const uint8_t* select, const double* lambda, int32_t n_lambda, double* mae,
                                      double* mre, double* beta, double* loo_pred, dge_ridge_info* info) {
-    if (!v || !y || !lambda || !mae || !mre) DGE_FAIL(DGE_ERR_ARG, "dge_ridge_loo_vectors: null argument");
-    return ridge_run("dge_ridge_loo_vectors", v, y, n_targets, select, lambda, n_lambda, mae, mre, beta, loo_pred, info);
+    const char* who = "dge_ridge_loo_vectors";
+    if (!v || !y || !lambda || !mae || !mre) DGE_FAIL(DGE_ERR_ARG, "%s: null argument", who);
+    int rc = ridge_limits(who, v->dim, n_targets, lambda, n_lambda);
+    if (rc || (rc = dge_require_device(v->device))) return rc;
+    dge_present pres;
+    if ((rc = pres.load(v))) return rc;
+    ur_rows u;
+    ur_intake(ur_in{v->rows, pres.p, select, nullptr, 0, nullptr, 0, y, n_targets}, &u);
+    return ridge_run(who, v, u, y, n_targets, lambda, n_lambda, mae, mre, beta, loo_pred, info);
 }
 
 extern "C" int dge_ridge_loo(int device, const float* features, int64_t n_rows, int32_t dim, const double* y, int32_t n_targets, const uint8_t* select, const double* lambda,
@@ -485,28 +432,20 @@ extern "C" int dge_ridge_loo(int device, const float* features, int64_t n_rows, 
     if (!features || !y || !lambda || !mae || !mre || n_rows < 0 || dim < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     int rc = ridge_limits(who, dim, n_targets, lambda, n_lambda);
     if (rc) return rc;
-    int64_t n = 0;
-    for (int64_t i = 0; i < n_rows; i++) {
-        if (select && !select[i]) continue;
-        for (int t = 0; t < n_targets; t++)
-            if (!rg_finite(y[(size_t)i * n_targets + t])) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld holds a feature or a target that is not finite", who, (long long)i);
-        n++;
-    }
-    if (n < 2) DGE_FAIL(DGE_ERR_ARG, "%s: %lld used rows; leave-one-out needs at least 2", who, (long long)n);
-    dge_vectors* v = nullptr;
-    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &v))) return rc;
-    rc = ridge_run(who, v, y, n_targets, select, lambda, n_lambda, mae, mre, beta, loo_pred, info);
-    dge_vectors_free(v);
-    return rc;
+    ur_rows u;
+    ur_intake(ur_in{n_rows, nullptr, select, nullptr, 0, nullptr, 0, y, n_targets}, &u);
+    if (u.kind == UR_TARGET) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld holds a feature or a target that is not finite", who, (long long)u.bad_row);
+    if (u.n < 2) DGE_FAIL(DGE_ERR_ARG, "%s: %lld used rows; leave-one-out needs at least 2", who, (long long)u.n);
+    dge_vectors_guard g;
+    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &g.v))) return rc;
+    return ridge_run(who, g.v, u, y, n_targets, lambda, n_lambda, mae, mre, beta, loo_pred, info);
 }
 
 extern "C" int dge_ridge_predict_vectors(const dge_vectors* v, const double* beta, int32_t n_models, double* out) {
     const char* who = "dge_ridge_predict_vectors";
     if (!v || !beta || !out) DGE_FAIL(DGE_ERR_ARG, "%s: null argument", who);
-    if (n_models < 1 || n_models > RG_MAX_MODELS) DGE_FAIL(DGE_ERR_ARG, "%s: n_models = %d is outside 1 .. %d", who, n_models, RG_MAX_MODELS);
-    if (v->dim < 1 || v->dim > RG_MAX_DIM) DGE_FAIL(DGE_ERR_ARG, "%s: dim = %d is outside 1 .. %d", who, v->dim, RG_MAX_DIM);
-    int rc;
-    if ((rc = dge_require_device(v->device))) return rc;
+    int rc = dge_range_check(who, "n_models", n_models, RG_MAX_MODELS);
+    if (rc || (rc = dge_range_check(who, "dim", v->dim, RG_MAX_DIM)) || (rc = dge_require_device(v->device))) return rc;
     if (v->rows == 0) return DGE_OK;
     if (v->rows > 0x7fffffffLL * RG_BLOCK) DGE_FAIL(DGE_ERR_ARG, "%s: %lld rows exceed 2^39", who, (long long)v->rows);
     const int P = v->dim + 1;

@@ -27,7 +27,6 @@
 #define SV_MAX_WAVES 16
 #define SV_LAUNCH_ITERS 1024      // the default slice
 #define SV_LAUNCH_CAP 65536       // and the longest one
-#define SV_BAD_NONE (~0ULL)
 
 struct sv_ctl {                   // a problem between two launches
     int64_t iters;
@@ -36,17 +35,6 @@ struct sv_ctl {                   // a problem between two launches
 };
 
 // ------------------------------------------------------------------------------------------ once per call
-// the least (used row, column) of a value that is not finite
-__global__ void k_sv_check(const float* __restrict__ x, const int64_t* __restrict__ used, int64_t n, int dim, unsigned long long* __restrict__ bad) {
-    const size_t total = (size_t)n * (size_t)dim, step = (size_t)gridDim.x * blockDim.x;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += step) {
-        const size_t i = e / (size_t)dim, c = e - i * (size_t)dim;
-        const size_t row = used ? (size_t)used[i] : i;
-        const uint32_t bits = __float_as_uint(x[row * (size_t)dim + c]);
-        if ((bits & 0x7f800000u) == 0x7f800000u) atomicMin(bad, (unsigned long long)e);
-    }
-}
-
 // HOT.  grid (ceil(n / 16), ceil(n / 16)), 256 lanes: lane (ti, tj) of the tile takes the chain of K(i, j).  Both halves of the matrix are computed: t only
 // changes sign between them, so the bits are equal.  Rows past n read as 0 and write nothing.
 __global__ void __launch_bounds__(256) k_sv_kernel(const float* __restrict__ x, const int64_t* __restrict__ used, int n, int dim, double gamma, double* __restrict__ K) {
@@ -264,16 +252,6 @@ __global__ void __launch_bounds__(64) k_sv_decide(const double* __restrict__ K, 
 }
 
 // ------------------------------------------------------------------------------------------ host
-template <typename T>
-static int sv_alloc(dge_tmp<T>& t, size_t n, const char* who) {
-    if (t.p) { (void)hipFree(t.p); t.p = nullptr; }
-    if (n == 0) n = 1;
-    const hipError_t e = hipMalloc((void**)&t.p, n * sizeof(T));
-    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); t.p = nullptr; DGE_FAIL(DGE_ERR_CAP, "%s: %zu bytes of device memory do not fit", who, n * sizeof(T)); }
-    DGE_HIP(e);
-    return DGE_OK;
-}
-
 static int svm_cfg_check(const char* who, const dge_svm_cfg* cfg, int32_t dim, dge_svm_cfg* c) {
     c->C = 1.0; c->gamma = dim > 0 ? 1.0 / (double)dim : 1.0; c->eps = 1e-3; c->max_iter = 10000000; c->state = 0; c->launch_iters = 0;
     if (!cfg) return DGE_OK;
@@ -286,30 +264,30 @@ static int svm_cfg_check(const char* who, const dge_svm_cfg* cfg, int32_t dim, d
     *c = *cfg;
     return DGE_OK;
 }
-static int svm_dim_check(const char* who, int32_t dim) {
-    if (dim < 1 || dim > SV_MAX_DIM) DGE_FAIL(DGE_ERR_ARG, "%s: dim = %d is outside 1 .. %d", who, dim, SV_MAX_DIM);
-    return DGE_OK;
-}
-static int svm_labels_check(const char* who, int32_t n_labels) {
-    if (n_labels < 1 || n_labels > SV_MAX_LABELS) DGE_FAIL(DGE_ERR_ARG, "%s: n_labels = %d is outside 1 .. %d", who, n_labels, SV_MAX_LABELS);
-    return DGE_OK;
-}
-static int svm_folds_check(const char* who, int32_t n_folds) {
-    if (n_folds < 1 || n_folds > SV_MAX_FOLDS) DGE_FAIL(DGE_ERR_ARG, "%s: n_folds = %d is outside 1 .. %d", who, n_folds, SV_MAX_FOLDS);
-    return DGE_OK;
-}
-static int svm_count_check(const char* who, int64_t n) {
+
+// The walk of both fits and both cross-validations: pres the present bytes (nullptr: every row); the first offence in the entry's words, then what the count
+// of used rows decides: problem (label, f) trains the used rows with fold != f.
+static int svm_intake(const char* who, int64_t rows, const uint8_t* pres, const uint8_t* y, int32_t n_labels, const uint8_t* select, const int32_t* fold, int32_t n_folds,
+                      const dge_svm_cfg& cfg, ur_rows* u) {
+    ur_intake(ur_in{rows, pres, select, fold, n_folds, y, n_labels}, u);
+    if (!fold) ur_no_folds(u);
+    if (u->kind == UR_FOLD) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has fold %d, outside -1 .. %d", who, (long long)u->bad_row, u->bad_value, n_folds - 1);
+    if (u->kind == UR_LABEL) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has label %d in column %d; labels are 0 or 1", who, (long long)u->bad_row, u->bad_value, u->bad_col);
+    const int64_t n = u->n;
     if (n < 2) DGE_FAIL(DGE_ERR_ARG, "%s: %lld used rows; at least 2 are needed", who, (long long)n);
     if (n > SV_MAX_ROWS) DGE_FAIL(DGE_ERR_RANGE, "%s: %lld used rows; at most %d may (the kernel matrix is held whole)", who, (long long)n, SV_MAX_ROWS);
+    for (size_t f = 0; f < u->tested.size(); f++)
+        if (n - u->tested[f] == 0) DGE_FAIL(DGE_ERR_ARG, "%s: fold %d has no training rows", who, (int)f);
+    if (cfg.state == 1 && n > SV_LDS_ROWS) DGE_FAIL(DGE_ERR_ARG, "%s: state = 1 holds at most %d used rows in LDS; the call has %lld", who, SV_LDS_ROWS, (long long)n);
     return DGE_OK;
 }
-
-static int svm_present(const dge_vectors* v, std::vector<uint8_t>& pres) {
-    pres.clear();
-    if (v->n_present == v->rows) return DGE_OK;
-    pres.resize((size_t)v->rows);
-    if (v->rows) DGE_HIP(hipMemcpy(pres.data(), v->d_present, (size_t)v->rows, hipMemcpyDeviceToHost));
-    return DGE_OK;
+// a *_vectors entry behind its limit checks: the device, the present bytes, the walk
+static int svm_vectors_intake(const char* who, const dge_vectors* v, const uint8_t* y, int32_t n_labels, const uint8_t* select, const int32_t* fold, int32_t n_folds,
+                              const dge_svm_cfg& cfg, ur_rows* u) {
+    int rc = dge_require_device(v->device);
+    dge_present pres;
+    if (rc || (rc = pres.load(v))) return rc;
+    return svm_intake(who, v->rows, pres.p, y, n_labels, select, fold, n_folds, cfg, u);
 }
 
 struct svm_out {              // per problem p = label * F + f; per (label, used row) where it says so
@@ -322,44 +300,26 @@ struct svm_out {              // per problem p = label * F + f; per (label, used
     float ms = 0.f;
 };
 
-// The used rows (numbers among all rows, ascending; all = true: every row), their labels yu [n_labels x n] and folds fu [n] (-1: trains every problem):
-// the problems (label, f), f < F.  decide: the held-out decision of every used row, and the votes that equal the label per problem.
-static int svm_run(const char* who, const dge_vectors* v, bool all, const std::vector<int64_t>& used, const std::vector<uint8_t>& yu, const std::vector<int32_t>& fu, int n_labels,
-                   int F, const dge_svm_cfg& cfg, bool decide, bool want_coef, svm_out* out) {
+// The used rows u (svm_intake has passed them), their labels yu [n_labels x n] and folds u.fold [n] (-1: trains every problem): the problems (label, f), f < F.
+// decide: the held-out decision of every used row, and the votes that equal the label per problem.
+static int svm_run(const char* who, const dge_vectors* v, const ur_rows& u, const std::vector<uint8_t>& yu, int n_labels, int F, const dge_svm_cfg& cfg, bool decide,
+                   bool want_coef, svm_out* out) {
+    const std::vector<int32_t>& fu = u.fold;
     const int dim = v->dim;
-    const int n = (int)fu.size();
+    const int n = (int)u.n;
     const int P = n_labels * F;
     int rc;
-    for (int f = 0; f < F; f++) {
-        int64_t train = 0;
-        for (int t = 0; t < n; t++) if (fu[(size_t)t] != f) train++;
-        if (train == 0) DGE_FAIL(DGE_ERR_ARG, "%s: fold %d has no training rows", who, f);
-    }
     const bool lds = cfg.state == 1 || (cfg.state == 0 && n <= SV_LDS_ROWS);
-    if (cfg.state == 1 && n > SV_LDS_ROWS) DGE_FAIL(DGE_ERR_ARG, "%s: state = 1 holds at most %d used rows in LDS; the call has %d", who, SV_LDS_ROWS, n);
     const int slice = cfg.launch_iters == 0 ? SV_LAUNCH_ITERS : std::min<int>(cfg.launch_iters, SV_LAUNCH_CAP);
 
     // the values first: a table that is refused pays for the row numbers and one word, not for the kernel matrix
-    dge_tmp<int64_t> d_used;
+    dge_used_rows d_used;
     dge_tmp<unsigned long long> d_bad, d_correct;
-    if (!all) {
-        if ((rc = sv_alloc(d_used, (size_t)n, who))) return rc;
-        DGE_HIP(hipMemcpy(d_used.p, used.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    const int64_t* dused = all ? nullptr : d_used.p;
-    if ((rc = sv_alloc(d_bad, 1, who))) return rc;
-    DGE_HIP(hipMemsetAsync(d_bad.p, 0xff, sizeof(unsigned long long), 0));
-    {
-        const size_t blocks = ((size_t)n * (size_t)dim + 255) / 256;
-        hipLaunchKernelGGL(k_sv_check, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, 0, v->d, dused, (int64_t)n, dim, d_bad.p);
-        DGE_HIP(hipGetLastError());
-    }
-    unsigned long long bad = SV_BAD_NONE;
-    DGE_HIP(hipMemcpy(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad != SV_BAD_NONE) {
-        const int64_t i = (int64_t)(bad / (unsigned long long)dim);
-        DGE_FAIL(DGE_ERR_ARG, "%s: row %lld, column %lld holds a value that is not finite", who, (long long)(all ? i : used[(size_t)i]), (long long)(bad % (unsigned long long)dim));
-    }
+    if ((rc = d_used.upload(u, who)) || (rc = dge_alloc_for(d_bad, 1, who))) return rc;
+    const int64_t* dused = d_used.p;
+    int64_t bad = -1;
+    if ((rc = dge_scan_rows<false>(v->d, dused, n, dim, d_bad.p, 0, nullptr, &bad))) return rc;
+    if (bad >= 0) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld, column %lld holds a value that is not finite", who, (long long)u.at(bad / dim), (long long)(bad % dim));
 
     const size_t nn = (size_t)n * (size_t)n, Pn = (size_t)P * (size_t)n;
     size_t free_b = 0, total_b = 0;
@@ -373,10 +333,10 @@ static int svm_run(const char* who, const dge_vectors* v, bool all, const std::v
     dge_tmp<double> d_K, d_alpha, d_G, d_supc, d_coef, d_dec;
     dge_tmp<int8_t> d_sgn;
     dge_tmp<sv_ctl> d_ctl;
-    if ((rc = sv_alloc(d_y, (size_t)n_labels * (size_t)n, who)) || (rc = sv_alloc(d_fold, (size_t)n, who)) || (rc = sv_alloc(d_K, nn, who)) ||
-        (rc = sv_alloc(d_alpha, Pn, who)) || (rc = sv_alloc(d_G, Pn, who)) || (rc = sv_alloc(d_sgn, Pn, who)) || (rc = sv_alloc(d_ctl, (size_t)P, who)) ||
-        (rc = sv_alloc(d_active, 1, who)) || (rc = sv_alloc(d_sup, Pn, who)) || (rc = sv_alloc(d_supc, Pn, who)) || (rc = sv_alloc(d_nsup, (size_t)P, who)) ||
-        (rc = sv_alloc(d_coef, Pn, who)) || (rc = sv_alloc(d_correct, (size_t)P, who)) || (rc = sv_alloc(d_dec, decide ? (size_t)n_labels * (size_t)n : 1, who))) return rc;
+    if ((rc = dge_alloc_for(d_y, (size_t)n_labels * (size_t)n, who)) || (rc = dge_alloc_for(d_fold, (size_t)n, who)) || (rc = dge_alloc_for(d_K, nn, who)) ||
+        (rc = dge_alloc_for(d_alpha, Pn, who)) || (rc = dge_alloc_for(d_G, Pn, who)) || (rc = dge_alloc_for(d_sgn, Pn, who)) || (rc = dge_alloc_for(d_ctl, (size_t)P, who)) ||
+        (rc = dge_alloc_for(d_active, 1, who)) || (rc = dge_alloc_for(d_sup, Pn, who)) || (rc = dge_alloc_for(d_supc, Pn, who)) || (rc = dge_alloc_for(d_nsup, (size_t)P, who)) ||
+        (rc = dge_alloc_for(d_coef, Pn, who)) || (rc = dge_alloc_for(d_correct, (size_t)P, who)) || (rc = dge_alloc_for(d_dec, decide ? (size_t)n_labels * (size_t)n : 1, who))) return rc;
     DGE_HIP(hipMemcpy(d_y.p, yu.data(), (size_t)n_labels * (size_t)n, hipMemcpyHostToDevice));
     DGE_HIP(hipMemcpy(d_fold.p, fu.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
 
@@ -453,67 +413,25 @@ static void svm_fill_info(dge_svm_info* info, int64_t rows, const svm_out& o) {
     info->kernel_bytes = rows * rows * 8; info->launches = o.launches; info->kernel_ms = o.ms;
 }
 
-static double sv_nan() { return __builtin_nan(""); }
-
-static int svm_fit_run(const char* who, const dge_vectors* v, const uint8_t* y, int32_t n_labels, const uint8_t* select, const dge_svm_cfg& cfg, double* coef, double* bias,
+static int svm_fit_run(const char* who, const dge_vectors* v, const ur_rows& u, const uint8_t* y, int32_t n_labels, const dge_svm_cfg& cfg, double* coef, double* bias,
                        int64_t* iterations, int32_t* converged, dge_svm_info* info) {
-    int rc;
-    if ((rc = svm_dim_check(who, v->dim))) return rc;
-    if ((rc = dge_require_device(v->device))) return rc;
-    std::vector<uint8_t> pres;
-    if ((rc = svm_present(v, pres))) return rc;
-    std::vector<int64_t> used;
-    for (int64_t i = 0; i < v->rows; i++) {
-        if ((!pres.empty() && !pres[(size_t)i]) || (select && !select[i])) continue;
-        for (int l = 0; l < n_labels; l++)
-            if (y[(size_t)l * (size_t)v->rows + (size_t)i] > 1) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has label %d in column %d; labels are 0 or 1", who, (long long)i, (int)y[(size_t)l * (size_t)v->rows + (size_t)i], l);
-        used.push_back(i);
-    }
-    const int64_t n = (int64_t)used.size();
-    if ((rc = svm_count_check(who, n))) return rc;
-    std::vector<uint8_t> yu((size_t)n_labels * (size_t)n);
-    for (int l = 0; l < n_labels; l++)
-        for (int64_t t = 0; t < n; t++) yu[(size_t)l * (size_t)n + (size_t)t] = y[(size_t)l * (size_t)v->rows + (size_t)used[(size_t)t]];
-    std::vector<int32_t> fu((size_t)n, -1);
     svm_out o;
-    if ((rc = svm_run(who, v, n == v->rows, used, yu, fu, n_labels, 1, cfg, false, true, &o))) return rc;
+    if (int rc = svm_run(who, v, u, ur_gather_labels(u, y, n_labels), n_labels, 1, cfg, false, true, &o)) return rc;
     for (int l = 0; l < n_labels; l++) {
-        double* row = coef + (size_t)l * (size_t)v->rows;
-        for (int64_t i = 0; i < v->rows; i++) row[i] = sv_nan();
-        for (int64_t t = 0; t < n; t++) row[used[(size_t)t]] = o.coef[(size_t)l * (size_t)n + (size_t)t];
+        ur_scatter_back(coef + (size_t)l * (size_t)v->rows, u, __builtin_nan(""), o.coef.data() + (size_t)l * (size_t)u.n);
         bias[l] = o.bias[(size_t)l];
         if (iterations) iterations[l] = o.iters[(size_t)l];
         if (converged) converged[l] = o.converged[(size_t)l];
     }
-    svm_fill_info(info, n, o);
+    svm_fill_info(info, u.n, o);
     return DGE_OK;
 }
 
-static int svm_cv_run(const char* who, const dge_vectors* v, const uint8_t* y, int32_t n_labels, const int32_t* fold, int32_t n_folds, const dge_svm_cfg& cfg, int64_t* correct,
+static int svm_cv_run(const char* who, const dge_vectors* v, const ur_rows& u, const uint8_t* y, int32_t n_labels, int32_t n_folds, const dge_svm_cfg& cfg, int64_t* correct,
                       int64_t* tested, int64_t* iterations, int64_t* support, int32_t* converged, double* decision, dge_svm_info* info) {
-    int rc;
-    if ((rc = svm_dim_check(who, v->dim))) return rc;
-    for (int64_t i = 0; i < v->rows; i++)
-        if (fold[i] < -1 || fold[i] >= n_folds) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has fold %d, outside -1 .. %d", who, (long long)i, fold[i], n_folds - 1);
-    if ((rc = dge_require_device(v->device))) return rc;
-    std::vector<uint8_t> pres;
-    if ((rc = svm_present(v, pres))) return rc;
-    std::vector<int64_t> used, tst((size_t)n_folds, 0);
-    std::vector<int32_t> fu;
-    for (int64_t i = 0; i < v->rows; i++) {
-        if ((!pres.empty() && !pres[(size_t)i]) || fold[i] < 0) continue;
-        for (int l = 0; l < n_labels; l++)
-            if (y[(size_t)l * (size_t)v->rows + (size_t)i] > 1) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has label %d in column %d; labels are 0 or 1", who, (long long)i, (int)y[(size_t)l * (size_t)v->rows + (size_t)i], l);
-        used.push_back(i); fu.push_back(fold[i]); tst[(size_t)fold[i]]++;
-    }
-    const int64_t n = (int64_t)used.size();
-    if ((rc = svm_count_check(who, n))) return rc;
-    std::vector<uint8_t> yu((size_t)n_labels * (size_t)n);
-    for (int l = 0; l < n_labels; l++)
-        for (int64_t t = 0; t < n; t++) yu[(size_t)l * (size_t)n + (size_t)t] = y[(size_t)l * (size_t)v->rows + (size_t)used[(size_t)t]];
     svm_out o;
-    if ((rc = svm_run(who, v, n == v->rows, used, yu, fu, n_labels, n_folds, cfg, true, false, &o))) return rc;
-    for (int f = 0; f < n_folds; f++) tested[f] = tst[(size_t)f];
+    if (int rc = svm_run(who, v, u, ur_gather_labels(u, y, n_labels), n_labels, n_folds, cfg, true, false, &o)) return rc;
+    for (int f = 0; f < n_folds; f++) tested[f] = u.tested[(size_t)f];
     for (int p = 0; p < n_labels * n_folds; p++) {
         correct[p] = o.correct[(size_t)p];
         if (iterations) iterations[p] = o.iters[(size_t)p];
@@ -521,24 +439,20 @@ static int svm_cv_run(const char* who, const dge_vectors* v, const uint8_t* y, i
         if (converged) converged[p] = o.converged[(size_t)p];
     }
     if (decision)
-        for (int l = 0; l < n_labels; l++) {
-            double* row = decision + (size_t)l * (size_t)v->rows;
-            for (int64_t i = 0; i < v->rows; i++) row[i] = sv_nan();
-            for (int64_t t = 0; t < n; t++) row[used[(size_t)t]] = o.decision[(size_t)l * (size_t)n + (size_t)t];
-        }
-    svm_fill_info(info, n, o);
+        for (int l = 0; l < n_labels; l++) ur_scatter_back(decision + (size_t)l * (size_t)v->rows, u, __builtin_nan(""), o.decision.data() + (size_t)l * (size_t)u.n);
+    svm_fill_info(info, u.n, o);
     return DGE_OK;
 }
 
 static int svm_decision_run(const char* who, const dge_vectors* sv, const double* coef, const double* bias, int32_t n_models, double gamma, const dge_vectors* x, double* out) {
     int rc;
-    if ((rc = svm_dim_check(who, sv->dim))) return rc;
+    if ((rc = dge_range_check(who, "dim", sv->dim, SV_MAX_DIM))) return rc;
     if (x->dim != sv->dim) DGE_FAIL(DGE_ERR_ARG, "%s: the rows of x have %d columns, the support rows %d", who, x->dim, sv->dim);
     if (x->device != sv->device) DGE_FAIL(DGE_ERR_ARG, "%s: x lives on device %d, the support rows on device %d", who, x->device, sv->device);
     if (sv->rows > 0x7fffffffLL / 2 || x->rows > 0x7fffffffLL / 2) DGE_FAIL(DGE_ERR_RANGE, "%s: more than 2^30 rows", who);
     if ((rc = dge_require_device(sv->device))) return rc;
-    std::vector<uint8_t> pres;
-    if ((rc = svm_present(sv, pres))) return rc;
+    dge_present pres;
+    if ((rc = pres.load(sv))) return rc;
     const int64_t R = sv->rows, X = x->rows;
     // the support lists on the host: the rows with a coefficient that is neither 0 nor NaN, ascending
     std::vector<int32_t> sup((size_t)n_models * (size_t)R), nsup((size_t)n_models, 0);
@@ -547,7 +461,7 @@ static int svm_decision_run(const char* who, const dge_vectors* sv, const double
         for (int64_t i = 0; i < R; i++) {
             const double c = coef[(size_t)l * (size_t)R + (size_t)i];
             if (c == 0.0 || c != c) continue;
-            if (!pres.empty() && !pres[(size_t)i]) DGE_FAIL(DGE_ERR_ARG, "%s: model %d has a coefficient on row %lld, which is absent", who, l, (long long)i);
+            if (pres.p && !pres.p[i]) DGE_FAIL(DGE_ERR_ARG, "%s: model %d has a coefficient on row %lld, which is absent", who, l, (long long)i);
             const size_t at = (size_t)l * (size_t)R + (size_t)nsup[(size_t)l]++;
             sup[at] = (int32_t)i; supc[at] = c;
         }
@@ -556,8 +470,8 @@ static int svm_decision_run(const char* who, const dge_vectors* sv, const double
     dge_tmp<int32_t> d_sup, d_nsup;
     dge_tmp<double> d_supc, d_bias, d_out;
     const size_t lists = std::max<size_t>(sup.size(), 1), outs = (size_t)n_models * (size_t)X;
-    if ((rc = sv_alloc(d_sup, lists, who)) || (rc = sv_alloc(d_supc, lists, who)) || (rc = sv_alloc(d_nsup, (size_t)n_models, who)) || (rc = sv_alloc(d_bias, (size_t)n_models, who)) ||
-        (rc = sv_alloc(d_out, outs, who))) return rc;
+    if ((rc = dge_alloc_for(d_sup, lists, who)) || (rc = dge_alloc_for(d_supc, lists, who)) || (rc = dge_alloc_for(d_nsup, (size_t)n_models, who)) || (rc = dge_alloc_for(d_bias, (size_t)n_models, who)) ||
+        (rc = dge_alloc_for(d_out, outs, who))) return rc;
     if (!sup.empty()) {
         DGE_HIP(hipMemcpy(d_sup.p, sup.data(), sup.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         DGE_HIP(hipMemcpy(d_supc.p, supc.data(), supc.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -577,9 +491,10 @@ extern "C" int dge_svm_fit_vectors(const dge_vectors* v, const uint8_t* y, int32
     const char* who = "dge_svm_fit_vectors";
     if (!v || !y || !coef || !bias || n_labels < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     dge_svm_cfg c;
-    int rc = svm_labels_check(who, n_labels);
-    if (rc || (rc = svm_cfg_check(who, cfg, v->dim, &c))) return rc;
-    return svm_fit_run(who, v, y, n_labels, select, c, coef, bias, iterations, converged, info);
+    ur_rows u;
+    int rc = dge_range_check(who, "n_labels", n_labels, SV_MAX_LABELS);
+    if (rc || (rc = svm_cfg_check(who, cfg, v->dim, &c)) || (rc = dge_range_check(who, "dim", v->dim, SV_MAX_DIM)) || (rc = svm_vectors_intake(who, v, y, n_labels, select, nullptr, 0, c, &u))) return rc;
+    return svm_fit_run(who, v, u, y, n_labels, c, coef, bias, iterations, converged, info);
 }
 
 extern "C" int dge_svm_fit(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* y, int32_t n_labels, const uint8_t* select, const dge_svm_cfg* cfg,
@@ -587,22 +502,12 @@ extern "C" int dge_svm_fit(int device, const float* features, int64_t n_rows, in
     const char* who = "dge_svm_fit";
     if (!features || !y || !coef || !bias || n_rows < 0 || dim < 0 || n_labels < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     dge_svm_cfg c;
-    int rc = svm_dim_check(who, dim);
-    if (rc || (rc = svm_labels_check(who, n_labels)) || (rc = svm_cfg_check(who, cfg, dim, &c))) return rc;
-    int64_t n = 0;
-    for (int64_t i = 0; i < n_rows; i++) {
-        if (select && !select[i]) continue;
-        for (int l = 0; l < n_labels; l++)
-            if (y[(size_t)l * (size_t)n_rows + (size_t)i] > 1) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has label %d in column %d; labels are 0 or 1", who, (long long)i, (int)y[(size_t)l * (size_t)n_rows + (size_t)i], l);
-        n++;
-    }
-    if ((rc = svm_count_check(who, n))) return rc;
-    if (c.state == 1 && n > SV_LDS_ROWS) DGE_FAIL(DGE_ERR_ARG, "%s: state = 1 holds at most %d used rows in LDS; the call has %lld", who, SV_LDS_ROWS, (long long)n);
-    dge_vectors* v = nullptr;
-    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &v))) return rc;
-    rc = svm_fit_run(who, v, y, n_labels, select, c, coef, bias, iterations, converged, info);
-    dge_vectors_free(v);
-    return rc;
+    ur_rows u;
+    int rc = dge_range_check(who, "dim", dim, SV_MAX_DIM);
+    if (rc || (rc = dge_range_check(who, "n_labels", n_labels, SV_MAX_LABELS)) || (rc = svm_cfg_check(who, cfg, dim, &c)) || (rc = svm_intake(who, n_rows, nullptr, y, n_labels, select, nullptr, 0, c, &u))) return rc;
+    dge_vectors_guard g;
+    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &g.v))) return rc;
+    return svm_fit_run(who, g.v, u, y, n_labels, c, coef, bias, iterations, converged, info);
 }
 
 extern "C" int dge_svm_cv_vectors(const dge_vectors* v, const uint8_t* y, int32_t n_labels, const int32_t* fold, int32_t n_folds, const dge_svm_cfg* cfg, int64_t* correct,
@@ -610,9 +515,13 @@ extern "C" int dge_svm_cv_vectors(const dge_vectors* v, const uint8_t* y, int32_
     const char* who = "dge_svm_cv_vectors";
     if (!v || !y || !fold || !correct || !tested || n_labels < 0 || n_folds < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     dge_svm_cfg c;
-    int rc = svm_labels_check(who, n_labels);
-    if (rc || (rc = svm_folds_check(who, n_folds)) || (rc = svm_cfg_check(who, cfg, v->dim, &c))) return rc;
-    return svm_cv_run(who, v, y, n_labels, fold, n_folds, c, correct, tested, iterations, support, converged, decision, info);
+    ur_rows u;
+    int rc = dge_range_check(who, "n_labels", n_labels, SV_MAX_LABELS);
+    if (rc || (rc = dge_range_check(who, "n_folds", n_folds, SV_MAX_FOLDS)) || (rc = svm_cfg_check(who, cfg, v->dim, &c)) || (rc = dge_range_check(who, "dim", v->dim, SV_MAX_DIM))) return rc;
+    for (int64_t i = 0; i < v->rows; i++)                          // every row's fold before a device is looked for, the labels behind the present bytes
+        if (fold[i] < -1 || fold[i] >= n_folds) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has fold %d, outside -1 .. %d", who, (long long)i, fold[i], n_folds - 1);
+    if ((rc = svm_vectors_intake(who, v, y, n_labels, nullptr, fold, n_folds, c, &u))) return rc;
+    return svm_cv_run(who, v, u, y, n_labels, n_folds, c, correct, tested, iterations, support, converged, decision, info);
 }
 
 extern "C" int dge_svm_cv(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* y, int32_t n_labels, const int32_t* fold, int32_t n_folds,
@@ -621,30 +530,17 @@ extern "C" int dge_svm_cv(int device, const float* features, int64_t n_rows, int
     const char* who = "dge_svm_cv";
     if (!features || !y || !fold || !correct || !tested || n_rows < 0 || dim < 0 || n_labels < 0 || n_folds < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     dge_svm_cfg c;
-    int rc = svm_dim_check(who, dim);
-    if (rc || (rc = svm_labels_check(who, n_labels)) || (rc = svm_folds_check(who, n_folds)) || (rc = svm_cfg_check(who, cfg, dim, &c))) return rc;
-    std::vector<int64_t> in_fold((size_t)n_folds, 0);
-    int64_t n = 0;
-    for (int64_t i = 0; i < n_rows; i++) {
-        if (fold[i] < -1 || fold[i] >= n_folds) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has fold %d, outside -1 .. %d", who, (long long)i, fold[i], n_folds - 1);
-        if (fold[i] < 0) continue;
-        for (int l = 0; l < n_labels; l++)
-            if (y[(size_t)l * (size_t)n_rows + (size_t)i] > 1) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has label %d in column %d; labels are 0 or 1", who, (long long)i, (int)y[(size_t)l * (size_t)n_rows + (size_t)i], l);
-        in_fold[(size_t)fold[i]]++; n++;
-    }
-    if ((rc = svm_count_check(who, n))) return rc;
-    for (int f = 0; f < n_folds; f++)
-        if (n - in_fold[(size_t)f] == 0) DGE_FAIL(DGE_ERR_ARG, "%s: fold %d has no training rows", who, f);
-    if (c.state == 1 && n > SV_LDS_ROWS) DGE_FAIL(DGE_ERR_ARG, "%s: state = 1 holds at most %d used rows in LDS; the call has %lld", who, SV_LDS_ROWS, (long long)n);
-    dge_vectors* v = nullptr;
-    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &v))) return rc;
-    rc = svm_cv_run(who, v, y, n_labels, fold, n_folds, c, correct, tested, iterations, support, converged, decision, info);
-    dge_vectors_free(v);
-    return rc;
+    ur_rows u;
+    int rc = dge_range_check(who, "dim", dim, SV_MAX_DIM);
+    if (rc || (rc = dge_range_check(who, "n_labels", n_labels, SV_MAX_LABELS)) || (rc = dge_range_check(who, "n_folds", n_folds, SV_MAX_FOLDS)) || (rc = svm_cfg_check(who, cfg, dim, &c)) ||
+        (rc = svm_intake(who, n_rows, nullptr, y, n_labels, nullptr, fold, n_folds, c, &u))) return rc;
+    dge_vectors_guard g;
+    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &g.v))) return rc;
+    return svm_cv_run(who, g.v, u, y, n_labels, n_folds, c, correct, tested, iterations, support, converged, decision, info);
 }
 
 static int svm_decision_args(const char* who, int32_t n_models, double gamma) {
-    if (n_models < 1 || n_models > SV_MAX_LABELS * SV_MAX_FOLDS) DGE_FAIL(DGE_ERR_ARG, "%s: n_models = %d is outside 1 .. %d", who, n_models, SV_MAX_LABELS * SV_MAX_FOLDS);
+    if (int rc = dge_range_check(who, "n_models", n_models, SV_MAX_LABELS * SV_MAX_FOLDS)) return rc;
     if (!(gamma > 0.0) || !(gamma < INFINITY)) DGE_FAIL(DGE_ERR_ARG, "%s: gamma = %g is not a finite number > 0", who, gamma);
     return DGE_OK;
 }
@@ -660,13 +556,10 @@ extern "C" int dge_svm_decision(int device, const float* sv_features, int64_t n_
                                 const float* x_features, int64_t n_x, double* out) {
     const char* who = "dge_svm_decision";
     if (!sv_features || !coef || !bias || !out || n_sv < 0 || dim < 0 || n_models < 0 || n_x < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
-    int rc = svm_dim_check(who, dim);
+    int rc = dge_range_check(who, "dim", dim, SV_MAX_DIM);
     if (rc || (rc = svm_decision_args(who, n_models, gamma))) return rc;
-    dge_vectors *sv = nullptr, *x = nullptr;
-    if ((rc = dge_vectors_from_host(device, sv_features, n_sv, dim, nullptr, &sv))) return rc;
-    if (x_features && (rc = dge_vectors_from_host(device, x_features, n_x, dim, nullptr, &x))) { dge_vectors_free(sv); return rc; }
-    rc = svm_decision_run(who, sv, coef, bias, n_models, gamma, x ? x : sv, out);
-    if (x) dge_vectors_free(x);
-    dge_vectors_free(sv);
-    return rc;
+    dge_vectors_guard sv, x;
+    if ((rc = dge_vectors_from_host(device, sv_features, n_sv, dim, nullptr, &sv.v))) return rc;
+    if (x_features && (rc = dge_vectors_from_host(device, x_features, n_x, dim, nullptr, &x.v))) return rc;
+    return svm_decision_run(who, sv.v, coef, bias, n_models, gamma, x.v ? x.v : sv.v, out);
 }

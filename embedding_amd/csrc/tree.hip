@@ -315,22 +315,13 @@ __global__ void k_tr_predict(const float* __restrict__ x, const int64_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------ host
-template <typename T>
-static int tr_alloc(dge_tmp<T>& t, size_t n, const char* who) {
-    if (t.p) { (void)hipFree(t.p); t.p = nullptr; }
-    if (n == 0) n = 1;
-    const hipError_t e = hipMalloc((void**)&t.p, n * sizeof(T));
-    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); t.p = nullptr; DGE_FAIL(DGE_ERR_CAP, "%s: %zu bytes of device memory do not fit", who, n * sizeof(T)); }
-    DGE_HIP(e);
-    return DGE_OK;
-}
 // the scratch of the library's scans: one buffer that only grows, so that a level allocates nothing
 struct tr_scratch {
     dge_tmp<uint8_t> t;
     size_t cap = 0;
     const char* who = "";
     int operator()(size_t bytes, void** p) {
-        if (bytes > cap) { if (int rc = tr_alloc(t, bytes, who)) return rc; cap = bytes; }
+        if (bytes > cap) { if (int rc = dge_alloc_for(t, bytes, who)) return rc; cap = bytes; }
         *p = t.p;
         return DGE_OK;
     }
@@ -345,14 +336,6 @@ static int tree_cfg_check(const char* who, const dge_tree_cfg* cfg, tr_limits* l
     *lim = tr_limits{cfg->max_depth, cfg->min_samples_split, cfg->min_samples_leaf};
     return DGE_OK;
 }
-static int tree_dim_check(const char* who, int32_t dim) {
-    if (dim < 1 || dim > TR_MAX_DIM) DGE_FAIL(DGE_ERR_ARG, "%s: dim = %d is outside 1 .. %d", who, dim, TR_MAX_DIM);
-    return DGE_OK;
-}
-static int tree_folds_check(const char* who, int32_t n_folds) {
-    if (n_folds < 1 || n_folds > TR_MAX_FOLDS) DGE_FAIL(DGE_ERR_ARG, "%s: n_folds = %d is outside 1 .. %d", who, n_folds, TR_MAX_FOLDS);
-    return DGE_OK;
-}
 
 struct tree_out {         // what a run gives: per tree
     std::vector<int32_t> n_nodes, depth;
@@ -365,20 +348,27 @@ struct tree_out {         // what a run gives: per tree
     float ms = 0.f;
 };
 
-// The used rows (numbers among all rows, ascending; empty with all = true: every row), their labels and folds (fold[i] outside 0 .. trees-1: the row trains every
-// tree and tests none), grow `trees` trees: tree t trains on the used rows with fold != t.  predict: count the test rows every tree votes right.
-static int tree_run(const char* who, const dge_vectors* v, bool all, const std::vector<int64_t>& used, const std::vector<uint8_t>& y, const std::vector<int32_t>& fold,
-                    int trees, const tr_limits& lim, bool predict, bool keep_arrays, tree_out* out) {
+// every tree of the call has rows to train on, and no more than the lists hold: tree t trains on the used rows with fold != t
+static int tree_counts(const char* who, const ur_rows& u, int trees) {
+    for (int t = 0; t < trees; t++) {
+        const int64_t nt = u.n - ((size_t)t < u.tested.size() ? u.tested[(size_t)t] : 0);
+        if (nt == 0) DGE_FAIL(DGE_ERR_ARG, "%s: fold %d has no training rows", who, t);
+        if (nt > TR_MAX_ROWS) DGE_FAIL(DGE_ERR_RANGE, "%s: %lld rows would train tree %d; at most 2^20 may", who, (long long)nt, t);
+    }
+    return DGE_OK;
+}
+
+// The used rows u (tree_counts has passed them), their labels y and folds (u.fold[i] outside 0 .. trees-1: the row trains every tree and tests none), grow `trees`
+// trees: tree t trains on the used rows with fold != t.  predict: count the test rows every tree votes right.
+static int tree_run(const char* who, const dge_vectors* v, const ur_rows& u, const std::vector<uint8_t>& y, int trees, const tr_limits& lim, bool predict, bool keep_arrays,
+                    tree_out* out) {
+    const std::vector<int32_t>& fold = u.fold;
     const int dim = v->dim;
-    const int64_t n = (int64_t)y.size();
+    const int64_t n = u.n;
     int rc;
     std::vector<int64_t> n_t((size_t)trees, 0), p_t((size_t)trees, 0);
     for (int t = 0; t < trees; t++)
         for (int64_t i = 0; i < n; i++) if (fold[(size_t)i] != t) { n_t[(size_t)t]++; p_t[(size_t)t] += y[(size_t)i]; }
-    for (int t = 0; t < trees; t++) {
-        if (n_t[(size_t)t] == 0) DGE_FAIL(DGE_ERR_ARG, "%s: fold %d has no training rows", who, t);
-        if (n_t[(size_t)t] > TR_MAX_ROWS) DGE_FAIL(DGE_ERR_RANGE, "%s: %lld rows would train tree %d; at most 2^20 may", who, (long long)n_t[(size_t)t], t);
-    }
     const size_t dn = (size_t)dim * (size_t)n;
 
     // how many trees grow together: what fits half the free memory (about 23 bytes an entry of a list: two lists with keys, the prefix counts, the runs), at most
@@ -394,7 +384,7 @@ static int tree_run(const char* who, const dge_vectors* v, bool all, const std::
     batch = std::max<int64_t>(1, std::min<int64_t>(batch, trees));
     if ((int64_t)batch * n > 0x7fffffffLL) DGE_FAIL(DGE_ERR_RANGE, "%s: %lld rows x %d columns are too many for one tree's lists", who, (long long)n, dim);
 
-    dge_tmp<int64_t> d_used;
+    dge_used_rows d_used;
     dge_tmp<uint8_t> d_y, d_mark;
     dge_tmp<int32_t> d_fold, d_seg, d_partial, d_dest, d_splits, d_next, d_depth, d_totals;
     dge_tmp<uint64_t> d_keys, d_keys_in;
@@ -410,13 +400,10 @@ static int tree_run(const char* who, const dge_vectors* v, bool all, const std::
     tr_scratch scratch;
     scratch.who = who;
 
-    if (!all) {
-        if ((rc = tr_alloc(d_used, (size_t)n, who))) return rc;
-        DGE_HIP(hipMemcpy(d_used.p, used.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice));
-    }
-    const int64_t* dused = all ? nullptr : d_used.p;
-    if ((rc = tr_alloc(d_y, (size_t)n, who)) || (rc = tr_alloc(d_fold, (size_t)n, who)) || (rc = tr_alloc(d_bad, 1, who)) || (rc = tr_alloc(d_correct, (size_t)trees, who)) ||
-        (rc = tr_alloc(d_keys, dn, who)) || (rc = tr_alloc(d_rows, dn, who)) || (rc = tr_alloc(d_keys_in, dn, who)) || (rc = tr_alloc(d_rows_in, dn, who))) return rc;
+    if ((rc = d_used.upload(u, who))) return rc;
+    const int64_t* dused = d_used.p;
+    if ((rc = dge_alloc_for(d_y, (size_t)n, who)) || (rc = dge_alloc_for(d_fold, (size_t)n, who)) || (rc = dge_alloc_for(d_bad, 1, who)) || (rc = dge_alloc_for(d_correct, (size_t)trees, who)) ||
+        (rc = dge_alloc_for(d_keys, dn, who)) || (rc = dge_alloc_for(d_rows, dn, who)) || (rc = dge_alloc_for(d_keys_in, dn, who)) || (rc = dge_alloc_for(d_rows_in, dn, who))) return rc;
     DGE_HIP(hipMemcpy(d_y.p, y.data(), (size_t)n, hipMemcpyHostToDevice));
     DGE_HIP(hipMemcpy(d_fold.p, fold.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
 
@@ -431,22 +418,20 @@ static int tree_run(const char* who, const dge_vectors* v, bool all, const std::
     }
     unsigned long long bad = TR_NONE;
     DGE_HIP(hipMemcpy(&bad, d_bad.p, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad != TR_NONE) {
-        const int64_t i = (int64_t)(bad / (unsigned long long)dim);
-        DGE_FAIL(DGE_ERR_ARG, "%s: row %lld, column %lld holds a value that is not finite", who, (long long)(all ? i : used[(size_t)i]), (long long)(bad % (unsigned long long)dim));
-    }
+    if (bad != TR_NONE)
+        DGE_FAIL(DGE_ERR_ARG, "%s: row %lld, column %lld holds a value that is not finite", who, (long long)u.at((int64_t)(bad / (unsigned long long)dim)), (long long)(bad % (unsigned long long)dim));
     if ((rc = dge_sort_pairs(scratch, d_keys_in.p, d_keys.p, d_rows_in.p, d_rows.p, (int64_t)dn, 32 + dge_bits((uint64_t)dim), 0, true))) return rc;
     (void)hipFree(d_keys_in.release());
     (void)hipFree(d_rows_in.release());
 
     out->n_nodes.assign((size_t)trees, 0); out->depth.assign((size_t)trees, 0); out->correct.assign((size_t)trees, 0);
     const size_t Mcap = (size_t)batch * (size_t)n, Kcap = Mcap / 2 + (size_t)batch + 1;
-    if ((rc = tr_alloc(d_ent[0], Mcap * dim, who)) || (rc = tr_alloc(d_ent[1], Mcap * dim, who)) || (rc = tr_alloc(d_key[0], Mcap * dim, who)) ||
-        (rc = tr_alloc(d_key[1], Mcap * dim, who)) || (rc = tr_alloc(d_G, Mcap * dim, who)) || (rc = tr_alloc(d_seg, Mcap, who)) || (rc = tr_alloc(d_mark, Mcap, who)) ||
-        (rc = tr_alloc(d_partial, ((Mcap + 63) / 64 + Kcap) * (size_t)dim, who)) || (rc = tr_alloc(d_node[0], Kcap, who)) || (rc = tr_alloc(d_node[1], Kcap, who)) ||
-        (rc = tr_alloc(d_best, Kcap, who)) || (rc = tr_alloc(d_tri, Kcap, who)) || (rc = tr_alloc(d_ex, Kcap, who)) || (rc = tr_alloc(d_dest, 2 * Kcap, who)) ||
-        (rc = tr_alloc(d_splits, (size_t)batch, who)) || (rc = tr_alloc(d_next, (size_t)batch, who)) || (rc = tr_alloc(d_depth, (size_t)batch, who)) ||
-        (rc = tr_alloc(d_totals, 2, who)) || (rc = tr_alloc(d_off, (size_t)batch + 1, who)) || (rc = tr_alloc(d_nt, (size_t)batch, who)) || (rc = tr_alloc(d_pt, (size_t)batch, who))) return rc;
+    if ((rc = dge_alloc_for(d_ent[0], Mcap * dim, who)) || (rc = dge_alloc_for(d_ent[1], Mcap * dim, who)) || (rc = dge_alloc_for(d_key[0], Mcap * dim, who)) ||
+        (rc = dge_alloc_for(d_key[1], Mcap * dim, who)) || (rc = dge_alloc_for(d_G, Mcap * dim, who)) || (rc = dge_alloc_for(d_seg, Mcap, who)) || (rc = dge_alloc_for(d_mark, Mcap, who)) ||
+        (rc = dge_alloc_for(d_partial, ((Mcap + 63) / 64 + Kcap) * (size_t)dim, who)) || (rc = dge_alloc_for(d_node[0], Kcap, who)) || (rc = dge_alloc_for(d_node[1], Kcap, who)) ||
+        (rc = dge_alloc_for(d_best, Kcap, who)) || (rc = dge_alloc_for(d_tri, Kcap, who)) || (rc = dge_alloc_for(d_ex, Kcap, who)) || (rc = dge_alloc_for(d_dest, 2 * Kcap, who)) ||
+        (rc = dge_alloc_for(d_splits, (size_t)batch, who)) || (rc = dge_alloc_for(d_next, (size_t)batch, who)) || (rc = dge_alloc_for(d_depth, (size_t)batch, who)) ||
+        (rc = dge_alloc_for(d_totals, 2, who)) || (rc = dge_alloc_for(d_off, (size_t)batch + 1, who)) || (rc = dge_alloc_for(d_nt, (size_t)batch, who)) || (rc = dge_alloc_for(d_pt, (size_t)batch, who))) return rc;
 
     std::vector<tr_node> nodes;
     std::vector<int32_t> dest, ones;
@@ -458,8 +443,8 @@ static int tree_run(const char* who, const dge_vectors* v, bool all, const std::
         off.assign((size_t)tb + 1, 0);
         for (int t = 0; t < tb; t++) off[(size_t)t + 1] = off[(size_t)t] + 2 * n_t[(size_t)(t0 + t)] - 1;
         const size_t cap_nodes = (size_t)off[(size_t)tb];
-        if ((rc = tr_alloc(d_feature, cap_nodes, who)) || (rc = tr_alloc(d_left, cap_nodes, who)) || (rc = tr_alloc(d_threshold, cap_nodes, who)) ||
-            (rc = tr_alloc(d_count, cap_nodes, who)) || (rc = tr_alloc(d_pos, cap_nodes, who))) return rc;
+        if ((rc = dge_alloc_for(d_feature, cap_nodes, who)) || (rc = dge_alloc_for(d_left, cap_nodes, who)) || (rc = dge_alloc_for(d_threshold, cap_nodes, who)) ||
+            (rc = dge_alloc_for(d_count, cap_nodes, who)) || (rc = dge_alloc_for(d_pos, cap_nodes, who))) return rc;
         const tr_arrays T{d_feature.p, d_threshold.p, d_left.p, d_count.p, d_pos.p};
         DGE_HIP(hipMemsetAsync(d_feature.p, 0xff, cap_nodes * sizeof(int32_t), 0));
         DGE_HIP(hipMemsetAsync(d_left.p, 0xff, cap_nodes * sizeof(int32_t), 0));
@@ -571,15 +556,6 @@ static int tree_run(const char* who, const dge_vectors* v, bool all, const std::
     return DGE_OK;
 }
 
-// the present bytes of v on the host (empty when every row is present)
-static int tree_present(const dge_vectors* v, std::vector<uint8_t>& pres) {
-    pres.clear();
-    if (v->n_present == v->rows) return DGE_OK;
-    pres.resize((size_t)v->rows);
-    if (v->rows) DGE_HIP(hipMemcpy(pres.data(), v->d_present, (size_t)v->rows, hipMemcpyDeviceToHost));
-    return DGE_OK;
-}
-
 static void tree_fill_info(dge_tree_info* info, int64_t rows, const tree_out& o) {
     if (!info) return;
     info->rows = rows; info->n_nodes = 0; info->depth = 0;
@@ -587,25 +563,22 @@ static void tree_fill_info(dge_tree_info* info, int64_t rows, const tree_out& o)
     info->levels = (int32_t)o.levels; info->trees = (int32_t)o.n_nodes.size(); info->batches = o.batches; info->kernel_ms = o.ms;
 }
 
-static int tree_fit_run(const char* who, const dge_vectors* v, const uint8_t* y, const uint8_t* select, const tr_limits& lim, int64_t cap, int32_t* feature, double* threshold,
+// the walk of both fits and both cross-validations: pres the present bytes (nullptr: every row); the first offence in the entry's words
+static int tree_intake(const char* who, int64_t rows, const uint8_t* pres, const uint8_t* y, const uint8_t* select, const int32_t* fold, int32_t n_folds, ur_rows* u) {
+    ur_intake(ur_in{rows, pres, select, fold, n_folds, y, 1}, u);
+    if (!fold) ur_no_folds(u);
+    if (u->kind == UR_FOLD) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has fold %d, outside -1 .. %d", who, (long long)u->bad_row, u->bad_value, n_folds - 1);
+    if (u->kind == UR_LABEL) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has label %d; labels are 0 or 1", who, (long long)u->bad_row, u->bad_value);
+    if (!fold && u->n == 0) DGE_FAIL(DGE_ERR_ARG, "%s: no row to train on", who);
+    return fold ? tree_counts(who, *u, n_folds) : DGE_OK;
+}
+
+static int tree_fit_run(const char* who, const dge_vectors* v, const ur_rows& u, const uint8_t* y, const tr_limits& lim, int64_t cap, int32_t* feature, double* threshold,
                         int32_t* left, int64_t* count, int64_t* pos, dge_tree_info* info) {
-    int rc;
-    if ((rc = tree_dim_check(who, v->dim))) return rc;
-    if ((rc = dge_require_device(v->device))) return rc;
-    std::vector<uint8_t> pres;
-    if ((rc = tree_present(v, pres))) return rc;
-    std::vector<int64_t> used;
-    std::vector<uint8_t> yu;
-    for (int64_t i = 0; i < v->rows; i++) {
-        if ((!pres.empty() && !pres[(size_t)i]) || (select && !select[i])) continue;
-        if (y[i] > 1) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has label %d; labels are 0 or 1", who, (long long)i, (int)y[i]);
-        used.push_back(i); yu.push_back(y[i]);
-    }
-    if (used.empty()) DGE_FAIL(DGE_ERR_ARG, "%s: no row to train on", who);
-    const bool all = (int64_t)used.size() == v->rows;
-    std::vector<int32_t> fold(used.size(), -1);
+    int rc = tree_counts(who, u, 1);
+    if (rc) return rc;
     tree_out o;
-    if ((rc = tree_run(who, v, all, used, yu, fold, 1, lim, false, true, &o))) return rc;
+    if ((rc = tree_run(who, v, u, ur_gather_labels(u, y, 1), 1, lim, false, true, &o))) return rc;
     const int64_t m = o.n_nodes[0];
     if (m > cap) {
         if (info) info->n_nodes = m;
@@ -616,97 +589,78 @@ static int tree_fit_run(const char* who, const dge_vectors* v, const uint8_t* y,
     memcpy(left, o.left.data(), (size_t)m * sizeof(int32_t));
     memcpy(count, o.count.data(), (size_t)m * sizeof(int64_t));
     memcpy(pos, o.pos.data(), (size_t)m * sizeof(int64_t));
-    tree_fill_info(info, (int64_t)used.size(), o);
+    tree_fill_info(info, u.n, o);
     return DGE_OK;
 }
 
-static int tree_cv_run(const char* who, const dge_vectors* v, const uint8_t* y, const int32_t* fold, int32_t n_folds, const tr_limits& lim, int64_t* correct, int64_t* tested,
+static int tree_cv_run(const char* who, const dge_vectors* v, const ur_rows& u, const uint8_t* y, int32_t n_folds, const tr_limits& lim, int64_t* correct, int64_t* tested,
                        int32_t* n_nodes, int32_t* depth, dge_tree_info* info) {
-    int rc;
-    if ((rc = tree_dim_check(who, v->dim))) return rc;
-    for (int64_t i = 0; i < v->rows; i++)
-        if (fold[i] < -1 || fold[i] >= n_folds) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has fold %d, outside -1 .. %d", who, (long long)i, fold[i], n_folds - 1);
-    if ((rc = dge_require_device(v->device))) return rc;
-    std::vector<uint8_t> pres;
-    if ((rc = tree_present(v, pres))) return rc;
-    std::vector<int64_t> used, tst((size_t)n_folds, 0);
-    std::vector<uint8_t> yu;
-    std::vector<int32_t> fu;
-    for (int64_t i = 0; i < v->rows; i++) {
-        if ((!pres.empty() && !pres[(size_t)i]) || fold[i] < 0) continue;
-        if (y[i] > 1) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has label %d; labels are 0 or 1", who, (long long)i, (int)y[i]);
-        used.push_back(i); yu.push_back(y[i]); fu.push_back(fold[i]); tst[(size_t)fold[i]]++;
-    }
-    if (used.empty()) DGE_FAIL(DGE_ERR_ARG, "%s: fold 0 has no training rows", who);
-    const bool all = (int64_t)used.size() == v->rows;
     tree_out o;
-    if ((rc = tree_run(who, v, all, used, yu, fu, n_folds, lim, true, false, &o))) return rc;
-    for (int t = 0; t < n_folds; t++) { correct[t] = o.correct[(size_t)t]; tested[t] = tst[(size_t)t]; if (n_nodes) n_nodes[t] = o.n_nodes[(size_t)t]; if (depth) depth[t] = o.depth[(size_t)t]; }
-    tree_fill_info(info, (int64_t)used.size(), o);
+    if (int rc = tree_run(who, v, u, ur_gather_labels(u, y, 1), n_folds, lim, true, false, &o)) return rc;
+    for (int t = 0; t < n_folds; t++) { correct[t] = o.correct[(size_t)t]; tested[t] = u.tested[(size_t)t]; if (n_nodes) n_nodes[t] = o.n_nodes[(size_t)t]; if (depth) depth[t] = o.depth[(size_t)t]; }
+    tree_fill_info(info, u.n, o);
     return DGE_OK;
+}
+
+// a *_vectors entry behind its limit checks: the device, the present bytes, the walk
+static int tree_vectors_intake(const char* who, const dge_vectors* v, const uint8_t* y, const uint8_t* select, const int32_t* fold, int32_t n_folds, ur_rows* u) {
+    int rc = dge_require_device(v->device);
+    dge_present pres;
+    if (rc || (rc = pres.load(v))) return rc;
+    return tree_intake(who, v->rows, pres.p, y, select, fold, n_folds, u);
 }
 
 extern "C" int dge_tree_fit_vectors(const dge_vectors* v, const uint8_t* y, const uint8_t* select, const dge_tree_cfg* cfg, int64_t cap, int32_t* feature, double* threshold,
                                     int32_t* left, int64_t* count, int64_t* pos, dge_tree_info* info) {
-    if (!v || !y || !feature || !threshold || !left || !count || !pos || cap < 0) DGE_FAIL(DGE_ERR_ARG, "dge_tree_fit_vectors: null or negative argument");
+    const char* who = "dge_tree_fit_vectors";
+    if (!v || !y || !feature || !threshold || !left || !count || !pos || cap < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     tr_limits lim;
-    if (int rc = tree_cfg_check("dge_tree_fit_vectors", cfg, &lim)) return rc;
-    return tree_fit_run("dge_tree_fit_vectors", v, y, select, lim, cap, feature, threshold, left, count, pos, info);
+    ur_rows u;
+    int rc = tree_cfg_check(who, cfg, &lim);
+    if (rc || (rc = dge_range_check(who, "dim", v->dim, TR_MAX_DIM)) || (rc = tree_vectors_intake(who, v, y, select, nullptr, 0, &u))) return rc;
+    return tree_fit_run(who, v, u, y, lim, cap, feature, threshold, left, count, pos, info);
 }
 
 extern "C" int dge_tree_fit(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* y, const uint8_t* select, const dge_tree_cfg* cfg, int64_t cap,
                             int32_t* feature, double* threshold, int32_t* left, int64_t* count, int64_t* pos, dge_tree_info* info) {
-    if (!features || !y || !feature || !threshold || !left || !count || !pos || n_rows < 0 || dim < 0 || cap < 0) DGE_FAIL(DGE_ERR_ARG, "dge_tree_fit: null or negative argument");
+    const char* who = "dge_tree_fit";
+    if (!features || !y || !feature || !threshold || !left || !count || !pos || n_rows < 0 || dim < 0 || cap < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     tr_limits lim;
-    int rc = tree_cfg_check("dge_tree_fit", cfg, &lim);
-    if (rc || (rc = tree_dim_check("dge_tree_fit", dim))) return rc;
-    int64_t n = 0;
-    for (int64_t i = 0; i < n_rows; i++) {
-        if (select && !select[i]) continue;
-        if (y[i] > 1) DGE_FAIL(DGE_ERR_ARG, "dge_tree_fit: row %lld has label %d; labels are 0 or 1", (long long)i, (int)y[i]);
-        n++;
-    }
-    if (n == 0) DGE_FAIL(DGE_ERR_ARG, "dge_tree_fit: no row to train on");
-    if (n > TR_MAX_ROWS) DGE_FAIL(DGE_ERR_RANGE, "dge_tree_fit: %lld rows would train the tree; at most 2^20 may", (long long)n);
-    dge_vectors* v = nullptr;
-    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &v))) return rc;
-    rc = tree_fit_run("dge_tree_fit", v, y, select, lim, cap, feature, threshold, left, count, pos, info);
-    dge_vectors_free(v);
-    return rc;
+    ur_rows u;
+    int rc = tree_cfg_check(who, cfg, &lim);
+    if (rc || (rc = dge_range_check(who, "dim", dim, TR_MAX_DIM)) || (rc = tree_intake(who, n_rows, nullptr, y, select, nullptr, 0, &u))) return rc;
+    if (u.n > TR_MAX_ROWS) DGE_FAIL(DGE_ERR_RANGE, "%s: %lld rows would train the tree; at most 2^20 may", who, (long long)u.n);
+    dge_vectors_guard g;
+    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &g.v))) return rc;
+    return tree_fit_run(who, g.v, u, y, lim, cap, feature, threshold, left, count, pos, info);
 }
 
 extern "C" int dge_tree_cv_vectors(const dge_vectors* v, const uint8_t* y, const int32_t* fold, int32_t n_folds, const dge_tree_cfg* cfg, int64_t* correct, int64_t* tested,
                                    int32_t* n_nodes, int32_t* depth, dge_tree_info* info) {
-    if (!v || !y || !fold || !correct || !tested) DGE_FAIL(DGE_ERR_ARG, "dge_tree_cv_vectors: null argument");
+    const char* who = "dge_tree_cv_vectors";
+    if (!v || !y || !fold || !correct || !tested) DGE_FAIL(DGE_ERR_ARG, "%s: null argument", who);
     tr_limits lim;
-    int rc = tree_cfg_check("dge_tree_cv_vectors", cfg, &lim);
-    if (rc || (rc = tree_folds_check("dge_tree_cv_vectors", n_folds))) return rc;
-    return tree_cv_run("dge_tree_cv_vectors", v, y, fold, n_folds, lim, correct, tested, n_nodes, depth, info);
+    ur_rows u;
+    int rc = tree_cfg_check(who, cfg, &lim);
+    if (rc || (rc = dge_range_check(who, "n_folds", n_folds, TR_MAX_FOLDS)) || (rc = dge_range_check(who, "dim", v->dim, TR_MAX_DIM))) return rc;
+    for (int64_t i = 0; i < v->rows; i++)                          // every row's fold before a device is looked for, the labels behind the present bytes
+        if (fold[i] < -1 || fold[i] >= n_folds) DGE_FAIL(DGE_ERR_ARG, "%s: row %lld has fold %d, outside -1 .. %d", who, (long long)i, fold[i], n_folds - 1);
+    if ((rc = tree_vectors_intake(who, v, y, nullptr, fold, n_folds, &u))) return rc;
+    return tree_cv_run(who, v, u, y, n_folds, lim, correct, tested, n_nodes, depth, info);
 }
 
 extern "C" int dge_tree_cv(int device, const float* features, int64_t n_rows, int32_t dim, const uint8_t* y, const int32_t* fold, int32_t n_folds, const dge_tree_cfg* cfg,
                            int64_t* correct, int64_t* tested, int32_t* n_nodes, int32_t* depth, dge_tree_info* info) {
-    if (!features || !y || !fold || !correct || !tested || n_rows < 0 || dim < 0) DGE_FAIL(DGE_ERR_ARG, "dge_tree_cv: null or negative argument");
+    const char* who = "dge_tree_cv";
+    if (!features || !y || !fold || !correct || !tested || n_rows < 0 || dim < 0) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     tr_limits lim;
-    int rc = tree_cfg_check("dge_tree_cv", cfg, &lim);
-    if (rc || (rc = tree_folds_check("dge_tree_cv", n_folds)) || (rc = tree_dim_check("dge_tree_cv", dim))) return rc;
-    std::vector<int64_t> in_fold((size_t)n_folds, 0);
-    int64_t n = 0;
-    for (int64_t i = 0; i < n_rows; i++) {
-        if (fold[i] < -1 || fold[i] >= n_folds) DGE_FAIL(DGE_ERR_ARG, "dge_tree_cv: row %lld has fold %d, outside -1 .. %d", (long long)i, fold[i], n_folds - 1);
-        if (fold[i] < 0) continue;
-        if (y[i] > 1) DGE_FAIL(DGE_ERR_ARG, "dge_tree_cv: row %lld has label %d; labels are 0 or 1", (long long)i, (int)y[i]);
-        in_fold[(size_t)fold[i]]++; n++;
-    }
-    for (int t = 0; t < n_folds; t++) {
-        if (n - in_fold[(size_t)t] == 0) DGE_FAIL(DGE_ERR_ARG, "dge_tree_cv: fold %d has no training rows", t);
-        if (n - in_fold[(size_t)t] > TR_MAX_ROWS) DGE_FAIL(DGE_ERR_RANGE, "dge_tree_cv: %lld rows would train tree %d; at most 2^20 may", (long long)(n - in_fold[(size_t)t]), t);
-    }
-    dge_vectors* v = nullptr;
-    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &v))) return rc;
-    rc = tree_cv_run("dge_tree_cv", v, y, fold, n_folds, lim, correct, tested, n_nodes, depth, info);
-    dge_vectors_free(v);
-    return rc;
+    ur_rows u;
+    int rc = tree_cfg_check(who, cfg, &lim);
+    if (rc || (rc = dge_range_check(who, "n_folds", n_folds, TR_MAX_FOLDS)) || (rc = dge_range_check(who, "dim", dim, TR_MAX_DIM)) ||
+        (rc = tree_intake(who, n_rows, nullptr, y, nullptr, fold, n_folds, &u))) return rc;
+    dge_vectors_guard g;
+    if ((rc = dge_vectors_from_host(device, features, n_rows, dim, nullptr, &g.v))) return rc;
+    return tree_cv_run(who, g.v, u, y, n_folds, lim, correct, tested, n_nodes, depth, info);
 }
 
 extern "C" int dge_tree_predict_vectors(const dge_vectors* v, int64_t n_nodes, const int32_t* feature, const double* threshold, const int32_t* left, const int64_t* count,
@@ -727,8 +681,8 @@ extern "C" int dge_tree_predict_vectors(const dge_vectors* v, int64_t n_nodes, c
     dge_tmp<double> d_threshold;
     dge_tmp<int64_t> d_count, d_pos;
     dge_tmp<uint8_t> d_out;
-    if ((rc = tr_alloc(d_feature, m, who)) || (rc = tr_alloc(d_left, m, who)) || (rc = tr_alloc(d_threshold, m, who)) || (rc = tr_alloc(d_count, m, who)) ||
-        (rc = tr_alloc(d_pos, m, who)) || (rc = tr_alloc(d_out, (size_t)v->rows, who))) return rc;
+    if ((rc = dge_alloc_for(d_feature, m, who)) || (rc = dge_alloc_for(d_left, m, who)) || (rc = dge_alloc_for(d_threshold, m, who)) || (rc = dge_alloc_for(d_count, m, who)) ||
+        (rc = dge_alloc_for(d_pos, m, who)) || (rc = dge_alloc_for(d_out, (size_t)v->rows, who))) return rc;
     DGE_HIP(hipMemcpy(d_feature.p, feature, m * sizeof(int32_t), hipMemcpyHostToDevice));
     DGE_HIP(hipMemcpy(d_left.p, left, m * sizeof(int32_t), hipMemcpyHostToDevice));
     DGE_HIP(hipMemcpy(d_threshold.p, threshold, m * sizeof(double), hipMemcpyHostToDevice));

@@ -5,6 +5,7 @@ import os
 import numpy as np
 
 from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, SvmCfg, SvmInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
+from .evaluate import _info_dict, _select_mask
 
 
 def _ptr(a):
@@ -229,10 +230,6 @@ class DeviceGraph:
 
     def sample_walks_into(self, corpus, row0, n_walks, seed, first_index):
         check(lib.dge_sample_walks_into(self._h, corpus._h, int(row0), int(n_walks), int(seed), int(first_index)))
-
-
-def _info_dict(inf):
-    return {f[0]: getattr(inf, f[0]) for f in inf._fields_}
 
 
 def _windows(windows):
@@ -679,7 +676,7 @@ class WalkCorpus:
         inf = SeqOutInfo()
         check(lib.dge_walks_write_seq(self._h, row0, n_rows, names._h if names is not None else None, int(bool(position_prefix)), os.fsencode(path),
                                       int(bool(append)), C.byref(inf)))
-        return {f[0]: getattr(inf, f[0]) for f in SeqOutInfo._fields_}
+        return _info_dict(inf)
 
     def to_seq_bytes(self, names=None, position_prefix=False, row0=0, n_rows=None):
         """The same text as write_seq's, into host memory (dge_walks_to_seq_text: a size query, then the text) -> (bytes, info)."""
@@ -689,7 +686,7 @@ class WalkCorpus:
         check(lib.dge_walks_to_seq_text(self._h, row0, n_rows, nh, int(bool(position_prefix)), None, 0, C.byref(need), None))
         buf = np.empty(max(need.value, 1), np.uint8)
         check(lib.dge_walks_to_seq_text(self._h, row0, n_rows, nh, int(bool(position_prefix)), _ptr(buf), need.value, C.byref(need), C.byref(inf)))
-        return buf[:need.value].tobytes(), {f[0]: getattr(inf, f[0]) for f in SeqOutInfo._fields_}
+        return buf[:need.value].tobytes(), _info_dict(inf)
 
     def add_position_prefix(self, region_count):
         check(lib.dge_walks_add_position_prefix(self._h, int(region_count)))
@@ -795,10 +792,7 @@ class Vectors:
         (n_init is then 1).  -> (labels int32 [rows], -1 on rows not selected; centres float32 [k x dim]; info: the fields of struct dge_kmeans_info)."""
         n, dim = self.shape
         k = int(k)
-        if select is not None:
-            select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
-            if select.shape != (n,):
-                raise ValueError("select must hold one entry per row")
+        select = _select_mask(select, n)
         if init is not None:
             init = np.ascontiguousarray(init, np.float32)
             if init.shape != (k, dim):
@@ -806,7 +800,7 @@ class Vectors:
         cfg = KmeansCfg(k, int(n_init), int(max_iter), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
         labels = np.empty(n, np.int32); centres = np.empty((max(k, 0), dim), np.float32); inf = KmeansInfo()
         check(lib.dge_kmeans_vectors(self._h, _ptr(select), C.byref(cfg), _ptr(init), _ptr(labels), _ptr(centres), C.byref(inf)))
-        return labels, centres, {f[0]: getattr(inf, f[0]) for f in KmeansInfo._fields_}
+        return labels, centres, _info_dict(inf)
 
 
     def _labels(self, y):
@@ -823,10 +817,7 @@ class Vectors:
         -> (tree: dict of feature int32, threshold float64, left int32, count int64, pos int64, one entry per node; info: the fields of struct dge_tree_info)."""
         n = self.shape[0]
         y = self._labels(y)
-        if select is not None:
-            select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
-            if select.shape != (n,):
-                raise ValueError("select must hold one entry per row")
+        select = _select_mask(select, n)
         cfg = TreeCfg(int(max_depth), int(min_samples_split), int(min_samples_leaf), 0)
         cap = max(2 * n - 1, 1)
         feature = np.empty(cap, np.int32); threshold = np.empty(cap, np.float64); left = np.empty(cap, np.int32)
@@ -834,7 +825,7 @@ class Vectors:
         check(lib.dge_tree_fit_vectors(self._h, _ptr(y), _ptr(select), C.byref(cfg), cap, _ptr(feature), _ptr(threshold), _ptr(left), _ptr(count), _ptr(pos), C.byref(inf)))
         m = inf.n_nodes
         tree = dict(feature=feature[:m].copy(), threshold=threshold[:m].copy(), left=left[:m].copy(), count=count[:m].copy(), pos=pos[:m].copy())
-        return tree, {f[0]: getattr(inf, f[0]) for f in TreeInfo._fields_}
+        return tree, _info_dict(inf)
 
     def tree_predict(self, tree):
         """The leaf vote of `tree` (the dict tree_fit gives) for every row (dge_tree_predict_vectors) -> uint8 [rows], 255 on an absent row."""
@@ -862,7 +853,7 @@ class Vectors:
         inf = TreeInfo()
         check(lib.dge_tree_cv_vectors(self._h, _ptr(y), _ptr(fold), F, C.byref(cfg), _ptr(correct), _ptr(tested), _ptr(nodes), _ptr(depth), C.byref(inf)))
         from .evaluate import cv_scores
-        return dict(cv_scores(correct, tested), n_nodes=nodes, depth=depth, info={f[0]: getattr(inf, f[0]) for f in TreeInfo._fields_})
+        return dict(cv_scores(correct, tested), n_nodes=nodes, depth=depth, info=_info_dict(inf))
 
     def ridge_loo(self, y, lambdas, select=None, want_beta=True, want_pred=True):
         """Leave-one-out ridge regression on these rows as the rule of include/dge.h (dge_ridge_loo_vectors): the same bits for the same used rows in row order,
@@ -877,7 +868,7 @@ class Vectors:
         beta = np.empty((L, T, dim + 1), np.float64) if want_beta else None
         pred = np.empty((L, T, n), np.float64) if want_pred else None
         check(lib.dge_ridge_loo_vectors(self._h, _ptr(y), T, _ptr(select), _ptr(lam), L, _ptr(mae), _ptr(mre), _ptr(beta), _ptr(pred), C.byref(inf)))
-        return dict(mae=mae, mre=mre, beta=beta, loo_pred=pred, info={f[0]: getattr(inf, f[0]) for f in RidgeInfo._fields_})
+        return dict(mae=mae, mre=mre, beta=beta, loo_pred=pred, info=_info_dict(inf))
 
     def ridge_predict(self, beta):
         """The predictions of the models beta [.. x (dim + 1)] (what ridge_loo gives, the intercept first) for every row (dge_ridge_predict_vectors)
@@ -913,14 +904,11 @@ class Vectors:
         n = self.shape[0]
         y = self._label_columns(y)
         L = y.shape[0]
-        if select is not None:
-            select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
-            if select.shape != (n,):
-                raise ValueError("select must hold one entry per row")
+        select = _select_mask(select, n)
         cfg = self._svm_cfg(C, gamma, eps, max_iter, state, launch_iters)
         coef = np.empty((L, n), np.float64); bias = np.empty(L, np.float64); iters = np.zeros(L, np.int64); conv = np.zeros(L, np.int32); inf = SvmInfo()
         check(lib.dge_svm_fit_vectors(self._h, _ptr(y), L, _ptr(select), _byref(cfg), _ptr(coef), _ptr(bias), _ptr(iters), _ptr(conv), _byref(inf)))
-        return dict(coef=coef, bias=bias, iterations=iters, converged=conv, gamma=cfg.gamma, info={f[0]: getattr(inf, f[0]) for f in SvmInfo._fields_})
+        return dict(coef=coef, bias=bias, iterations=iters, converged=conv, gamma=cfg.gamma, info=_info_dict(inf))
 
     def svm_decision(self, coef, bias, gamma, x=None):
         """f(x) of the models (coef [.. x rows], bias [..]: what svm_fit gives for these rows) for every row of x, another Vectors of the same dim, or of these
@@ -955,7 +943,7 @@ class Vectors:
                                      _byref(inf)))
         from .evaluate import svm_scores
         return dict(svm_scores(correct, tested), iterations=iters, support=support, converged=conv, decision=decision, gamma=cfg.gamma,
-                    info={f[0]: getattr(inf, f[0]) for f in SvmInfo._fields_})
+                    info=_info_dict(inf))
 
 
 def make_config(dim, window, n_vertices, negative=5, min_count=2, epochs=1, workers=0, alpha=0.025, min_alpha=1e-4,

@@ -46,6 +46,21 @@ def ndcg_vectors(vectors, gnd_vectors, k=10):
     return vectors.ndcg_against(gnd_vectors, k)
 
 
+def _info_dict(inf):
+    """the fields of a ctypes info struct"""
+    return {f[0]: getattr(inf, f[0]) for f in inf._fields_}
+
+
+def _select_mask(select, n):
+    """select -> uint8 [n], non-zero = take the row; None stays None"""
+    if select is None:
+        return None
+    select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+    if select.shape != (n,):
+        raise ValueError("select must hold one entry per row")
+    return select
+
+
 def kmeans_gpu(features, k, seed=1, n_init=10, max_iter=300, select=None, init=None, device=0):
     """k-means of host rows [n x dim] on the device as the rule of include/dge.h (dge_kmeans).  -> (labels int32 [n], -1 on rows select leaves out;
     centres float32 [k x dim]; info: the fields of struct dge_kmeans_info)."""
@@ -55,10 +70,7 @@ def kmeans_gpu(features, k, seed=1, n_init=10, max_iter=300, select=None, init=N
     n, dim = f.shape
     k = int(k)
     p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
-    if select is not None:
-        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
-        if select.shape != (n,):
-            raise ValueError("select must hold one entry per row")
+    select = _select_mask(select, n)
     if init is not None:
         init = np.ascontiguousarray(init, np.float32)
         if init.shape != (k, dim):
@@ -66,7 +78,7 @@ def kmeans_gpu(features, k, seed=1, n_init=10, max_iter=300, select=None, init=N
     cfg = KmeansCfg(k, int(n_init), int(max_iter), 0, int(seed) & 0xFFFFFFFFFFFFFFFF)
     labels = np.empty(n, np.int32); centres = np.empty((max(k, 0), dim), np.float32); inf = KmeansInfo()
     check(lib.dge_kmeans(int(device), p(f), n, dim, p(select), C.byref(cfg), p(init), p(labels), p(centres), C.byref(inf)))
-    return labels, centres, {fl[0]: getattr(inf, fl[0]) for fl in KmeansInfo._fields_}
+    return labels, centres, _info_dict(inf)
 
 
 def clustering_accuracy(labels, gnd, k):
@@ -126,7 +138,7 @@ def nmf_gpu(rows, cols, vals, shape, rank=10, max_iter=30, update="divergence", 
             raise ValueError("init must be (W [%d x %d], H [%d x %d])" % (n, rank, rank, m))
     W = np.empty((max(n, 0), max(rank, 0)), np.float64); H = np.empty((max(rank, 0), max(m, 0)), np.float64); inf = NmfInfo()
     check(lib.dge_nmf_coo(int(device), p(r), p(c), p(v), len(v), n, m, C.byref(cfg), p(iw), p(ih), p(W), p(H), C.byref(inf)))
-    return W, H, {fl[0]: getattr(inf, fl[0]) for fl in NmfInfo._fields_ if fl[0] != "reserved"}
+    return W, H, {k: v for k, v in _info_dict(inf).items() if k != "reserved"}
 
 
 def nmf_features(W, H):
@@ -168,7 +180,7 @@ def line_gpu(src, dst, w, n, dim=20, order=2, negative=5, samples=1000000, batch
             raise ValueError("init must be X [%d x %d] or (X, Y) of that shape" % (n, dim))
     X = np.empty((max(n, 0), max(dim, 0)), np.float64); Y = np.empty_like(X); touched = np.empty(max(n, 0), np.uint8); inf = LineInfo()
     check(lib.dge_line_coo(int(device), p(s), p(d), p(v), len(v), n, C.byref(cfg), p(ix), p(iy), p(X), p(Y), p(touched), C.byref(inf)))
-    return X, Y, touched.astype(bool), {fl[0]: getattr(inf, fl[0]) for fl in LineInfo._fields_}
+    return X, Y, touched.astype(bool), _info_dict(inf)
 
 
 def line_features(X, touched, dtype=np.float32):
@@ -220,6 +232,18 @@ def stratified_folds(y, n_folds, select=None):
     return fold
 
 
+def _cv_folds(y, n_folds, fold, select):
+    """The folds of a cross-validation on host rows: the caller's, or stratified_folds of the labels y [n] -> int32 [n]"""
+    if fold is None:
+        fold = stratified_folds(y, n_folds, select)
+    elif select is not None:
+        raise ValueError("give fold or select, not both: fold -1 leaves a row out")
+    fold = np.ascontiguousarray(fold, np.int32)
+    if fold.shape != y.shape:
+        raise ValueError("fold must hold one entry per row")
+    return fold
+
+
 def _tree_args(features, y):
     f = np.ascontiguousarray(features, np.float32)
     if f.ndim != 2:
@@ -240,10 +264,7 @@ def tree_fit_gpu(features, y, select=None, max_depth=0, min_samples_split=2, min
     f, y = _tree_args(features, y)
     n, dim = f.shape
     p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)      # noqa: E731
-    if select is not None:
-        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
-        if select.shape != (n,):
-            raise ValueError("select must hold one entry per row")
+    select = _select_mask(select, n)
     cfg = TreeCfg(int(max_depth), int(min_samples_split), int(min_samples_leaf), 0)
     cap = max(2 * n - 1, 1)
     feature = np.empty(cap, np.int32); threshold = np.empty(cap, np.float64); left = np.empty(cap, np.int32); count = np.empty(cap, np.int64); pos = np.empty(cap, np.int64)
@@ -251,7 +272,7 @@ def tree_fit_gpu(features, y, select=None, max_depth=0, min_samples_split=2, min
     check(lib.dge_tree_fit(int(device), p(f), n, dim, p(y), p(select), C.byref(cfg), cap, p(feature), p(threshold), p(left), p(count), p(pos), C.byref(inf)))
     m = inf.n_nodes
     tree = dict(feature=feature[:m].copy(), threshold=threshold[:m].copy(), left=left[:m].copy(), count=count[:m].copy(), pos=pos[:m].copy())
-    return tree, {fl[0]: getattr(inf, fl[0]) for fl in TreeInfo._fields_}
+    return tree, _info_dict(inf)
 
 
 def tree_cv_gpu(features, y, n_folds=10, fold=None, select=None, max_depth=0, min_samples_split=2, min_samples_leaf=1, device=0):
@@ -263,19 +284,13 @@ def tree_cv_gpu(features, y, n_folds=10, fold=None, select=None, max_depth=0, mi
     f, y = _tree_args(features, y)
     n, dim = f.shape
     F = int(n_folds)
-    if fold is None:
-        fold = stratified_folds(y, F, select)
-    elif select is not None:
-        raise ValueError("give fold or select, not both: fold -1 leaves a row out")
-    fold = np.ascontiguousarray(fold, np.int32)
-    if fold.shape != (n,):
-        raise ValueError("fold must hold one entry per row")
+    fold = _cv_folds(y, F, fold, select)
     p = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
     cfg = TreeCfg(int(max_depth), int(min_samples_split), int(min_samples_leaf), 0)
     correct = np.zeros(max(F, 0), np.int64); tested = np.zeros(max(F, 0), np.int64); nodes = np.zeros(max(F, 0), np.int32); depth = np.zeros(max(F, 0), np.int32)
     inf = TreeInfo()
     check(lib.dge_tree_cv(int(device), p(f), n, dim, p(y), p(fold), F, C.byref(cfg), p(correct), p(tested), p(nodes), p(depth), C.byref(inf)))
-    return dict(cv_scores(correct, tested), n_nodes=nodes, depth=depth, info={fl[0]: getattr(inf, fl[0]) for fl in TreeInfo._fields_})
+    return dict(cv_scores(correct, tested), n_nodes=nodes, depth=depth, info=_info_dict(inf))
 
 
 def _ridge_args(n, y, lambdas, select):
@@ -288,10 +303,7 @@ def _ridge_args(n, y, lambdas, select):
     lam = np.ascontiguousarray(np.atleast_1d(np.asarray(lambdas, np.float64)))
     if lam.ndim != 1:
         raise ValueError("lambdas must be a number or one-dimensional")
-    if select is not None:
-        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
-        if select.shape != (n,):
-            raise ValueError("select must hold one entry per row")
+    select = _select_mask(select, n)
     return np.ascontiguousarray(y), lam, select
 
 
@@ -311,7 +323,7 @@ def ridge_loo_gpu(features, y, lambdas, select=None, device=0):
     mae = np.empty((L, T), np.float64); mre = np.empty((L, T), np.float64); beta = np.empty((L, T, dim + 1), np.float64); pred = np.empty((L, T, n), np.float64)
     inf = RidgeInfo()
     check(lib.dge_ridge_loo(int(device), p(f), n, dim, p(y), T, p(select), p(lam), L, p(mae), p(mre), p(beta), p(pred), C.byref(inf)))
-    return dict(mae=mae, mre=mre, beta=beta, loo_pred=pred, info={fl[0]: getattr(inf, fl[0]) for fl in RidgeInfo._fields_})
+    return dict(mae=mae, mre=mre, beta=beta, loo_pred=pred, info=_info_dict(inf))
 
 
 def svm_scores(correct, tested):
@@ -351,14 +363,11 @@ def svm_fit_gpu(features, y, select=None, C=1.0, gamma=None, eps=1e-3, max_iter=
     n, dim = f.shape
     L = y.shape[0]
     p = lambda a: None if a is None else a.ctypes.data_as(Ct.c_void_p)      # noqa: E731
-    if select is not None:
-        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
-        if select.shape != (n,):
-            raise ValueError("select must hold one entry per row")
+    select = _select_mask(select, n)
     cfg = SvmCfg(float(C), 1.0 / max(dim, 1) if gamma is None else float(gamma), float(eps), int(max_iter), int(state), int(launch_iters))
     coef = np.empty((L, n), np.float64); bias = np.empty(L, np.float64); iters = np.zeros(L, np.int64); conv = np.zeros(L, np.int32); inf = SvmInfo()
     check(lib.dge_svm_fit(int(device), p(f), n, dim, p(y), L, p(select), Ct.byref(cfg), p(coef), p(bias), p(iters), p(conv), Ct.byref(inf)))
-    return dict(coef=coef, bias=bias, iterations=iters, converged=conv, gamma=cfg.gamma, info={fl[0]: getattr(inf, fl[0]) for fl in SvmInfo._fields_})
+    return dict(coef=coef, bias=bias, iterations=iters, converged=conv, gamma=cfg.gamma, info=_info_dict(inf))
 
 
 def svm_cv_gpu(features, y, n_folds=10, fold=None, select=None, C=1.0, gamma=None, eps=1e-3, max_iter=10_000_000, state=0, launch_iters=0, want_decision=False,
@@ -372,13 +381,7 @@ def svm_cv_gpu(features, y, n_folds=10, fold=None, select=None, C=1.0, gamma=Non
     f, y = _svm_args(features, y)
     n, dim = f.shape
     L, F = y.shape[0], int(n_folds)
-    if fold is None:
-        fold = stratified_folds(y[0], F, select)
-    elif select is not None:
-        raise ValueError("give fold or select, not both: fold -1 leaves a row out")
-    fold = np.ascontiguousarray(fold, np.int32)
-    if fold.shape != (n,):
-        raise ValueError("fold must hold one entry per row")
+    fold = _cv_folds(y[0], F, fold, select)
     p = lambda a: None if a is None else a.ctypes.data_as(Ct.c_void_p)      # noqa: E731
     cfg = SvmCfg(float(C), 1.0 / max(dim, 1) if gamma is None else float(gamma), float(eps), int(max_iter), int(state), int(launch_iters))
     shape = (L, max(F, 0))
@@ -387,4 +390,4 @@ def svm_cv_gpu(features, y, n_folds=10, fold=None, select=None, C=1.0, gamma=Non
     decision = np.empty((L, n), np.float64) if want_decision else None
     check(lib.dge_svm_cv(int(device), p(f), n, dim, p(y), L, p(fold), F, Ct.byref(cfg), p(correct), p(tested), p(iters), p(support), p(conv), p(decision), Ct.byref(inf)))
     return dict(svm_scores(correct, tested), iterations=iters, support=support, converged=conv, decision=decision, gamma=cfg.gamma,
-                info={fl[0]: getattr(inf, fl[0]) for fl in SvmInfo._fields_})
+                info=_info_dict(inf))
