@@ -259,7 +259,7 @@ extern "C" int dge_flows_add_entries(dge_flows* f, const int32_t* hour, const in
     SEQ_TRY(dge_require_device(rg->device));
     if (n == 0) return DGE_OK;
     SeqRun R;
-    SEQ_TRY(trip_open(R, rg->device, who));
+    SEQ_TRY(seq_open(R, rg->device, who));
     dge_tmp<uint64_t> d_key, nkey;
     dge_tmp<int64_t> d_cnt, ncnt;
     dge_tmp<unsigned long long> counters;
@@ -295,7 +295,7 @@ extern "C" int dge_flows_window_edges(const dge_flows* f, const dge_hour_window*
     if (f->n == 0) return DGE_OK;
     SEQ_TRY(dge_require_device(f->regions->device));
     SeqRun R;
-    SEQ_TRY(trip_open(R, f->regions->device, who));
+    SEQ_TRY(seq_open(R, f->regions->device, who));
     dge_tmp<uint64_t> okey;
     dge_tmp<int64_t> ow;
     int64_t E = 0;
@@ -319,7 +319,7 @@ extern "C" int dge_graph_add_flow_windows(dge_graph* g, const dge_flows* f, cons
     SEQ_TRY(od_check(g, names, who));
     SEQ_TRY(dge_require_device(g->device));
     SeqRun R;
-    SEQ_TRY(trip_open(R, g->device, who));
+    SEQ_TRY(seq_open(R, g->device, who));
     dge_tmp<uint64_t> okey;
     dge_tmp<int64_t> ow;
     int64_t E = 0, Rn = 0, S = 0;
@@ -364,7 +364,7 @@ extern "C" int dge_flows_triplets(const dge_flows* f, const dge_triplet_rule* ru
     if (f->n == 0 || rg->R < 3) return DGE_OK;
     SEQ_TRY(dge_require_device(rg->device));
     SeqRun R;
-    SEQ_TRY(trip_open(R, rg->device, who));
+    SEQ_TRY(seq_open(R, rg->device, who));
     const uint64_t Ru = (uint64_t)rg->R;
     const dge_hour_window five[5] = {r.A, r.B, r.C, r.D, r.E};
     dge_tmp<uint64_t> wkey, e12, e23, e31;

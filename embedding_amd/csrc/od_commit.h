@@ -8,8 +8,6 @@
 
 #include "seq_tokens.h"
 
-struct OdKeepFlag { const uint8_t* keep; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n ? keep[i] : 0; } };
-
 // the ids of the kept flows' endpoints: edge e's at [2e], [2e + 1]
 static __global__ void __launch_bounds__(SEQ_BLOCK) k_od_endpoints(const int64_t* src_id, const int64_t* dst_id, const int64_t* keepx, int64_t rows, int64_t* ends) {
     const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
@@ -115,7 +113,7 @@ void od_reset(dge_graph* g) {
     DGE_HIP(hipMemsetAsync(mark.p, 0, (size_t)std::max<int64_t>(Rn, 1), R.stream));
     if (E) hipLaunchKernelGGL(k_od_edges, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, src_id, dst_id, w_bits, slice, keepx, rows, regions.p, Rn, T, coo_src.p, coo_dst.p,
                               coo_w.p, mark.p);
-    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdKeepFlag{mark.p, Rn}), markx.p, Rn + 1));
+    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqByteFlag{mark.p, Rn}), markx.p, Rn + 1));
     SEQ_TRY(seq_kernels_end(R));
     int64_t S = 0;
     SEQ_TRY(seq_read_back(R, &S, markx.p + Rn, 8));

@@ -7,9 +7,10 @@
 //
 // The passes, on the one buffer of seq_tokens.h (every piece with its pad byte):
 //   seq_tokenise               token t's first byte and line, the rows (rowx, row_first) — the .seq reader's kernels and chunk transport, unchanged
-//   k_od_ragged                every row must have 3 tokens
+//   k_seq_ragged               every row must have 3 tokens
 //   k_od_parse                 a lane per row: its piece (= slice), od_parse.h's integer routines -> src id, dst id, the weight's bits; "not mine" weights flagged
-//   host path                  the flagged tokens' bytes in one blob, strtod in the "C" locale, k_od_scatter puts the bits in place
+//   host path                  seq_pick / seq_tokens_to_host / seq_host_numbers (seq_tokens.h): the flagged tokens' bytes in one blob, strtod in the "C"
+//                              locale; k_od_scatter puts the bits in place
 //   k_od_keep                  a weight that is not finite is a bad token; keep[r] = w > 0
 //   scan of keep               a stable compaction: kept flow r is edge keepx[r], edges stand in text order
 //   od_commit.h, which dge_graph_add_flows (trip_map.hip) runs too:
@@ -27,20 +28,11 @@
 // whitespace byte and the buffer ends in SEQ_TAIL blanks, so the byte loops stop inside the allocation; their length is the token's.  Lanes of a wave hold
 // adjacent lines (~20 bytes each), so their reads fall into the same few cache lines; divergence is over the digits of a token (ids 5-6, weights 1-4 in
 // the reference's files), and the division loop of od_parse_f64 has a fixed trip count.
-#include <locale.h>
-#include <stdlib.h>
-
 #include "od_commit.h"
 #include "od_parse.h"
 #include "seq_tokens.h"
 
 // ------------------------------------------------------------------------------------------ kernels
-__global__ void __launch_bounds__(SEQ_BLOCK) k_od_ragged(const int64_t* row_first, int64_t rows, unsigned long long* ragged) {
-    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (r >= rows) return;
-    if (row_first[r + 1] - row_first[r] != 3) atomicMin(ragged, (unsigned long long)r);
-}
-
 // row r = tokens row_first[r] .. + 2 (the ragged pass has run).  status[r]: 1 = the host finishes the weight.  bad_at: least offset of a malformed token
 __global__ void __launch_bounds__(SEQ_BLOCK) k_od_parse(const uint8_t* buf, const int64_t* tok_start, const int64_t* row_first, int64_t rows, const int64_t* piece_off,
                                                         int64_t n_pieces, int64_t* src_id, int64_t* dst_id, uint64_t* w_bits, int32_t* slice, uint8_t* status,
@@ -70,22 +62,10 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_od_parse(const uint8_t* buf, cons
     if (threadIdx.x == 0 && sum) atomicAdd(n_host, sum);
 }
 
-struct OdHostFlag { const uint8_t* status; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n ? status[i] : 0; } };
-struct OdHostLen {       // bytes of host token k (the weight of row host_row[k]) in the blob, its NUL included
-    const uint8_t* buf; const int64_t* tok_start; const int64_t* row_first; const int64_t* host_row; int64_t n;
-    __device__ int64_t operator()(int64_t k) const { return k < n ? seq_tok_len(buf + tok_start[row_first[host_row[k]] + 2]) + 1 : 0; }
+struct OdHostStart {     // host token k: the weight, the third token, of row host_row[k]
+    const int64_t* tok_start; const int64_t* row_first; const int64_t* host_row;
+    __device__ int64_t operator()(int64_t k) const { return tok_start[row_first[host_row[k]] + 2]; }
 };
-
-__global__ void __launch_bounds__(SEQ_BLOCK) k_od_host_bytes(const uint8_t* buf, const int64_t* tok_start, const int64_t* row_first, const int64_t* host_row, const int64_t* host_off,
-                                                             int64_t n, uint8_t* blob) {
-    const int64_t k = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (k >= n) return;
-    const uint8_t* src = buf + tok_start[row_first[host_row[k]] + 2];
-    const int64_t len = host_off[k + 1] - host_off[k] - 1;
-    uint8_t* dst = blob + host_off[k];
-    for (int64_t i = 0; i < len; i++) dst[i] = src[i];
-    dst[len] = 0;
-}
 
 __global__ void __launch_bounds__(SEQ_BLOCK) k_od_scatter(const int64_t* host_row, const uint64_t* host_bits, int64_t n, uint64_t* w_bits) {
     const int64_t k = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
@@ -115,14 +95,13 @@ int od_read(SeqRun& R, dge_graph* g, dge_names* names, dge_od_info* info, const 
     SEQ_TRY(seq_alloc(R, words, 3, "the counters"));
     DGE_HIP(hipMemcpyAsync(words.p, w, sizeof(w), hipMemcpyHostToDevice, R.stream));
     SEQ_TRY(seq_kernels_begin(R));
-    if (rows) hipLaunchKernelGGL(k_od_ragged, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, R.row_first.p, rows, words.p);
+    if (rows) hipLaunchKernelGGL(k_seq_ragged, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, R.row_first.p, (const uint8_t*)nullptr, rows, (int64_t)3, words.p);
     SEQ_TRY(seq_kernels_end(R));
     SEQ_TRY(seq_read_back(R, w, words.p, 8));
     if (w[0] != ~0ull) {
-        int64_t f[2], at = 0;
-        SEQ_TRY(seq_read_back(R, f, R.row_first.p + (int64_t)w[0], 16));
-        SEQ_TRY(seq_read_back(R, &at, R.tok_start.p + f[0], 8));
-        DGE_FAIL(DGE_ERR_IO, "%s: the line at %s has %lld token%s where 3 are expected: src dst w", who, seq_where(R, at).c_str(), (long long)(f[1] - f[0]), f[1] - f[0] == 1 ? "" : "s");
+        int64_t at = 0, count = 0;
+        SEQ_TRY(seq_row_where(R, (int64_t)w[0], &at, &count));
+        DGE_FAIL(DGE_ERR_IO, "%s: the line at %s has %lld token%s where 3 are expected: src dst w", who, seq_where(R, at).c_str(), (long long)count, count == 1 ? "" : "s");
     }
 
     // ---- the flows: two ids, a weight, the slice
@@ -148,30 +127,16 @@ int od_read(SeqRun& R, dge_graph* g, dge_names* names, dge_od_info* info, const 
     // ---- the host path: the flagged weights' bytes in one blob, strtod, the bits back into place
     const int64_t n_host = (int64_t)w[2];
     if (n_host > 0) {
-        dge_tmp<int64_t> hostx, host_row, host_off;
-        dge_tmp<uint8_t> blob;
+        dge_tmp<int64_t> host_row;
         dge_tmp<uint64_t> host_bits;
-        SEQ_TRY(seq_alloc(R, hostx, rows + 1, "the host tokens' numbers"));
-        SEQ_TRY(seq_alloc(R, host_row, n_host, "the host tokens"));
-        SEQ_TRY(seq_alloc(R, host_off, n_host + 1, "the host tokens' offsets"));
+        std::vector<int64_t> off;
+        std::unique_ptr<char[]> text;
+        std::vector<uint64_t> bits;
         SEQ_TRY(seq_alloc(R, host_bits, n_host, "the host tokens' values"));
         SEQ_TRY(seq_kernels_begin(R));
-        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdHostFlag{status.p, rows}), hostx.p, rows + 1));
-        hipLaunchKernelGGL(k_seq_name_tok, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, hostx.p, (int64_t)0, rows, host_row.p);
-        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdHostLen{R.buf.p, R.tok_start.p, R.row_first.p, host_row.p, n_host}), host_off.p,
-                         n_host + 1));
-        std::vector<int64_t> off((size_t)n_host + 1);
-        SEQ_TRY(seq_read_back(R, off.data(), host_off.p, (size_t)(n_host + 1) * 8));
-        SEQ_TRY(seq_alloc(R, blob, off[(size_t)n_host], "the host tokens' bytes"));
-        hipLaunchKernelGGL(k_od_host_bytes, dim3(seq_grid(n_host)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.tok_start.p, R.row_first.p, host_row.p, host_off.p, n_host, blob.p);
-        SEQ_TRY(seq_kernels_end(R));
-        std::unique_ptr<char[]> text(new char[(size_t)off[(size_t)n_host]]);
-        SEQ_TRY(seq_read_back(R, text.get(), blob.p, (size_t)off[(size_t)n_host]));
-        std::vector<uint64_t> bits((size_t)n_host);
-        locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
-        if (!c_locale) DGE_FAIL(DGE_ERR_STATE, "%s: the \"C\" locale is not available", who);
-        for (int64_t k = 0; k < n_host; k++) { const double d = strtod_l(text.get() + off[(size_t)k], nullptr, c_locale); memcpy(&bits[(size_t)k], &d, 8); }
-        freelocale(c_locale);
+        SEQ_TRY(seq_pick(R, status.p, rows, n_host, host_row, "the host tokens"));
+        SEQ_TRY(seq_tokens_to_host(R, OdHostStart{R.tok_start.p, R.row_first.p, host_row.p}, n_host, off, text, "the host tokens"));
+        SEQ_TRY(seq_host_numbers(text.get(), off.data(), n_host, bits, who));
         DGE_HIP(hipMemcpyAsync(host_bits.p, bits.data(), (size_t)n_host * 8, hipMemcpyHostToDevice, R.stream));
         SEQ_TRY(seq_kernels_begin(R));
         hipLaunchKernelGGL(k_od_scatter, dim3(seq_grid(n_host)), dim3(SEQ_BLOCK), 0, R.stream, host_row.p, host_bits.p, n_host, w_bits.p);
@@ -181,7 +146,7 @@ int od_read(SeqRun& R, dge_graph* g, dge_names* names, dge_od_info* info, const 
     // ---- the kept flows, numbered in text order
     SEQ_TRY(seq_kernels_begin(R));
     if (rows) hipLaunchKernelGGL(k_od_keep, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, w_bits.p, R.tok_start.p, R.row_first.p, rows, keep.p, words.p + 1);
-    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), OdKeepFlag{keep.p, rows}), keepx.p, rows + 1));
+    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqByteFlag{keep.p, rows}), keepx.p, rows + 1));
     SEQ_TRY(seq_kernels_end(R));
     SEQ_TRY(seq_read_back(R, w + 1, words.p + 1, 8));
     if (w[1] != ~0ull)
@@ -205,35 +170,23 @@ int od_read(SeqRun& R, dge_graph* g, dge_names* names, dge_od_info* info, const 
 // ------------------------------------------------------------------------------------------ entries
 extern "C" int dge_graph_add_od_texts(dge_graph* g, const char* const* texts, const int64_t* n_bytes, int32_t n_slices, dge_names* names, dge_od_info* info) {
     if (!g || !texts || !n_bytes || n_slices < 1) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_od_texts: null or negative argument, or fewer than 1 slice");
-    for (int32_t k = 0; k < n_slices; k++)
-        if (n_bytes[k] < 0 || (n_bytes[k] > 0 && !texts[k])) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_od_texts: text %d is null or of negative size", k);
+    SEQ_TRY(seq_check_texts(texts, n_bytes, n_slices, "dge_graph_add_od_texts"));
     SEQ_TRY(od_check(g, names, "dge_graph_add_od_texts"));
     SEQ_TRY(dge_require_device(g->device));
     SeqRun R;
     R.device = g->device;
-    for (int32_t k = 0; k < n_slices; k++) {
-        SeqPiece p; p.mem = reinterpret_cast<const uint8_t*>(texts[k]); p.size = n_bytes[k];
-        R.pieces.push_back(p);
-    }
+    SEQ_TRY(seq_add_texts(R.pieces, texts, n_bytes, n_slices, "dge_graph_add_od_texts"));
     return od_read(R, g, names, info, "dge_graph_add_od_texts");
 }
 
 extern "C" int dge_graph_add_od_files(dge_graph* g, const char* const* paths, int32_t n_slices, dge_names* names, dge_od_info* info) {
     if (!g || !paths || n_slices < 1) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_od_files: null or negative argument, or fewer than 1 slice");
-    for (int32_t k = 0; k < n_slices; k++) if (!paths[k]) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_od_files: path %d is null", k);
+    SEQ_TRY(seq_check_paths(paths, n_slices, "dge_graph_add_od_files"));
     SEQ_TRY(od_check(g, names, "dge_graph_add_od_files"));
     SEQ_TRY(dge_require_device(g->device));
     SeqRun R;
     R.device = g->device;
-    for (int32_t k = 0; k < n_slices; k++) {
-        SeqPiece p; p.path = paths[k];
-        p.fd = open(paths[k], O_RDONLY | O_CLOEXEC);
-        if (p.fd < 0) DGE_FAIL(DGE_ERR_IO, "cannot open %s: %s", paths[k], strerror(errno));
-        R.pieces.push_back(p);                     // (the run closes it)
-        struct stat st;
-        if (fstat(p.fd, &st) != 0 || !S_ISREG(st.st_mode)) DGE_FAIL(DGE_ERR_IO, "cannot read %s: not a regular file", paths[k]);
-        R.pieces.back().size = (int64_t)st.st_size;
-    }
+    SEQ_TRY(seq_add_files(R.pieces, paths, n_slices, "dge_graph_add_od_files"));
     return od_read(R, g, names, info, "dge_graph_add_od_files");
 }
 

@@ -108,8 +108,7 @@ extern "C" int dge_walks_from_seq_text(int device, const char* text, int64_t n_b
     SEQ_TRY(dge_require_device(device));
     SeqRun R;
     R.device = device;
-    SeqPiece p; p.mem = reinterpret_cast<const uint8_t*>(text); p.size = n_bytes;
-    R.pieces.push_back(p);
+    SEQ_TRY(seq_add_texts(R.pieces, &text, &n_bytes, 1, "dge_walks_from_seq_text"));
     SeqOptions opt; opt.intern = intern ? 1 : 0;
     SEQ_TRY(seq_ingest(R, names, opt, "dge_walks_from_seq_text"));
     return seq_finish(R, names, opt.intern, out, info, "dge_walks_from_seq_text");
@@ -117,20 +116,12 @@ extern "C" int dge_walks_from_seq_text(int device, const char* text, int64_t n_b
 
 extern "C" int dge_walks_from_seq_files(int device, const char* const* paths, int32_t n_paths, dge_names* names, int intern, dge_walks** out, dge_seq_info* info) {
     if (!out || !names || n_paths < 0 || (n_paths > 0 && !paths)) DGE_FAIL(DGE_ERR_ARG, "dge_walks_from_seq_files: null or negative argument");
-    for (int32_t k = 0; k < n_paths; k++) if (!paths[k]) DGE_FAIL(DGE_ERR_ARG, "dge_walks_from_seq_files: path %d is null", k);
+    SEQ_TRY(seq_check_paths(paths, n_paths, "dge_walks_from_seq_files"));
     *out = nullptr;
     SEQ_TRY(dge_require_device(device));
     SeqRun R;
     R.device = device;
-    for (int32_t k = 0; k < n_paths; k++) {
-        SeqPiece p; p.path = paths[k];
-        p.fd = open(paths[k], O_RDONLY | O_CLOEXEC);
-        if (p.fd < 0) DGE_FAIL(DGE_ERR_IO, "cannot open %s: %s", paths[k], strerror(errno));
-        R.pieces.push_back(p);                     // (the run closes it)
-        struct stat st;
-        if (fstat(p.fd, &st) != 0 || !S_ISREG(st.st_mode)) DGE_FAIL(DGE_ERR_IO, "cannot read %s: not a regular file", paths[k]);
-        R.pieces.back().size = (int64_t)st.st_size;
-    }
+    SEQ_TRY(seq_add_files(R.pieces, paths, n_paths, "dge_walks_from_seq_files"));
     SeqOptions opt; opt.intern = intern ? 1 : 0;
     SEQ_TRY(seq_ingest(R, names, opt, "dge_walks_from_seq_files"));
     return seq_finish(R, names, opt.intern, out, info, "dge_walks_from_seq_files");
@@ -143,8 +134,7 @@ extern "C" int dge_selftest_seq_intern(int device, const char* text, int64_t n_b
     SEQ_TRY(dge_require_device(device));
     SeqRun R;
     R.device = device;
-    SeqPiece p; p.mem = reinterpret_cast<const uint8_t*>(text); p.size = n_bytes;
-    R.pieces.push_back(p);
+    SEQ_TRY(seq_add_texts(R.pieces, &text, &n_bytes, 1, "dge_selftest_seq_intern"));
     SeqOptions opt; opt.hash_bits = hash_bits; opt.initial_slots = initial_slots;
     SEQ_TRY(seq_ingest(R, nullptr, opt, "dge_selftest_seq_intern"));
     *n_tokens = R.T;

@@ -1,6 +1,7 @@
 // seq_tokens.h — the tokeniser, the name table and the byte transport that the text readers share: seq_ingest.hip (.seq walks), vec_read.hip (.vec vectors) and
 // od_read.hip (.od flows; it interns nothing) all include it, so every kernel and host routine below exists once in source.  Everything is static: each
-// translation unit gets its own copy of the code and the library exports nothing from here.  Outside the build stamp, like the readers.
+// translation unit gets its own copy of the code and the library exports nothing from here.  Outside the build stamp, like the readers.  The host half of
+// the intake — files and texts as pieces, the read step, the joiner of the one buffer — is plain C++ in seq_pieces.h, which this header includes.
 //
 // One buffer holds everything the kernels read (seq_plan.h: seq_layout): the names the caller's dge_names already holds, one per line, then every file
 // (or the caller's text) with one pad byte behind it, then blanks up to whole chunks.  The prior names are thereby the first tokens of the buffer and take
@@ -13,7 +14,9 @@
 //                              every token (.seq), or the prior names and the token that opens each row (.vec)
 //   k_seq_intern               open addressing, one 8-byte slot per string = the SMALLEST entry index seen with that string (its first appearance)
 //   ids                        a scan of "e is its string's first appearance" numbers the names in first-appearance order; id[e] = number of its string
-//   k_seq_name_*               the new names' bytes into one blob for the host
+//   seq_tokens_to_host         selected tokens (the new names; the value tokens a reader leaves to the host) NUL-terminated into one blob for the host:
+//                              seq_pick or k_seq_name_tok lists them, k_seq_tok_bytes copies them, seq_host_numbers finishes numbers with strtod / strtof
+//   k_seq_ragged               the least row that has not the number of tokens its reader wants; seq_row_where turns it into an offset for the message
 //
 // Why the intern pass is right on eight L2s that are not coherent.  A slot's history is EMPTY -> t1 -> t2 < t1 -> ..., every ti a
 // token of ONE string: a slot is claimed once (compare-and-swap from EMPTY) and afterwards only lowered (atomicMin) by tokens that compared equal to
@@ -30,11 +33,8 @@
 // Contention: a token that reads its string in the slot with a first appearance below its own index issues no atomic at all — on a corpus of few names
 // that is nearly every token (atomics on one address complete one after the other).
 #pragma once
-#include <errno.h>
-#include <fcntl.h>
-#include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
+#include <locale.h>
+#include <stdlib.h>
 
 #include <chrono>
 #include <hipcub/hipcub.hpp>
@@ -45,7 +45,7 @@
 
 #include "dge_algos.h"
 #include "dge_device.h"
-#include "seq_plan.h"
+#include "seq_pieces.h"
 
 // blob: count strings, string k at blob + off[k], NUL-terminated; takes the blob over
 static inline void names_append(dge_names* n, std::unique_ptr<char[]> blob, const int64_t* off, int64_t count) {
@@ -210,9 +210,18 @@ struct SeqFirstFlag {    // token t is the first appearance of its string
     const unsigned long long* table; const int64_t* slot; int64_t T;
     __device__ int64_t operator()(int64_t t) const { return (t < T && table[slot[t]] == (unsigned long long)t) ? 1 : 0; }
 };
-struct SeqNameLen {      // bytes of new name k in the blob, its NUL included
-    const int64_t* name_tok; const int64_t* tok_len; int64_t n;
-    __device__ int64_t operator()(int64_t k) const { return k < n ? tok_len[name_tok[k]] + 1 : 0; }
+struct SeqByteFlag {     // byte i of an array is set
+    const uint8_t* p; int64_t n;
+    __device__ int64_t operator()(int64_t i) const { return (i < n && p[i] != 0) ? 1 : 0; }
+};
+template <typename Start>
+struct SeqItemLen {      // bytes of item k in the blob, its NUL included: the token whose first byte is start_of(k)
+    const uint8_t* buf; Start start_of; int64_t n;
+    __device__ int64_t operator()(int64_t k) const { return k < n ? seq_tok_len(buf + start_of(k)) + 1 : 0; }
+};
+struct SeqNameStart {    // new name k: entry name_tok[k] of the intern pass
+    const int64_t* starts; const int64_t* name_tok;
+    __device__ int64_t operator()(int64_t k) const { return starts[name_tok[k]]; }
 };
 
 static __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_row_first(const int64_t* rowx, int64_t P, int64_t T, int64_t* row_first) {
@@ -254,15 +263,23 @@ static __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_name_tok(const int64_t
     if (namex[t + 1] != namex[t]) name_tok[namex[t] - P] = t;
 }
 
-static __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_name_bytes(const uint8_t* buf, const int64_t* tok_start, const int64_t* tok_len, const int64_t* name_tok, const int64_t* name_off,
-                                                              int64_t n, uint8_t* blob) {
+// item k's bytes and a NUL to blob + off[k]; off is the scan of SeqItemLen over the same start_of
+template <typename Start>
+static __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_tok_bytes(const uint8_t* buf, Start start_of, const int64_t* off, int64_t n, uint8_t* blob) {
     const int64_t k = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
     if (k >= n) return;
-    const int64_t t = name_tok[k], len = tok_len[t];
-    const uint8_t* src = buf + tok_start[t];
-    uint8_t* dst = blob + name_off[k];
+    const uint8_t* src = buf + start_of(k);
+    const int64_t len = off[k + 1] - off[k] - 1;
+    uint8_t* dst = blob + off[k];
     for (int64_t i = 0; i < len; i++) dst[i] = src[i];
     dst[len] = 0;
+}
+
+// every row that skip (when given) does not mark must have want tokens: the least row that has not
+[[maybe_unused]] static __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_ragged(const int64_t* row_first, const uint8_t* skip, int64_t rows, int64_t want, unsigned long long* ragged) {
+    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (r >= rows || (skip && skip[r])) return;
+    if (row_first[r + 1] - row_first[r] != want) atomicMin(ragged, (unsigned long long)r);
 }
 
 // one lane: where[0] = newlines in [lo, at), where[1] = bytes between the start of at's line (or lo) and at.  The lane walks inside three chunks at the most,
@@ -290,8 +307,6 @@ static __global__ void __launch_bounds__(SEQ_BLOCK) k_seq_name_bytes(const uint8
 // ------------------------------------------------------------------------------------------ host side of one ingest
 namespace {
 
-struct SeqPiece { const char* path = nullptr; const uint8_t* mem = nullptr; int fd = -1; int64_t size = 0; };
-
 struct SeqRun {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -314,7 +329,7 @@ struct SeqRun {
     int64_t P = 0, T = 0, lines = 0, rows = 0, max_len = 1, n_names = 0, unknown = 0;
     int64_t N = 0;                    // entries interned: T (.seq: every token), or P + the rows (.vec: the token that opens each)
     ~SeqRun() {
-        for (SeqPiece& p : pieces) if (p.fd >= 0) close(p.fd);
+        seq_close_pieces(pieces);
         for (int i = 0; i < 2; i++) { if (pin[i]) (void)hipHostFree(pin[i]); if (copied[i]) (void)hipEventDestroy(copied[i]); }
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -338,6 +353,13 @@ template <typename T>
 void seq_release(SeqRun& R, dge_tmp<T>& t, int64_t n) { if (t.p) { (void)hipFree(t.p); t.p = nullptr; R.held -= (int64_t)((size_t)(n > 0 ? n : 1) * sizeof(T)); } }
 
 #define SEQ_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
+
+// what every run starts with: its device, its name in the messages about memory, its stream
+[[maybe_unused]] int seq_open(SeqRun& R, int device, const char* what) {
+    R.device = device; R.what = what;
+    DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
+    return DGE_OK;
+}
 
 int seq_read_back(SeqRun& R, void* dst, const void* src, size_t bytes) {
     DGE_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, R.stream));
@@ -369,42 +391,6 @@ int seq_scan(SeqRun& R, In in, int64_t* out, int64_t n) {      // out[i] = sum o
     tmp.release();
     return DGE_OK;
 }
-
-// The joined stream — prior names, then every piece with its pad byte — produced front to back into a pinned buffer.
-struct SeqJoiner {
-    SeqRun& R; const std::string& prefix;
-    int64_t in_prefix = 0; size_t k = 0; int64_t at = 0; uint8_t last = '\n';
-    int fill(uint8_t* dst, int64_t cap, int64_t* got) {
-        int64_t n = 0;
-        while (n < cap) {
-            if (in_prefix < (int64_t)prefix.size()) {
-                const int64_t m = std::min<int64_t>(cap - n, (int64_t)prefix.size() - in_prefix);
-                memcpy(dst + n, prefix.data() + in_prefix, (size_t)m);
-                in_prefix += m; n += m;
-                continue;
-            }
-            if (k >= R.pieces.size()) break;
-            SeqPiece& p = R.pieces[k];
-            if (at < p.size) {
-                int64_t m = std::min<int64_t>(cap - n, p.size - at);
-                if (p.mem) memcpy(dst + n, p.mem + at, (size_t)m);
-                else {
-                    const ssize_t r = read(p.fd, dst + n, (size_t)m);
-                    if (r < 0 && errno == EINTR) continue;
-                    if (r <= 0) DGE_FAIL(DGE_ERR_IO, "cannot read %s: %s after %lld of %lld bytes", p.path, r < 0 ? strerror(errno) : "the file ends", (long long)at, (long long)p.size);
-                    m = (int64_t)r;
-                }
-                last = dst[n + m - 1];
-                at += m; n += m;
-                continue;
-            }
-            dst[n++] = seq_pad_byte(p.size, last);
-            k++; at = 0; last = '\n';
-        }
-        *got = n;
-        return DGE_OK;
-    }
-};
 
 // buffer offset -> offset in the caller's text (the pieces taken one after the other, pads and prefix not counted) and the piece it lies in
 int64_t seq_text_offset(const SeqRun& R, int64_t at, size_t* piece) {
@@ -448,7 +434,7 @@ struct SeqOptions { int32_t hash_bits = 64; int64_t initial_slots = 0; int inter
     std::vector<int64_t> sizes;
     for (const SeqPiece& p : R.pieces) sizes.push_back(p.size);
     if (!seq_plan_layout((int64_t)prefix.size(), sizes.data(), (int64_t)sizes.size(), &R.L)) DGE_FAIL(DGE_ERR_ARG, "%s: the text's size leaves 64 bits", who);
-    DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
+    SEQ_TRY(seq_open(R, R.device, R.what));
     // ---- bytes to the device: chunk c + 1 is read (or copied out of the caller's memory) into one pinned buffer while chunk c leaves the other
     const auto t0 = clock::now();
     SEQ_TRY(seq_alloc(R, R.buf, R.L.padded, "the text"));
@@ -459,7 +445,7 @@ struct SeqOptions { int32_t hash_bits = 64; int64_t initial_slots = 0; int inter
             DGE_HIP(hipHostMalloc((void**)&R.pin[i], (size_t)pin_bytes, hipHostMallocDefault));
             DGE_HIP(hipEventCreateWithFlags(&R.copied[i], hipEventDisableTiming));
         }
-        SeqJoiner join{R, prefix};
+        SeqJoiner join{R.pieces, prefix};
         int64_t done = 0;
         for (int64_t c = 0; done < R.L.used; c++) {
             const int b = (int)(c & 1);
@@ -587,24 +573,76 @@ struct SeqOptions { int32_t hash_bits = 64; int64_t initial_slots = 0; int inter
     return DGE_OK;
 }
 
-// the bytes of the n_new names behind the prior ones (entries as in seq_intern), NUL-terminated, in ONE blob for the host: string k at off[k]
+// the indices of the set bytes of flags[0 .. n), ascending, in picked; count: how many are set (the caller has counted them).  what: "the host tokens"
+[[maybe_unused]] int seq_pick(SeqRun& R, const uint8_t* flags, int64_t n, int64_t count, dge_tmp<int64_t>& picked, const char* what) {
+    dge_tmp<int64_t> numx;
+    SEQ_TRY(seq_alloc(R, numx, n + 1, (std::string(what) + "' numbers").c_str()));
+    SEQ_TRY(seq_alloc(R, picked, count, what));
+    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqByteFlag{flags, n}), numx.p, n + 1));
+    hipLaunchKernelGGL(k_seq_name_tok, dim3(seq_grid(n)), dim3(SEQ_BLOCK), 0, R.stream, numx.p, (int64_t)0, n, picked.p);
+    seq_release(R, numx, n + 1);
+    return DGE_OK;
+}
+
+// The n tokens whose first bytes are at start_of(k) (a device functor), NUL-terminated, in ONE blob for the host: string k at off[k].  Called with the kernels'
+// clock running (seq_kernels_begin; the caller's own index kernels stand in front) and stops it before the blob comes back.  what: "the new names"
+template <typename Start>
+int seq_tokens_to_host(SeqRun& R, Start start_of, int64_t n, std::vector<int64_t>& off, std::unique_ptr<char[]>& host_blob, const char* what) {
+    dge_tmp<int64_t> d_off;
+    dge_tmp<uint8_t> blob;
+    off.assign((size_t)n + 1, 0);
+    SEQ_TRY(seq_alloc(R, d_off, n + 1, (std::string(what) + "' offsets").c_str()));
+    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqItemLen<Start>{R.buf.p, start_of, n}), d_off.p, n + 1));
+    SEQ_TRY(seq_read_back(R, off.data(), d_off.p, (size_t)(n + 1) * 8));
+    SEQ_TRY(seq_alloc(R, blob, off[(size_t)n], (std::string(what) + "' bytes").c_str()));
+    hipLaunchKernelGGL(k_seq_tok_bytes<Start>, dim3(seq_grid(n)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, start_of, d_off.p, n, blob.p);
+    SEQ_TRY(seq_kernels_end(R));
+    host_blob.reset(new char[(size_t)off[(size_t)n]]);
+    return seq_read_back(R, host_blob.get(), blob.p, (size_t)off[(size_t)n]);
+}
+
+// the bytes of the n_new names behind the prior ones (entries as in seq_intern).  A name's length comes from seq_tok_len here, not from the stored tok_len[]:
+// the same number by construction, k_seq_hash runs the same seq_run loop over the same bytes.
 [[maybe_unused]] int seq_new_names(SeqRun& R, const int64_t* starts, int64_t n_new, std::vector<int64_t>& off, std::unique_ptr<char[]>& host_blob) {
-    const int64_t T = R.N, P = R.P;
     off.assign((size_t)std::max<int64_t>(n_new, 0) + 1, 0);
     if (n_new <= 0) return DGE_OK;
-    dge_tmp<int64_t> name_tok, name_off;
-    dge_tmp<uint8_t> blob;
+    dge_tmp<int64_t> name_tok;
     SEQ_TRY(seq_alloc(R, name_tok, n_new, "the new names' tokens"));
-    SEQ_TRY(seq_alloc(R, name_off, n_new + 1, "the new names' offsets"));
     SEQ_TRY(seq_kernels_begin(R));
-    hipLaunchKernelGGL(k_seq_name_tok, dim3(seq_grid(T - P)), dim3(SEQ_BLOCK), 0, R.stream, R.namex.p, P, T, name_tok.p);
-    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqNameLen{name_tok.p, R.tok_len.p, n_new}), name_off.p, n_new + 1));
-    SEQ_TRY(seq_read_back(R, off.data(), name_off.p, (size_t)(n_new + 1) * 8));
-    SEQ_TRY(seq_alloc(R, blob, off[(size_t)n_new], "the new names' bytes"));
-    hipLaunchKernelGGL(k_seq_name_bytes, dim3(seq_grid(n_new)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, starts, R.tok_len.p, name_tok.p, name_off.p, n_new, blob.p);
-    SEQ_TRY(seq_kernels_end(R));
-    host_blob.reset(new char[(size_t)off[(size_t)n_new]]);
-    return seq_read_back(R, host_blob.get(), blob.p, (size_t)off[(size_t)n_new]);
+    hipLaunchKernelGGL(k_seq_name_tok, dim3(seq_grid(R.N - R.P)), dim3(SEQ_BLOCK), 0, R.stream, R.namex.p, R.P, R.N, name_tok.p);
+    return seq_tokens_to_host(R, SeqNameStart{starts, name_tok.p}, n_new, off, host_blob, "the new names");
+}
+
+// the "C" locale for the numbers the host finishes, whatever the process has set
+struct SeqCLocale {
+    locale_t c = (locale_t)0;
+    ~SeqCLocale() { if (c) freelocale(c); }
+    int open(const char* who) {
+        c = newlocale(LC_ALL_MASK, "C", (locale_t)0);
+        if (!c) DGE_FAIL(DGE_ERR_STATE, "%s: the \"C\" locale is not available", who);
+        return DGE_OK;
+    }
+};
+
+// the n strings of seq_tokens_to_host as numbers: the bits of strtod (T = uint64_t) or of strtof (T = uint32_t)
+template <typename T>
+int seq_host_numbers(const char* text, const int64_t* off, int64_t n, std::vector<T>& bits, const char* who) {
+    SeqCLocale loc;
+    SEQ_TRY(loc.open(who));
+    bits.resize((size_t)n);
+    for (int64_t k = 0; k < n; k++) {
+        if constexpr (sizeof(T) == 8) { const double d = strtod_l(text + off[k], nullptr, loc.c); memcpy(&bits[(size_t)k], &d, 8); }
+        else { const float f = strtof_l(text + off[k], nullptr, loc.c); memcpy(&bits[(size_t)k], &f, 4); }
+    }
+    return DGE_OK;
+}
+
+// row r for a message: the buffer offset of its first token and how many tokens it has
+[[maybe_unused]] int seq_row_where(SeqRun& R, int64_t r, int64_t* at, int64_t* count) {
+    int64_t f[2];
+    SEQ_TRY(seq_read_back(R, f, R.row_first.p + r, 16));
+    *count = f[1] - f[0];
+    return seq_read_back(R, at, R.tok_start.p + f[0], 8);
 }
 
 }  // namespace

@@ -116,12 +116,6 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_sp_topk(const double* __restrict_
 // ------------------------------------------------------------------------------------------ host side
 namespace {
 
-int sp_open(SeqRun& R, int device, const char* what) {
-    R.device = device; R.what = what;
-    DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-    return DGE_OK;
-}
-
 // the centroids of rg, on the device and on the host, computed once (under the handle's mutex: a handle may be shared by threads)
 int sp_centroids(const dge_regions* rg, const char* who) {
     std::lock_guard<std::mutex> once(rg->cent_mutex);
@@ -130,7 +124,7 @@ int sp_centroids(const dge_regions* rg, const char* who) {
     if (R == 0) { rg->cent_done = true; return DGE_OK; }
     SEQ_TRY(dge_require_device(rg->device));
     SeqRun Rn;
-    SEQ_TRY(sp_open(Rn, rg->device, who));
+    SEQ_TRY(seq_open(Rn, rg->device, who));
     dge_tmp<double> cent;
     dge_tmp<uint8_t> ok;
     SEQ_TRY(seq_alloc(Rn, cent, 2 * R, "the centroids"));
@@ -170,7 +164,7 @@ int sp_build(dge_graph* g, const double* d_cent, const int64_t* ids, int64_t R, 
     if (R == 0) return dge_graph_set_sources(g, nullptr, 0, 1);            // an empty graph, as the three calls leave it
     DGE_HIP(hipSetDevice(g->device));
     SeqRun Rn;
-    SEQ_TRY(sp_open(Rn, g->device, who));
+    SEQ_TRY(seq_open(Rn, g->device, who));
     const int64_t E = R * (int64_t)k;
     dge_tmp<int64_t> row_ptr;
     dge_tmp<int32_t> nbr;

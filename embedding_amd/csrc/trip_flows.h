@@ -46,12 +46,6 @@ static __global__ void __launch_bounds__(SEQ_BLOCK) k_slot_decode(const uint64_t
 
 namespace {
 
-int trip_open(SeqRun& R, int device, const char* what) {
-    R.device = device; R.what = what;
-    DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
-    return DGE_OK;
-}
-
 // keys ascending with duplicates, vals: -> distinct keys with summed values.  vals == nullptr: every value is 1.  The outputs are allocated here.
 int trip_reduce(SeqRun& R, const uint64_t* keys, const int64_t* vals, int64_t n, dge_tmp<uint64_t>& ukey, dge_tmp<int64_t>& usum, int64_t* n_out) {
     *n_out = 0;

@@ -261,7 +261,7 @@ int regions_locate(const dge_regions* rg, const double* xy, int64_t n, int32_t* 
     if (!rg || n < 0 || (n > 0 && (!xy || !region))) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     SEQ_TRY(dge_require_device(rg->device));
     SeqRun R;
-    SEQ_TRY(trip_open(R, rg->device, who));
+    SEQ_TRY(seq_open(R, rg->device, who));
     dge_tmp<unsigned long long> counters;
     dge_tmp<double> d_xy;
     dge_tmp<int32_t> d_region;
@@ -292,7 +292,7 @@ int flows_add(dge_flows* f, const double* sxy, const double* exy, const int32_t*
     SEQ_TRY(dge_require_device(rg->device));
     if (n == 0) return DGE_OK;
     SeqRun R;
-    SEQ_TRY(trip_open(R, rg->device, who));
+    SEQ_TRY(seq_open(R, rg->device, who));
     const int64_t cap = std::min(n, TRIP_CHUNK);
     const uint64_t Ru = (uint64_t)std::max<int64_t>(rg->R, 1);
     const int key_bits = 64;                     // (the unmapped trips' key is all ones)
@@ -453,7 +453,7 @@ extern "C" int dge_regions_create(int device, const int64_t* ids, int64_t R, con
 
     SEQ_TRY(dge_require_device(device));
     SeqRun Rn;
-    SEQ_TRY(trip_open(Rn, device, who));
+    SEQ_TRY(seq_open(Rn, device, who));
     SEQ_TRY(trip_upload(Rn, &rg->d_seg, seg.data(), (int64_t)seg.size(), "the segments"));
     SEQ_TRY(trip_upload(Rn, &rg->d_seg_first, seg_first.data(), R + 1, "the regions' segments"));
     SEQ_TRY(trip_upload(Rn, &rg->d_box, box.data(), R * 4, "the regions' boxes"));
@@ -511,7 +511,7 @@ int dge_flows_merge(dge_flows* f, const dge_flows* part) {
     SeqRun R;
     if (part->n > 0) {
         SEQ_TRY(dge_require_device(f->regions->device));
-        SEQ_TRY(trip_open(R, f->regions->device, who));
+        SEQ_TRY(seq_open(R, f->regions->device, who));
         dge_tmp<uint64_t> nkey;
         dge_tmp<int64_t> ncnt;
         int64_t nn = 0;
@@ -557,7 +557,7 @@ extern "C" int dge_flows_slot_edges(const dge_flows* f, int32_t T, int32_t mode,
     if (f->n == 0) return DGE_OK;
     SEQ_TRY(dge_require_device(f->regions->device));
     SeqRun R;
-    SEQ_TRY(trip_open(R, f->regions->device, who));
+    SEQ_TRY(seq_open(R, f->regions->device, who));
     dge_tmp<uint64_t> okey;
     dge_tmp<int64_t> ow;
     int64_t E = 0;
@@ -586,7 +586,7 @@ int dge_flows_slot_coo(const dge_flows* f, int32_t T, int32_t mode, int32_t slot
     if (f->n == 0) DGE_FAIL(DGE_ERR_ARG, "%s: slot %d holds no entry: the table is empty", who, slot);
     SEQ_TRY(dge_require_device(rg->device));
     SeqRun R;
-    SEQ_TRY(trip_open(R, rg->device, who));
+    SEQ_TRY(seq_open(R, rg->device, who));
     // rank of a region's id -> its number among the selected regions
     std::vector<int32_t> idrank((size_t)Rn), map((size_t)Rn, -1);
     SEQ_TRY(seq_read_back(R, idrank.data(), rg->d_idrank, (size_t)Rn * 4));
@@ -631,7 +631,7 @@ extern "C" int dge_graph_add_flows(dge_graph* g, const dge_flows* f, int32_t T, 
     SEQ_TRY(od_check(g, names, who));
     SEQ_TRY(dge_require_device(g->device));
     SeqRun R;
-    SEQ_TRY(trip_open(R, g->device, who));
+    SEQ_TRY(seq_open(R, g->device, who));
     dge_tmp<uint64_t> okey;
     dge_tmp<int64_t> ow;
     int64_t E = 0, Rn = 0, S = 0;

@@ -6,8 +6,8 @@
 // written by a training launch.
 //
 // Transport (this reader's own; seq_tokens.h's loads a whole text, and the trip files are the one text of the pipeline that must not be resident).  The host
-// cuts each piece into SLABS of whole lines: it fills a pinned buffer with the tail the last slab left and fresh bytes up to slab_bytes, looks backwards for the
-// last terminator, sends everything up to it and keeps the rest as the next tail.  That search touches the end of the buffer only; no per-line work is done on
+// (TripFeeder of seq_pieces.h, plain C++ that tests/test_seq_pieces_host.py runs without a device) cuts each piece into SLABS of whole lines: it fills a
+// pinned buffer with the tail the last slab left and fresh bytes up to slab_bytes, looks backwards for the last terminator, sends everything up to it and keeps the rest as the next tail.  That search touches the end of the buffer only; no per-line work is done on
 // the host.  What the cut guarantees the kernels:
 //   - a slab holds whole lines of ONE piece; only a piece's last slab may end without a terminator;
 //   - a "\r" that ends a slab is a whole terminator: when the piece goes on with "\n" that byte is dropped on the way in (it is half of the "\r\n" already
@@ -21,16 +21,13 @@
 //                                counts, a rocPRIM scan and the second pass give line l the offset of its terminator; line l starts behind terminator l-1.
 //   k_trip_parse                 a workgroup takes 256 consecutive lines, copies their contiguous bytes into LDS with 16-byte loads (a tile of TRIP_TILE bytes;
 //                                a range that does not fit is read from global memory by the same code) and every lane parses its own line out of it.
-//   host path                    lines with a coordinate od_parse_f64 hands back come back by index; the host parses them again out of the pinned slab with the
+//   host path                    lines with a coordinate od_parse_f64 hands back come back by index (seq_pick, k_trip_host_list); the host parses them again out of the pinned slab with the
 //                                same trip_parse.h, finishes the coordinates with strtod, and k_trip_patch writes the records in place — before anything reads them.
 //   k_trip_compact around a scan the status-0 records in text order, for dge_flows_add_trips_device.
 // Offsets inside a slab are 32-bit; line numbers and byte totals are 64-bit.  Counters are integers added with atomicAdd after a block reduction.
 // Coherence: no protocol.  Every array is written by one kernel and read by later ones on the same stream.
 //
 // The shape (slab transport, LDS tile, one lane per line) is the one the design proposed; none of it has been measured against an alternative.
-#include <locale.h>
-#include <stdlib.h>
-
 #include <algorithm>
 
 #include "seq_tokens.h"
@@ -122,14 +119,14 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_trip_parse(const uint8_t* buf, in
     }
 }
 
-struct TripHostFlag { const uint8_t* mask; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n && mask[i] ? 1 : 0; } };
 struct TripOkFlag { const uint8_t* status; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n && status[i] == 0 ? 1 : 0; } };
 
-__global__ void __launch_bounds__(SEQ_BLOCK) k_trip_host_list(const int64_t* hostx, const int32_t* line_at, const int32_t* line_len, int64_t n, int64_t* list) {
-    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (i >= n || hostx[i + 1] == hostx[i]) return;
-    int64_t* out = list + 3 * hostx[i];
-    out[0] = i; out[1] = line_at[i]; out[2] = line_len[i];
+// host line k = record picked[k]: (record, offset, length)
+__global__ void __launch_bounds__(SEQ_BLOCK) k_trip_host_list(const int64_t* picked, const int32_t* line_at, const int32_t* line_len, int64_t n, int64_t* list) {
+    const int64_t k = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    if (k >= n) return;
+    const int64_t i = picked[k];
+    list[3 * k] = i; list[3 * k + 1] = line_at[i]; list[3 * k + 2] = line_len[i];
 }
 
 __global__ void __launch_bounds__(SEQ_BLOCK) k_trip_patch(const int64_t* list, const int32_t* p_status_hour, const uint64_t* p_xy, int64_t n, uint8_t* status, int32_t* hour,
@@ -156,107 +153,6 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_trip_compact(const int64_t* okx, 
 // ------------------------------------------------------------------------------------------ host side
 namespace {
 
-int64_t trip_last_terminator(const uint8_t* b, int64_t n) {
-    const uint8_t* nl = n ? static_cast<const uint8_t*>(memrchr(b, '\n', (size_t)n)) : nullptr;
-    const int64_t a = nl ? nl - b : -1;
-    const uint8_t* cr = n - a - 1 > 0 ? static_cast<const uint8_t*>(memrchr(b + a + 1, '\r', (size_t)(n - a - 1))) : nullptr;
-    return cr ? cr - b : a;
-}
-
-// the pieces' bytes, cut into slabs of whole lines (the head of this file states what a slab is)
-struct TripFeeder {
-    std::vector<SeqPiece>& pieces;
-    int64_t S;
-    size_t k = 0;
-    int64_t at = 0;                   // bytes of piece k taken
-    bool opens = true;                // the next slab is the first of piece k
-    bool pending_cr = false;          // the last byte sent was a "\r" that ended a buffer: a "\n" that follows is its other half
-    std::vector<uint8_t> tail, skip;
-    int64_t n_tail = 0;
-
-    int read_some(uint8_t* dst, int64_t cap, int64_t* got) {
-        SeqPiece& p = pieces[k];
-        *got = 0;
-        while (*got == 0 && at < p.size && cap > 0) {
-            int64_t m = std::min<int64_t>(cap, p.size - at);
-            if (p.mem) memcpy(dst, p.mem + at, (size_t)m);
-            else {
-                const ssize_t r = read(p.fd, dst, (size_t)m);
-                if (r < 0 && errno == EINTR) continue;
-                if (r <= 0) DGE_FAIL(DGE_ERR_IO, "cannot read %s: %s after %lld of %lld bytes", p.path, r < 0 ? strerror(errno) : "the file ends", (long long)at, (long long)p.size);
-                m = (int64_t)r;
-            }
-            at += m;
-            if (pending_cr) {
-                pending_cr = false;
-                if (dst[0] == '\n') { m--; memmove(dst, dst + 1, (size_t)m); }
-            }
-            *got = m;
-        }
-        return DGE_OK;
-    }
-
-    // an over-long line's rest: bytes up to and with the next terminator are dropped, what follows it becomes the tail
-    int skip_line() {
-        if (skip.empty()) skip.resize((size_t)std::min<int64_t>(S, (int64_t)1 << 20));          // what follows the terminator becomes the tail: no more than a tail's room
-        for (;;) {
-            int64_t got = 0;
-            SEQ_TRY(read_some(skip.data(), (int64_t)skip.size(), &got));
-            if (got == 0) return DGE_OK;
-            int64_t p = 0;
-            while (p < got && skip[(size_t)p] != '\n' && skip[(size_t)p] != '\r') p++;
-            if (p == got) continue;
-            if (skip[(size_t)p] == '\r') {
-                if (p + 1 < got) { if (skip[(size_t)p + 1] == '\n') p++; }
-                else pending_cr = true;
-            }
-            n_tail = got - p - 1;
-            memcpy(tail.data(), skip.data() + p + 1, (size_t)n_tail);
-            return DGE_OK;
-        }
-    }
-
-    // the next slab into buf (S bytes): *n = 0 when the text is through.  *first: the slab opens its piece.  *open_end: its last line has no terminator.
-    int next(uint8_t* buf, int64_t* n_out, bool* first, bool* open_end) {
-        *n_out = 0;
-        if (tail.empty()) tail.resize((size_t)S);
-        while (k < pieces.size()) {
-            int64_t n = n_tail;
-            if (n) memcpy(buf, tail.data(), (size_t)n);
-            n_tail = 0;
-            for (;;) {
-                int64_t got = 0;
-                SEQ_TRY(read_some(buf + n, S - n, &got));
-                if (got == 0) break;
-                n += got;
-            }
-            const bool at_end = at >= pieces[k].size;
-            int64_t send = n;
-            if (!at_end) {                                   // the buffer is full and the piece goes on
-                const int64_t t = trip_last_terminator(buf, n);
-                if (t < 0) {
-                    send = TRIP_MAX_LINE + 2;
-                    buf[TRIP_MAX_LINE + 1] = '\n';
-                    SEQ_TRY(skip_line());
-                } else {
-                    send = t + 1;
-                    n_tail = n - send;
-                    memcpy(tail.data(), buf + send, (size_t)n_tail);
-                    if (n_tail == 0 && buf[t] == '\r') pending_cr = true;
-                }
-            }
-            const bool was_first = opens;
-            opens = false;
-            if (at >= pieces[k].size && n_tail == 0) { k++; at = 0; opens = true; pending_cr = false; }
-            if (send == 0) continue;                         // an empty piece, or one whose rest was the "\n" of a "\r\n"
-            *n_out = send; *first = was_first;
-            *open_end = buf[send - 1] != '\n' && buf[send - 1] != '\r';
-            return DGE_OK;
-        }
-        return DGE_OK;
-    }
-};
-
 struct TripSink {                     // where the records go: the caller's arrays (dge_trips_parse_texts) or a flow table
     uint8_t* status = nullptr; int32_t* hour = nullptr; double* sxy = nullptr; double* exy = nullptr;
     int64_t cap = 0;
@@ -276,19 +172,16 @@ struct TripReader {
     dge_tmp<double> sxy, exy;
     dge_tmp<unsigned long long> counters;
     hipEvent_t ea = nullptr, eb = nullptr;
-    locale_t c_locale = (locale_t)0;
+    SeqCLocale locale;
     dge_trip_text_info info = {};
     ~TripReader() {
         if (ea) (void)hipEventDestroy(ea);
         if (eb) (void)hipEventDestroy(eb);
-        if (c_locale) freelocale(c_locale);
     }
 
     int open(const char* who) {
-        R.what = who;
-        c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
-        if (!c_locale) DGE_FAIL(DGE_ERR_STATE, "%s: the \"C\" locale is not available", who);
-        DGE_HIP(hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking));
+        SEQ_TRY(locale.open(who));
+        SEQ_TRY(seq_open(R, R.device, who));
         DGE_HIP(hipEventCreate(&ea));
         DGE_HIP(hipEventCreate(&eb));
         int64_t total = 0, largest = 0;
@@ -365,16 +258,15 @@ struct TripReader {
         info.ok += (int64_t)c[TT_OK]; info.bad_fields += (int64_t)c[TT_BAD_FIELDS]; info.bad_parse += (int64_t)c[TT_BAD_PARSE]; info.too_long += (int64_t)c[TT_TOO_LONG];
         const int64_t n_host = (int64_t)c[TT_HOST_LINES];
         if (n_host > 0) {
-            dge_tmp<int64_t> hostx, list;
+            dge_tmp<int64_t> picked, list;
             dge_tmp<int32_t> p_sh;
             dge_tmp<uint64_t> p_xy;
-            SEQ_TRY(seq_alloc(R, hostx, m + 1, "the host lines' numbers"));
             SEQ_TRY(seq_alloc(R, list, 3 * n_host, "the host lines"));
             SEQ_TRY(seq_alloc(R, p_sh, 2 * n_host, "the host lines' records"));
             SEQ_TRY(seq_alloc(R, p_xy, 4 * n_host, "the host lines' points"));
             SEQ_TRY(seq_kernels_begin(R));
-            SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), TripHostFlag{host_mask.p, m}), hostx.p, m + 1));
-            hipLaunchKernelGGL(k_trip_host_list, dim3(seq_grid(m)), dim3(SEQ_BLOCK), 0, R.stream, hostx.p, line_at.p, line_len.p, m, list.p);
+            SEQ_TRY(seq_pick(R, host_mask.p, m, n_host, picked, "the host lines"));
+            hipLaunchKernelGGL(k_trip_host_list, dim3(seq_grid(n_host)), dim3(SEQ_BLOCK), 0, R.stream, picked.p, line_at.p, line_len.p, n_host, list.p);
             SEQ_TRY(seq_kernels_end(R));
             std::vector<int64_t> l((size_t)n_host * 3);
             std::vector<int32_t> sh((size_t)n_host * 2);
@@ -384,7 +276,7 @@ struct TripReader {
                 const uint8_t* line = R.pin[s.b] + l[(size_t)k * 3 + 1];
                 trip_rec r;
                 trip_parse_line(line, l[(size_t)k * 3 + 2], format, &r);
-                info.host_values += trip_finish_host(line, &r, c_locale);
+                info.host_values += trip_finish_host(line, &r, locale.c);
                 sh[(size_t)k * 2] = r.status; sh[(size_t)k * 2 + 1] = r.hour;
                 memcpy(&xy[(size_t)k * 4], r.xy, 32);
                 if (r.status == TRIP_OK) info.ok++; else info.bad_parse++;
@@ -454,22 +346,13 @@ int trip_check_options(const struct dge_trip_text_options* opt, const char* who)
 
 int trip_check_texts(const char* const* texts, const int64_t* n_bytes, int32_t n, const char* who) {
     if (n < 0 || (n > 0 && (!texts || !n_bytes))) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
-    for (int32_t k = 0; k < n; k++)
-        if (n_bytes[k] < 0 || (n_bytes[k] > 0 && !texts[k])) DGE_FAIL(DGE_ERR_ARG, "%s: text %d is null or of negative size", who, k);
-    return DGE_OK;
+    return seq_check_texts(texts, n_bytes, n, who);
 }
 
 void trip_configure(TripReader& T, int device, const struct dge_trip_text_options* opt) {
     T.R.device = device;
     T.format = opt->format; T.header = opt->header != 0;
     T.S = opt->slab_bytes == 0 ? TRIP_SLAB_DEFAULT : std::min(opt->slab_bytes, TRIP_SLAB_MAX);
-}
-
-void trip_add_texts(TripReader& T, const char* const* texts, const int64_t* n_bytes, int32_t n) {
-    for (int32_t k = 0; k < n; k++) {
-        SeqPiece p; p.mem = reinterpret_cast<const uint8_t*>(texts[k]); p.size = n_bytes[k];
-        T.R.pieces.push_back(p);
-    }
 }
 
 // the text's trips into a table of their own, that table into f: on any error f is as it was
@@ -498,7 +381,7 @@ extern "C" int dge_trips_parse_texts(int device, const char* const* texts, const
     SEQ_TRY(dge_require_device(device));
     TripReader T;
     trip_configure(T, device, opt);
-    trip_add_texts(T, texts, n_bytes, n);
+    SEQ_TRY(seq_add_texts(T.R.pieces, texts, n_bytes, n, who));
     SEQ_TRY(T.open(who));
     TripSink sink;
     sink.status = status; sink.hour = hour; sink.sxy = start_xy; sink.exy = end_xy; sink.cap = cap;
@@ -517,26 +400,18 @@ extern "C" int dge_flows_add_trip_texts(dge_flows* f, const char* const* texts, 
     SEQ_TRY(dge_require_device(dge_flows_device(f)));
     TripReader T;
     trip_configure(T, dge_flows_device(f), opt);
-    trip_add_texts(T, texts, n_bytes, n);
+    SEQ_TRY(seq_add_texts(T.R.pieces, texts, n_bytes, n, who));
     return trip_into_flows(T, f, info, who);
 }
 
 extern "C" int dge_flows_add_trip_files(dge_flows* f, const char* const* paths, int32_t n, const struct dge_trip_text_options* opt, dge_trip_text_info* info) {
     const char* who = "dge_flows_add_trip_files";
     if (!f || n < 0 || (n > 0 && !paths)) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
-    for (int32_t k = 0; k < n; k++) if (!paths[k]) DGE_FAIL(DGE_ERR_ARG, "%s: path %d is null", who, k);
+    SEQ_TRY(seq_check_paths(paths, n, who));
     SEQ_TRY(trip_check_options(opt, who));
     SEQ_TRY(dge_require_device(dge_flows_device(f)));
     TripReader T;
     trip_configure(T, dge_flows_device(f), opt);
-    for (int32_t k = 0; k < n; k++) {              // every file is opened before anything runs
-        SeqPiece p; p.path = paths[k];
-        p.fd = open(paths[k], O_RDONLY | O_CLOEXEC);
-        if (p.fd < 0) DGE_FAIL(DGE_ERR_IO, "cannot open %s: %s", paths[k], strerror(errno));
-        T.R.pieces.push_back(p);                   // (the run closes it)
-        struct stat st;
-        if (fstat(p.fd, &st) != 0 || !S_ISREG(st.st_mode)) DGE_FAIL(DGE_ERR_IO, "cannot read %s: not a regular file", paths[k]);
-        T.R.pieces.back().size = (int64_t)st.st_size;
-    }
+    SEQ_TRY(seq_add_files(T.R.pieces, paths, n, who));
     return trip_into_flows(T, f, info, who);
 }

@@ -6,13 +6,14 @@
 // The passes, on the one buffer of seq_tokens.h (prior names as its leading lines, then every piece with its pad byte):
 //   seq_tokenise               token t's first byte and line, the rows (rowx, row_first) — the .seq reader's kernels and chunk transport, unchanged
 //   k_vec_mark                 per row: its piece; with header != 0 the first row of a piece is its "V D" line, checked and read here
-//   k_vec_ragged               every other row must have dim + 1 tokens (dim: the first such row's)
+//   k_seq_ragged               every other row must have dim + 1 tokens (dim: the first such row's); the header lines are its skip mask
 //   k_vec_entries + seq_intern only the token that OPENS a row is a name: the prior names and those tokens — 1 token in dim + 1 — are the entries the
 //                              .seq reader's k_seq_hash / k_seq_intern / ids passes run on.  Entry order is text order, so ids are first-appearance ids.
 //   k_vec_parse                a lane per value token: vec_parse.h's integer routine -> out[id(row) * dim + column]; "not mine" tokens are flagged
 //   k_vec_first_row / _dups    a row is a duplicate when its name opened an earlier ROW: when the string's first appearance is an earlier row, or, for a
 //                              name the caller already held (first appearance among the prior names), when it is not the least row with that name
-//   host path                  the flagged tokens' bytes in one blob (as the new names'), strtof in the "C" locale, k_vec_scatter puts the bits in place
+//   host path                  seq_pick / seq_tokens_to_host / seq_host_numbers (seq_tokens.h): the flagged tokens' bytes in one blob, as the new names',
+//                              strtof in the "C" locale; k_vec_scatter puts the bits in place
 // Every error is the LEAST position of its kind, found with atomicMin on a row, an entry or a byte offset: which lane gets there first does not matter.
 // Absent rows are the zero fill of the result; present[] is written by the lane of the row's name.
 //
@@ -21,9 +22,6 @@
 // kernels.  No second protocol: every other array here is written by one kernel and read by later ones on the same stream; out[] and present[] are
 // written at most once per element unless a name opens two rows (a new name or a prior one), in which case k_vec_dups finds the second row, the call
 // fails and the result is discarded.
-#include <locale.h>
-#include <stdlib.h>
-
 #include "seq_tokens.h"
 #include "vec_parse.h"
 
@@ -55,14 +53,6 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_vec_mark(const uint8_t* buf, cons
     if (row_first[r + 1] - t == 2) { v = vec_uint(buf + tok_start[t]); d = vec_uint(buf + tok_start[t + 1]); }
     hdr_v[k] = v; hdr_d[k] = d;
     if (v < 0 || d < 0) atomicMin(bad_hdr, (unsigned long long)r);
-}
-
-struct VecHdrFlag { const uint8_t* is_hdr; int64_t rows; __device__ int64_t operator()(int64_t r) const { return r < rows ? is_hdr[r] : 0; } };
-
-__global__ void __launch_bounds__(SEQ_BLOCK) k_vec_ragged(const int64_t* row_first, const uint8_t* is_hdr, int64_t rows, int64_t want, unsigned long long* ragged) {
-    const int64_t r = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (r >= rows || is_hdr[r]) return;
-    if (row_first[r + 1] - row_first[r] != want) atomicMin(ragged, (unsigned long long)r);
 }
 
 // entry e: the prior names, then the token that opens each row that is no header line, in text order
@@ -126,22 +116,10 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_vec_dups(const unsigned long long
     if (first != (unsigned long long)e) atomicMin(dup, (unsigned long long)e);
 }
 
-struct VecHostFlag { const uint8_t* status; int64_t n; __device__ int64_t operator()(int64_t i) const { return i < n ? status[i] : 0; } };
-struct VecHostLen {      // bytes of host token k in the blob, its NUL included
-    const uint8_t* buf; const int64_t* tok_start; const int64_t* host_tok; int64_t P, n;
-    __device__ int64_t operator()(int64_t k) const { return k < n ? seq_tok_len(buf + tok_start[P + host_tok[k]]) + 1 : 0; }
+struct VecHostStart {    // host token k: value token host_tok[k], counted from the first token behind the prior names
+    const int64_t* tok_start; const int64_t* host_tok; int64_t P;
+    __device__ int64_t operator()(int64_t k) const { return tok_start[P + host_tok[k]]; }
 };
-
-__global__ void __launch_bounds__(SEQ_BLOCK) k_vec_host_bytes(const uint8_t* buf, const int64_t* tok_start, const int64_t* host_tok, const int64_t* host_off, int64_t P, int64_t n,
-                                                              uint8_t* blob) {
-    const int64_t k = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    if (k >= n) return;
-    const uint8_t* src = buf + tok_start[P + host_tok[k]];
-    const int64_t len = host_off[k + 1] - host_off[k] - 1;
-    uint8_t* dst = blob + host_off[k];
-    for (int64_t i = 0; i < len; i++) dst[i] = src[i];
-    dst[len] = 0;
-}
 
 __global__ void __launch_bounds__(SEQ_BLOCK) k_vec_scatter(const int64_t* host_tok, const uint32_t* host_bits, int64_t n, const int64_t* rowx, const int64_t* row_first,
                                                            const int64_t* hdrx, const int32_t* ent_id, int64_t P, int64_t dim, uint32_t* out) {
@@ -178,7 +156,7 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
     DGE_HIP(hipMemsetAsync(piece_first.p, 0xFF, (size_t)std::max<int64_t>(n_pieces, 1) * 8, R.stream));
     if (rows) hipLaunchKernelGGL(k_vec_mark, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.tok_start.p, R.row_first.p, rows, piece_off.p, n_pieces, header ? 1 : 0,
                                  is_hdr.p, piece_first.p, hdr_v.p, hdr_d.p, words.p, words.p + 1);
-    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), VecHdrFlag{is_hdr.p, rows}), hdrx.p, rows + 1));
+    SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqByteFlag{is_hdr.p, rows}), hdrx.p, rows + 1));
     SEQ_TRY(seq_kernels_end(R));
     SEQ_TRY(seq_read_back(R, w, words.p, sizeof(w)));
     int64_t n_hdr = 0;
@@ -189,15 +167,9 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
         SEQ_TRY(seq_read_back(R, hv.data(), hdr_v.p, (size_t)n_pieces * 8));
         SEQ_TRY(seq_read_back(R, hd.data(), hdr_d.p, (size_t)n_pieces * 8));
     }
-    auto row_offset = [&](int64_t r, int64_t* at, int64_t* count) -> int {
-        int64_t f[2];
-        SEQ_TRY(seq_read_back(R, f, R.row_first.p + r, 16));
-        *count = f[1] - f[0];
-        return vec_token_offset(R, f[0], at);
-    };
     if (w[0] != ~0ull) {
         int64_t at = 0, count = 0;
-        SEQ_TRY(row_offset((int64_t)w[0], &at, &count));
+        SEQ_TRY(seq_row_where(R, (int64_t)w[0], &at, &count));
         DGE_FAIL(DGE_ERR_IO, "%s: the header line at %s is not two unsigned decimal integers \"V D\" (it has %lld tokens)", who, seq_where(R, at).c_str(), (long long)count);
     }
     // ---- dim: the first row's token count less the name
@@ -205,16 +177,16 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
     int64_t dim = 0;
     if (n_data > 0) {
         int64_t at = 0, count = 0;
-        SEQ_TRY(row_offset((int64_t)w[1], &at, &count));
+        SEQ_TRY(seq_row_where(R, (int64_t)w[1], &at, &count));
         dim = count - 1;
         if (dim < 1) DGE_FAIL(DGE_ERR_IO, "%s: the row at %s has 1 token where at least 2 are expected: a name and its values", who, seq_where(R, at).c_str());
         if (dim > 0x7fffffffLL) DGE_FAIL(DGE_ERR_RANGE, "%s: %lld values a row do not fit an int32 dim", who, (long long)dim);
         SEQ_TRY(seq_kernels_begin(R));
-        hipLaunchKernelGGL(k_vec_ragged, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, R.row_first.p, is_hdr.p, rows, dim + 1, words.p + 2);
+        hipLaunchKernelGGL(k_seq_ragged, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, R.row_first.p, is_hdr.p, rows, dim + 1, words.p + 2);
         SEQ_TRY(seq_kernels_end(R));
         SEQ_TRY(seq_read_back(R, w + 2, words.p + 2, 8));
         if (w[2] != ~0ull) {
-            SEQ_TRY(row_offset((int64_t)w[2], &at, &count));
+            SEQ_TRY(seq_row_where(R, (int64_t)w[2], &at, &count));
             DGE_FAIL(DGE_ERR_IO, "%s: the row at %s has %lld tokens where %lld are expected (a name and %lld values, as on the first row)", who, seq_where(R, at).c_str(),
                      (long long)count, (long long)(dim + 1), (long long)dim);
         }
@@ -276,29 +248,16 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
     // ---- the host path: the flagged tokens' bytes in one blob, strtof, the bits back into place
     const int64_t n_host = (int64_t)w[5];
     if (n_host > 0) {
-        dge_tmp<int64_t> hostx, host_tok, host_off;
-        dge_tmp<uint8_t> blob;
+        dge_tmp<int64_t> host_tok;
         dge_tmp<uint32_t> host_bits;
-        SEQ_TRY(seq_alloc(R, hostx, T - P + 1, "the host tokens' numbers"));
-        SEQ_TRY(seq_alloc(R, host_tok, n_host, "the host tokens"));
-        SEQ_TRY(seq_alloc(R, host_off, n_host + 1, "the host tokens' offsets"));
+        std::vector<int64_t> off;
+        std::unique_ptr<char[]> text;
+        std::vector<uint32_t> bits;
         SEQ_TRY(seq_alloc(R, host_bits, n_host, "the host tokens' values"));
         SEQ_TRY(seq_kernels_begin(R));
-        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), VecHostFlag{status.p, T - P}), hostx.p, T - P + 1));
-        hipLaunchKernelGGL(k_seq_name_tok, dim3(seq_grid(T - P)), dim3(SEQ_BLOCK), 0, R.stream, hostx.p, (int64_t)0, T - P, host_tok.p);
-        SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), VecHostLen{R.buf.p, R.tok_start.p, host_tok.p, P, n_host}), host_off.p, n_host + 1));
-        std::vector<int64_t> off((size_t)n_host + 1);
-        SEQ_TRY(seq_read_back(R, off.data(), host_off.p, (size_t)(n_host + 1) * 8));
-        SEQ_TRY(seq_alloc(R, blob, off[(size_t)n_host], "the host tokens' bytes"));
-        hipLaunchKernelGGL(k_vec_host_bytes, dim3(seq_grid(n_host)), dim3(SEQ_BLOCK), 0, R.stream, R.buf.p, R.tok_start.p, host_tok.p, host_off.p, P, n_host, blob.p);
-        SEQ_TRY(seq_kernels_end(R));
-        std::unique_ptr<char[]> text(new char[(size_t)off[(size_t)n_host]]);
-        SEQ_TRY(seq_read_back(R, text.get(), blob.p, (size_t)off[(size_t)n_host]));
-        std::vector<uint32_t> bits((size_t)n_host);
-        locale_t c_locale = newlocale(LC_ALL_MASK, "C", (locale_t)0);
-        if (!c_locale) DGE_FAIL(DGE_ERR_STATE, "%s: the \"C\" locale is not available", who);
-        for (int64_t k = 0; k < n_host; k++) { const float f = strtof_l(text.get() + off[(size_t)k], nullptr, c_locale); memcpy(&bits[(size_t)k], &f, 4); }
-        freelocale(c_locale);
+        SEQ_TRY(seq_pick(R, status.p, T - P, n_host, host_tok, "the host tokens"));
+        SEQ_TRY(seq_tokens_to_host(R, VecHostStart{R.tok_start.p, host_tok.p, P}, n_host, off, text, "the host tokens"));
+        SEQ_TRY(seq_host_numbers(text.get(), off.data(), n_host, bits, who));
         DGE_HIP(hipMemcpyAsync(host_bits.p, bits.data(), (size_t)n_host * 4, hipMemcpyHostToDevice, R.stream));
         SEQ_TRY(seq_kernels_begin(R));
         hipLaunchKernelGGL(k_vec_scatter, dim3(seq_grid(n_host)), dim3(SEQ_BLOCK), 0, R.stream, host_tok.p, host_bits.p, n_host, R.rowx.p, R.row_first.p, hdrx.p, R.tok_id.p, P, dim, vals.p);
@@ -333,27 +292,18 @@ extern "C" int dge_vectors_from_vec_text(int device, const char* text, int64_t n
     SEQ_TRY(dge_require_device(device));
     SeqRun R;
     R.device = device;
-    SeqPiece p; p.mem = reinterpret_cast<const uint8_t*>(text); p.size = n_bytes;
-    R.pieces.push_back(p);
+    SEQ_TRY(seq_add_texts(R.pieces, &text, &n_bytes, 1, "dge_vectors_from_vec_text"));
     return vec_read(R, header, names, intern ? 1 : 0, out, info, "dge_vectors_from_vec_text");
 }
 
 extern "C" int dge_vectors_from_vec_files(int device, const char* const* paths, int32_t n_paths, int header, dge_names* names, int intern, dge_vectors** out, dge_vec_info* info) {
     if (!out || !names || n_paths < 0 || (n_paths > 0 && !paths)) DGE_FAIL(DGE_ERR_ARG, "dge_vectors_from_vec_files: null or negative argument");
-    for (int32_t k = 0; k < n_paths; k++) if (!paths[k]) DGE_FAIL(DGE_ERR_ARG, "dge_vectors_from_vec_files: path %d is null", k);
+    SEQ_TRY(seq_check_paths(paths, n_paths, "dge_vectors_from_vec_files"));
     *out = nullptr;
     SEQ_TRY(dge_require_device(device));
     SeqRun R;
     R.device = device;
-    for (int32_t k = 0; k < n_paths; k++) {
-        SeqPiece p; p.path = paths[k];
-        p.fd = open(paths[k], O_RDONLY | O_CLOEXEC);
-        if (p.fd < 0) DGE_FAIL(DGE_ERR_IO, "cannot open %s: %s", paths[k], strerror(errno));
-        R.pieces.push_back(p);                     // (the run closes it)
-        struct stat st;
-        if (fstat(p.fd, &st) != 0 || !S_ISREG(st.st_mode)) DGE_FAIL(DGE_ERR_IO, "cannot read %s: not a regular file", paths[k]);
-        R.pieces.back().size = (int64_t)st.st_size;
-    }
+    SEQ_TRY(seq_add_files(R.pieces, paths, n_paths, "dge_vectors_from_vec_files"));
     return vec_read(R, header, names, intern ? 1 : 0, out, info, "dge_vectors_from_vec_files");
 }
 

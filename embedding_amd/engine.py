@@ -55,19 +55,12 @@ class DeviceGraph:
         g = cls(device)
         inf = OdInfo()
         nh = names._h if names is not None else None
-        pieces = paths_or_list_of_bytes
-        if isinstance(pieces, (str, os.PathLike)):
-            pieces = [pieces]
-        pieces = list(pieces)
-        if pieces and all(isinstance(p, (bytes, bytearray, memoryview)) for p in pieces):
-            views = [np.frombuffer(p, np.uint8) for p in pieces]
-            ptrs = (C.c_void_p * len(views))(*[v.ctypes.data if v.size else None for v in views])
-            sizes = (C.c_int64 * len(views))(*[v.size for v in views])
-            check(lib.dge_graph_add_od_texts(g._h, ptrs, sizes, len(views), nh, C.byref(inf)))
+        kind, _keep, ptrs, sizes, n = _piece_args(paths_or_list_of_bytes)
+        if kind == "texts":
+            check(lib.dge_graph_add_od_texts(g._h, ptrs, sizes, n, nh, C.byref(inf)))
         else:
-            arr = (C.c_char_p * len(pieces))(*[os.fsencode(p) for p in pieces])
-            check(lib.dge_graph_add_od_files(g._h, arr, len(pieces), nh, C.byref(inf)))
-        return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
+            check(lib.dge_graph_add_od_files(g._h, ptrs, n, nh, C.byref(inf)))
+        return g, names, _info_dict(inf, reserved=False)
 
     @classmethod
     def from_flows(cls, flows, T, mode=DGE_SLOTS_EVEN, names=True):
@@ -80,7 +73,7 @@ class DeviceGraph:
         g = cls(flows.regions.device)
         inf = OdInfo()
         check(lib.dge_graph_add_flows(g._h, flows._h, int(T), int(mode), names._h if names is not None else None, C.byref(inf)))
-        return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
+        return g, names, _info_dict(inf, reserved=False)
 
     @classmethod
     def from_flow_windows(cls, flows, windows, names=True):
@@ -97,7 +90,7 @@ class DeviceGraph:
         inf = OdInfo()
         win = _windows(windows)
         check(lib.dge_graph_add_flow_windows(g._h, flows._h, win, len(win), names._h if names is not None else None, C.byref(inf)))
-        return g, names, {f[0]: getattr(inf, f[0]) for f in OdInfo._fields_ if f[0] != "reserved"}
+        return g, names, _info_dict(inf, reserved=False)
 
     @classmethod
     def from_spatial(cls, regions_or_ids_xy, k=10, scale=100.0, names=True, device=0):
@@ -238,14 +231,32 @@ def _windows(windows):
     return (HourWindow * len(windows))(*[HourWindow(a, b) for a, b in windows])
 
 
+_BYTES = (bytes, bytearray, memoryview)
+
+
 def _text_args(texts):
     """bytes-like pieces -> (the arrays kept alive, pointer array, size array, count)"""
-    if isinstance(texts, (bytes, bytearray, memoryview)):
+    if isinstance(texts, _BYTES):
         texts = [texts]
     views = [np.frombuffer(t, np.uint8) for t in texts]
     ptrs = (C.c_void_p * max(len(views), 1))(*[v.ctypes.data if v.size else None for v in views])
     sizes = (C.c_int64 * max(len(views), 1))(*[v.size for v in views])
     return views, ptrs, sizes, len(views)
+
+
+def _piece_args(x, kind=None):
+    """A path, a sequence of paths, a bytes-like or a sequence of bytes-likes -> (kind, the arrays kept alive, pointer array, size array, count), kind "texts"
+    or "paths" (no size array then).  kind given: the caller's entry takes only that.  Otherwise texts are a bytes-like or a sequence of nothing but
+    bytes-likes; an empty sequence is one of paths."""
+    if isinstance(x, (str, os.PathLike)):
+        x = [x]
+    elif not isinstance(x, _BYTES):
+        x = list(x)
+    if kind is None:
+        kind = "texts" if isinstance(x, _BYTES) or (x and all(isinstance(p, _BYTES) for p in x)) else "paths"
+    if kind == "texts":
+        return ("texts",) + _text_args(x)
+    return "paths", None, (C.c_char_p * max(len(x), 1))(*[os.fsencode(p) for p in x]), None, len(x)
 
 
 def parse_trips(texts, fmt, header=True, slab_bytes=0, device=0):
@@ -369,7 +380,7 @@ class Flows:
     def add_trip_text(self, texts, fmt, header=True, slab_bytes=0):
         """Taxi trip text (one text or a sequence of texts, bytes-like, each a piece) parsed and added on the device (include/dge.h: dge_flows_add_trip_texts):
         the table stands where add_trips leaves it on the status-0 records of the text.  -> the fields of struct dge_trip_text_info"""
-        views, ptrs, sizes, n = _text_args(texts)
+        _, _keep, ptrs, sizes, n = _piece_args(texts, "texts")
         opt = TripTextOptions(int(fmt), 1 if header else 0, int(slab_bytes))
         inf = TripTextInfo()
         check(lib.dge_flows_add_trip_texts(self._h, ptrs, sizes, n, C.byref(opt), C.byref(inf)))
@@ -377,13 +388,10 @@ class Flows:
 
     def add_trip_files(self, paths, fmt, header=True, slab_bytes=0):
         """The same for trip files (one path or a sequence), streamed from disk: dge_flows_add_trip_files."""
-        if isinstance(paths, (str, os.PathLike)):
-            paths = [paths]
-        paths = list(paths)
-        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        _, _keep, arr, _, n = _piece_args(paths, "paths")
         opt = TripTextOptions(int(fmt), 1 if header else 0, int(slab_bytes))
         inf = TripTextInfo()
-        check(lib.dge_flows_add_trip_files(self._h, arr, len(paths), C.byref(opt), C.byref(inf)))
+        check(lib.dge_flows_add_trip_files(self._h, arr, n, C.byref(opt), C.byref(inf)))
         return _info_dict(inf)
 
     def info(self):
@@ -516,7 +524,7 @@ class Flows:
         W = np.empty((n, rank), np.float64); H = np.empty((rank, n), np.float64); index = np.empty(n, np.int64); inf = NmfInfo()
         check(lib.dge_nmf_flows(self._h, int(T), int(mode), int(slot), _ptr(select), C.byref(cfg), _ptr(W), _ptr(H), _ptr(index), C.byref(inf)))
         ids = getattr(self.regions, "ids", None)
-        info = {k: v for k, v in _info_dict(inf).items() if k != "reserved"}
+        info = _info_dict(inf, reserved=False)
         info["region_index"] = index
         return W, H, (ids[index] if ids is not None else index), info
 
@@ -628,19 +636,12 @@ class WalkCorpus:
         if names is None:
             names = Names()
         h = C.c_void_p(0); inf = SeqInfo()
-        if isinstance(paths_or_bytes, (bytes, bytearray, memoryview)):
-            data = paths_or_bytes
-            if isinstance(data, bytes):
-                ptr = C.cast(C.c_char_p(data), C.c_void_p); n = len(data)
-            else:
-                view = np.frombuffer(data, np.uint8)
-                ptr = _ptr(view); n = view.size
-            check(lib.dge_walks_from_seq_text(int(device), ptr, n, names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
+        kind, _keep, ptrs, sizes, n = _piece_args(paths_or_bytes, "texts" if isinstance(paths_or_bytes, _BYTES) else "paths")      # the text comes alone
+        if kind == "texts":
+            check(lib.dge_walks_from_seq_text(int(device), ptrs[0], sizes[0], names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
         else:
-            paths = [paths_or_bytes] if isinstance(paths_or_bytes, (str, os.PathLike)) else list(paths_or_bytes)
-            arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
-            check(lib.dge_walks_from_seq_files(int(device), arr, len(paths), names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
-        return cls(h, int(device)), names, {f[0]: getattr(inf, f[0]) for f in SeqInfo._fields_ if f[0] != "reserved"}
+            check(lib.dge_walks_from_seq_files(int(device), ptrs, n, names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
+        return cls(h, int(device)), names, _info_dict(inf, reserved=False)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -716,19 +717,12 @@ class Vectors:
         if names is None:
             names = Names()
         h = C.c_void_p(0); inf = VecInfo()
-        if isinstance(paths_or_bytes, (bytes, bytearray, memoryview)):
-            data = paths_or_bytes
-            if isinstance(data, bytes):
-                ptr = C.cast(C.c_char_p(data), C.c_void_p); n = len(data)
-            else:
-                view = np.frombuffer(data, np.uint8)
-                ptr = _ptr(view); n = view.size
-            check(lib.dge_vectors_from_vec_text(int(device), ptr, n, int(bool(header)), names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
+        kind, _keep, ptrs, sizes, n = _piece_args(paths_or_bytes, "texts" if isinstance(paths_or_bytes, _BYTES) else "paths")      # the text comes alone
+        if kind == "texts":
+            check(lib.dge_vectors_from_vec_text(int(device), ptrs[0], sizes[0], int(bool(header)), names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
         else:
-            paths = [paths_or_bytes] if isinstance(paths_or_bytes, (str, os.PathLike)) else list(paths_or_bytes)
-            arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
-            check(lib.dge_vectors_from_vec_files(int(device), arr, len(paths), int(bool(header)), names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
-        return cls(h, int(device)), names, {f[0]: getattr(inf, f[0]) for f in VecInfo._fields_ if f[0] != "reserved"}
+            check(lib.dge_vectors_from_vec_files(int(device), ptrs, n, int(bool(header)), names._h, int(bool(intern)), C.byref(h), C.byref(inf)))
+        return cls(h, int(device)), names, _info_dict(inf, reserved=False)
 
     @classmethod
     def from_host(cls, rows, present=None, device=0):

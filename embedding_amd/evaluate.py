@@ -46,9 +46,9 @@ def ndcg_vectors(vectors, gnd_vectors, k=10):
     return vectors.ndcg_against(gnd_vectors, k)
 
 
-def _info_dict(inf):
-    """the fields of a ctypes info struct"""
-    return {f[0]: getattr(inf, f[0]) for f in inf._fields_}
+def _info_dict(inf, reserved=True):
+    """the fields of a ctypes info struct; reserved=False: without the field of that name"""
+    return {f[0]: getattr(inf, f[0]) for f in inf._fields_ if reserved or f[0] != "reserved"}
 
 
 def _select_mask(select, n):

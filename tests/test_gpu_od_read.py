@@ -367,3 +367,57 @@ def test_empty_texts_and_range(dge):
     first = b"".join(b"%d %d 1\n" % (a, b) for a, b in zip(ids[::2].tolist(), ids[1::2].tolist()))
     msg = fails(dge, lambda: dge.DeviceGraph.from_od([first] + [b""] * 39_999), code=2)
     assert "40000 slices of 53688 regions" in msg
+
+
+# ------------------------------------------------------------------------------------------ the shared hand-back (csrc/seq_tokens.h: seq_pick, seq_tokens_to_host)
+def host_count_pieces(n_host):
+    """600 flows over 3 pieces, every second weight one the host finishes (more than 19 significant digits) until n_host are placed; every weight is distinct"""
+    lines = [b"%d %d %s\n" % (IDS[i % 30], IDS[(i * 7 + 1) % 30], b"%d.00000000000000000001" % (i + 1) if i % 2 == 0 and i // 2 < n_host else b"%d" % (i + 1)) for i in range(600)]
+    return [b"".join(lines[:211]), b"".join(lines[211:389]), b"".join(lines[389:])]
+
+
+@pytest.mark.parametrize("n_host", [1, 256, 257])
+def test_the_hand_back_count_across_a_workgroup(dge, classify, n_host):
+    """1, 256 and 257 host weights among weights the device finishes, over 3 pieces: one lane, a full workgroup and one lane of a second one in seq_pick's
+    index kernel and in the byte copy; a misplaced weight shows in the store, where every edge's weight is its own."""
+    pieces = host_count_pieces(n_host)
+    ref = second_reading(pieces, classify)
+    g, names, info = got = dge.DeviceGraph.from_od(pieces)
+    check(dge, got, ref, walks=False)
+    assert info["host_values"] == ref["info"]["host_values"] == n_host
+
+
+def test_host_weights_around_the_eight_byte_loop(dge, classify):
+    """Host weights of 7, 8, 9, 16 and 17 bytes (seq_tok_len reads 8 bytes at a time) — od_parse.h hands back no token of fewer than 4 bytes, so there is none of
+    1 byte — one of them the last token of the last piece with no newline behind it.  (A weight is never the first token of a piece: test_gpu_vec_read.py
+    and test_gpu_seq_ingest.py put a new name there.)  The 25-digit weight of test_weight_forms is the 25-byte case."""
+    forms = [b"1.23e99", b"1.234e99", b"1.2345e99", b"1.23456789012e99", b"1.234567890123e99", b"1e55"]
+    assert [len(f) for f in forms] == [7, 8, 9, 16, 17, 4] and classify(forms) == len(forms)
+    lines = [b"%d %d %s" % (IDS[i], IDS[i + 1], f) for i, f in enumerate(forms + forms[::-1])]
+    pieces = [b"\n".join(lines[:5]) + b"\n", b"\n".join(lines[5:]).replace(b" ", b"\t")]
+    assert pieces[1].endswith(b"\t1.23e99")
+    ref = second_reading(pieces, classify)
+    g, names, info = got = dge.DeviceGraph.from_od(pieces)
+    check(dge, got, ref, walks=False)
+    assert info["host_values"] == 12
+    assert sorted(g.get_csr(tables=False)["weight"].tolist()) == sorted(float(f) for f in forms * 2)
+
+
+RAGGED = {           # row -> the message of the parent commit's library for ragged_pieces(row)
+    0: "libdge error 7: dge_graph_add_od_texts: the line at offset 0 of the text (piece 0), line 1, column 1 has 2 tokens where 3 are expected: src dst w",
+    256: "libdge error 7: dge_graph_add_od_texts: the line at offset 4802 of the text (piece 1), line 127, column 1 has 2 tokens where 3 are expected: src dst w",
+    299: "libdge error 7: dge_graph_add_od_texts: the line at offset 5634 of the text (piece 1), line 170, column 1 has 2 tokens where 3 are expected: src dst w",
+}
+
+
+def ragged_pieces(row):
+    """300 flows over 2 pieces; flow `row` lacks its weight"""
+    lines = [b"%d %d %d" % (IDS[i % 30], IDS[(i + 3) % 30], i + 1) if i != row else b"%d %d" % (IDS[i % 30], IDS[(i + 3) % 30]) for i in range(300)]
+    return [b"\n".join(lines[:130]) + b"\n", b"\n".join(lines[130:]) + b"\n"]
+
+
+@pytest.mark.parametrize("row", [0, 256, 299])
+def test_a_ragged_row_is_named_as_before(dge, row):
+    """k_seq_ragged without a skip mask and seq_row_where: a row one token short at row 0, at row 256 (the first lane of the second workgroup) and at the last
+    row.  The message — offset, piece, line, column, counts — is the one the library gave before the kernel and the read-back were shared."""
+    assert fails(dge, lambda: dge.DeviceGraph.from_od(ragged_pieces(row))) == RAGGED[row]

@@ -269,3 +269,25 @@ def test_errors(dge, tmp_path):
     assert names.as_bytes() == [b"a"]
     corpus, _, info = dge.WalkCorpus.from_seq(ok, names=names)      # the names object is still good
     assert corpus.to_host().tolist() == [[0, 1, 2], [3, 4, -1]] and info["lines"] == 2
+
+
+# ------------------------------------------------------------------------------------------ the new names' way to the host (csrc/seq_tokens.h: seq_tokens_to_host)
+def test_new_names_across_a_workgroup_and_around_the_eight_byte_loop(dge, tmp_path):
+    """257 new names behind 3 prior ones — a full workgroup and one lane more in k_seq_name_tok and in the byte copy — among them names of 1, 7, 8, 9, 16 and 17
+    bytes (seq_tok_len, which now gives a name its length, reads 8 bytes at a time), one the first token of the second piece and one the last token of the
+    last piece with no newline behind it.  The Names bytes are the second reading's, in first-appearance order."""
+    prior = [b"p0", b"never-in-the-text", b"p2"]
+    sized = [bytes([97 + k]) * n for k, n in enumerate((1, 7, 8, 9, 16, 17))]
+    fresh = sized[:3] + [b"n%d" % ((k * 41) % 251) for k in range(251)] + sized[3:]
+    assert len(set(fresh)) == len(fresh) == 257
+    toks = [b"p2"] + [t for k, n in enumerate(fresh) for t in ((n, fresh[k // 2]) if k % 3 else (n, b"p0"))]          # every name again later, and prior ones between
+    cut = toks.index(sized[3])
+    lines = lambda ts: b"\n".join(b" ".join(ts[i:i + 9]) for i in range(0, len(ts), 9))
+    pieces = [lines(toks[:cut]) + b"\n", lines(toks[cut:] + [sized[5]])]
+    assert pieces[1].startswith(sized[3] + b" ") and pieces[1].endswith(b" " + sized[5])
+    paths = [str(tmp_path / ("w%d.seq" % k)) for k in range(2)]
+    for p, data in zip(paths, pieces):
+        open(p, "wb").write(data)
+    corpus, names, info = got = dge.WalkCorpus.from_seq(paths, names=dge.Names(prior))
+    check(dge, pieces, got, prior=prior)
+    assert info["names_added"] == 257 and names.as_bytes() == prior + fresh

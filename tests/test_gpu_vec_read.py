@@ -344,3 +344,81 @@ def test_a_text_above_two_to_the_31_bytes(dge, classify):
     assert info["bytes"] == n > 2 ** 31 and info["rows"] == 11 and info["lines"] == counts["lines"] and info["host_values"] == 1 and info["dim"] == 4
     assert names.as_bytes() == want_names and same_bits(vec.to_host(), want) and vec.present().all()
     print("text of %.2f GB: read %.0f ms, kernels %.0f ms" % (n / 1e9, info["read_ms"], info["kernel_ms"]))
+
+
+# ------------------------------------------------------------------------------------------ the shared hand-back (csrc/seq_tokens.h: seq_pick, seq_tokens_to_host)
+PRIOR3 = [b"r5", b"never-in-the-text", b"r0"]
+
+
+def host_count_pieces(n_host):
+    """200 rows of 3 values over 2 pieces, each with its "V D" line; every second value is one the host finishes (more than 19 significant digits) until n_host
+    are placed; every value is distinct"""
+    rows = [b"r%d " % r + b" ".join(b"%d.00000000000000000001" % (3 * r + c + 1) if (3 * r + c) % 2 == 0 and (3 * r + c) // 2 < n_host else b"%d" % (3 * r + c + 1) for c in range(3))
+            for r in range(200)]
+    return [b"120 3\n" + b"\n".join(rows[:120]) + b"\n", b"80 3\n" + b"\n".join(rows[120:]) + b"\n"]
+
+
+@pytest.mark.parametrize("n_host", [1, 256, 257])
+def test_the_hand_back_count_across_a_workgroup(dge, classify, tmp_path, n_host):
+    """1, 256 and 257 host values among values the device finishes: one lane, a full workgroup and one lane of a second one in seq_pick's index kernel and in
+    the byte copy.  header=True over 2 pieces and 3 prior names, so that P, hdrx and the piece lookup all enter the index arithmetic; a misplaced value shows,
+    every value is its own."""
+    pieces = host_count_pieces(n_host)
+    paths = [str(tmp_path / ("h%d.vec" % k)) for k in range(2)]
+    for p, data in zip(paths, pieces):
+        open(p, "wb").write(data)
+    vec, names, info = got = dge.Vectors.from_vec(paths, header=True, names=dge.Names(PRIOR3))
+    check(dge, pieces, got, classify, header=True, prior=PRIOR3)
+    assert info["host_values"] == n_host and info["names_added"] == 198
+
+
+LENGTHS = (1, 7, 8, 9, 16, 17)
+
+
+def test_lengths_around_the_eight_byte_loop(dge, classify, tmp_path):
+    """New names of 1, 7, 8, 9, 16 and 17 bytes and host values of 14 (the shortest vec_parse.h hands back: ten digits and an exponent below -54), 16, 17 and 22
+    bytes — seq_tok_len reads 8 bytes at a time.  A new name is the first token of the second piece; a host value is the last token of the last piece with no
+    newline behind it."""
+    hosts = [b"1234567891e-55", b"123456789123e-57", b"1234567891234e-58", b"7.00000000000000000001"]
+    assert [len(h) for h in hosts] == [14, 16, 17, 22] and classify(hosts) == len(hosts)
+    names = [bytes([97 + k]) * n for k, n in enumerate(LENGTHS)] + [bytes([65 + k]) * n for k, n in enumerate(LENGTHS)]
+    rows = [n + b" %d " % (k + 1) + hosts[k % 4] for k, n in enumerate(names)]
+    pieces = [b"\n".join(rows[:6]) + b"\n", b"\n".join(rows[6:])]
+    assert pieces[1].startswith(b"A 7 ") and pieces[1].endswith(b" 7.00000000000000000001")
+    paths = [str(tmp_path / ("l%d.vec" % k)) for k in range(2)]
+    for p, data in zip(paths, pieces):
+        open(p, "wb").write(data)
+    vec, got_names, info = got = dge.Vectors.from_vec(paths, names=dge.Names(PRIOR3))
+    check(dge, pieces, got, classify, prior=PRIOR3)
+    assert info["host_values"] == 12 and got_names.as_bytes() == PRIOR3 + names
+
+
+def test_new_names_across_a_workgroup_with_a_host_value(dge, classify):
+    """257 new names behind 3 prior ones: a full workgroup and one lane more in k_seq_name_tok and in the byte copy of seq_tokens_to_host, which the same call
+    runs a second time for its one host value.  The Names are the second reading's, in first-appearance order."""
+    rows = [b"n%d %d\n" % ((k * 37) % 257, k + 1) for k in range(257)]
+    rows[100] = b"n%d 16777217.0000000000000000000000001\n" % ((100 * 37) % 257)
+    data = b"r0 1000\n" + b"".join(rows)
+    vec, names, info = got = dge.Vectors.from_vec(data, names=dge.Names(PRIOR3))
+    check(dge, data, got, classify, prior=PRIOR3)
+    assert info["names_added"] == 257 and info["host_values"] == 1 and names.as_bytes()[3:5] == [b"n0", b"n37"]
+
+
+RAGGED = {           # row -> the message of the parent commit's library for ragged_text(row)
+    0: "libdge error 7: dge_vectors_from_vec_text: the row at offset 11 of the text (piece 0), line 3, column 1 has 3 tokens where 2 are expected (a name and 1 values, as on the first row)",
+    256: "libdge error 7: dge_vectors_from_vec_text: the row at offset 3061 of the text (piece 0), line 258, column 1 has 2 tokens where 3 are expected (a name and 2 values, as on the first row)",
+    299: "libdge error 7: dge_vectors_from_vec_text: the row at offset 3620 of the text (piece 0), line 301, column 1 has 2 tokens where 3 are expected (a name and 2 values, as on the first row)",
+}
+
+
+def ragged_text(row):
+    """300 rows of 2 values behind their "V D" line; row `row` lacks its last value"""
+    return b"300 2\n" + b"".join(b"r%d %d %d\n" % (r, r + 1, 2 * r) if r != row else b"r%d %d\n" % (r, r + 1) for r in range(300))
+
+
+@pytest.mark.parametrize("row", [0, 256, 299])
+def test_a_ragged_row_is_named_as_before(dge, row):
+    """k_seq_ragged with the header line as its skip mask and seq_row_where: a row one token short at row 0 — dim is then its own, and row 1 is the ragged one
+    — at row 256 (text row 257 with the header: the second workgroup) and at the last row.  The message — offset, piece, line, column, counts — is the one
+    the library gave before the kernel and the read-back were shared."""
+    assert fails(dge, lambda: dge.Vectors.from_vec(ragged_text(row), header=True)) == RAGGED[row]

@@ -87,7 +87,10 @@ def test_vec_read_is_built_into_the_library_and_stays_out_of_the_stamp():
     recipes = [l for l in mk.splitlines() if l.startswith("\t") and "vec_read" in l]
     assert recipes == []                               # the generic rule builds it
     # the tokeniser exists once: both readers include the header that holds it
+    # (the joiner is host code and stands in seq_pieces.h, which seq_tokens.h includes)
     tok = open(os.path.join(CSRC, "seq_tokens.h")).read()
+    assert '#include "seq_pieces.h"' in tok and "struct SeqJoiner" not in tok
+    tok += open(os.path.join(CSRC, "seq_pieces.h")).read()
     for name in ("k_seq_count", "k_seq_emit", "k_seq_hash", "k_seq_intern", "k_seq_row_first", "struct SeqJoiner"):
         assert tok.count("void __launch_bounds__(SEQ_BLOCK) " + name + "(") == 1 or (name.startswith("struct") and tok.count(name) == 1), name
         for f in ("seq_ingest.hip", "vec_read.hip"):
