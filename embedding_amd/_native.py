@@ -156,6 +156,12 @@ class SvmInfo(C.Structure):
                 ("support", C.c_int64), ("kernel_bytes", C.c_int64), ("launches", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class PairwiseInfo(C.Structure):
+    """struct dge_pairwise_info (include/dge.h) — what dge_pairwise_eval_vectors reports."""
+    _fields_ = [("regions", C.c_int64), ("members", C.c_int64), ("tested", C.c_int64), ("threshold_keys", C.c_int64), ("knn_ms", C.c_double),
+                ("ground_ms", C.c_double), ("score_ms", C.c_double)]
+
+
 class HourWindow(C.Structure):
     """struct dge_hour_window (include/dge.h): the hours start, start + 1, .., start + hours - 1, each mod 24."""
     _fields_ = [("start", C.c_int32), ("hours", C.c_int32)]
@@ -326,6 +332,8 @@ SIGNATURES = {
     "dge_svm_fit": (_int, [_int, _vp, _i64, _i32, _vp, _i32, _vp, _P(SvmCfg), _vp, _vp, _vp, _vp, _P(SvmInfo)]),
     "dge_svm_decision": (_int, [_int, _vp, _i64, _i32, _vp, _vp, _i32, C.c_double, _vp, _i64, _vp]),
     "dge_svm_cv": (_int, [_int, _vp, _i64, _i32, _vp, _i32, _vp, _i32, _P(SvmCfg), _vp, _vp, _vp, _vp, _vp, _vp, _P(SvmInfo)]),
+    "dge_pairwise_eval_vectors": (_int, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _P(PairwiseInfo)]),
+    "dge_pairwise_ground_vectors": (_int, [_vp, _i32, _vp, _vp]),
     "dge_selftest_locked_rows": (_int, [_int, _i32, _i64, _i32, C.c_uint64, _i32, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave": (_int, [_int, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),
     "dge_selftest_atomics_wave_block": (_int, [_int, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _P(_i64), _P(_dbl)]),

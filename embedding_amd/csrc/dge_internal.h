@@ -181,3 +181,7 @@ int dge_graph_adopt_pruned(dge_graph* g, int64_t* d_row_ptr, double* d_w, int32_
 // launches the strided walk kernel on `stream`; rows [row0,row0+n) of out (row length L)
 int dge_launch_walks_strided(const dge_graph* g, hipStream_t stream, int32_t* d_out, int64_t n, int32_t L,
                              int64_t seed, int64_t first_index, int32_t* d_deadend_count);
+
+// knn.hip's device form for other translation units: x [n x D] in device memory -> the k nearest other rows of every row (d_oi, d_od: [n x k]); d_present may be
+// null; d_inv [n] and d_xn [n x 256] are scratch the caller owns.  k is bounded only by the strip kernel's LDS (DGE_ERR_ARG beyond it).  One host wait.
+int dge_knn_device(const float* d_x, const uint8_t* d_present, int n, int D, int k, float* d_inv, float* d_xn, int32_t* d_oi, float* d_od, double* ms_kernel);

@@ -308,3 +308,9 @@ extern "C" int dge_ndcg_at_k_vectors(const dge_vectors* f, const dge_vectors* gn
     if ((rc = dge_require_device(f->device))) return rc;
     return ndcg_device(f->d, f->dim, gnd->d, gnd->dim, (int32_t)f->rows, k, ndcg, ms_kernels);
 }
+
+// knn_device for the other translation units (pairwise.hip: a set's members stacked in device memory); declared in dge_internal.h.  The callers above check
+// k against KNN_MAX_K; this one leaves the limit to the strip kernel's LDS check.
+int dge_knn_device(const float* d_x, const uint8_t* d_present, int n, int D, int k, float* d_inv, float* d_xn, int32_t* d_oi, float* d_od, double* ms_kernel) {
+    return knn_device(d_x, d_present, n, D, k, d_inv, d_xn, d_oi, d_od, ms_kernel);
+}

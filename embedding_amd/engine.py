@@ -780,6 +780,43 @@ class Vectors:
         check(lib.dge_ndcg_at_k_vectors(self._h, gnd._h, int(k), C.byref(out), C.byref(ms)))
         return out.value, ms.value
 
+    def pairwise_eval(self, gnd, row_of, ks=(5, 10, 20, 30, 40, 50, 60, 70), rel_m=0, test=None, want_rows=False, want_lists=False):
+        """The per-slice pairwise figure of these feature rows under the ground rows `gnd` (a Vectors, one row a region) as the rule of include/dge.h
+        (dge_pairwise_eval_vectors); see evaluate.pairwise_eval for the arguments and the dict it returns."""
+        from ._native import PairwiseInfo
+        n = gnd.shape[0]
+        row_of = np.ascontiguousarray(row_of, np.int64)
+        if row_of.ndim == 1:
+            row_of = row_of[None, :]
+        if row_of.ndim != 2 or row_of.shape[1] != n:
+            raise ValueError("row_of must be [n_sets x n] with n = %d ground rows, not %s" % (n, list(row_of.shape)))
+        ks = np.ascontiguousarray(np.atleast_1d(ks), np.int32)
+        if ks.ndim != 1 or len(ks) == 0:
+            raise ValueError("ks must be a non-empty one-dimensional sequence")
+        test = _select_mask(test, n)
+        S, K, kmax, rel_m = row_of.shape[0], len(ks), int(ks[-1]), int(rel_m)
+        ndcg = np.zeros((S, K)); precision = np.zeros((S, K)) if rel_m else None
+        members = np.zeros(S, np.int64); tested = np.zeros(S, np.int64); inf = PairwiseInfo()
+        ratio = np.empty((S, K, n)) if want_rows else None; hits = np.empty((S, K, n), np.int32) if want_rows else None
+        ideal = np.empty((K, n)) if want_rows else None
+        lists = np.empty((S, n, max(kmax, 0)), np.int32) if want_lists else None
+        check(lib.dge_pairwise_eval_vectors(self._h, gnd._h, _ptr(row_of), S, _ptr(test), _ptr(ks), K, rel_m, _ptr(ndcg), _ptr(precision), _ptr(members),
+                                            _ptr(tested), _ptr(ratio), _ptr(hits), _ptr(lists), _ptr(ideal), C.byref(inf)))
+        out = dict(ndcg=ndcg, precision=precision, members=members, tested=tested, coverage=members / float(n), ks=ks, info=_info_dict(inf))
+        if want_rows:
+            out.update(ratio=ratio, hits=hits, ideal=ideal)
+        if want_lists:
+            out["lists"] = lists
+        return out
+
+    def pairwise_ground(self, m):
+        """These rows as ground rows: the m <= 128 nearest other regions of every region by the keys of the pairwise rule (dge_pairwise_ground_vectors)
+        -> (idx int32 [n x m], dist float64 [n x m])."""
+        n, m = self.shape[0], int(m)
+        idx = np.empty((n, max(m, 0)), np.int32); dist = np.empty((n, max(m, 0)), np.float64)
+        check(lib.dge_pairwise_ground_vectors(self._h, m, _ptr(idx), _ptr(dist)))
+        return idx, dist
+
     def kmeans(self, k, seed=1, n_init=10, max_iter=300, select=None, init=None):
         """k-means on these rows as the rule of include/dge.h (dge_kmeans_vectors): the same bits for the same rows, k, seed, n_init and max_iter.
         select: one entry per row, non-zero = take the row (default: every present row).  init: [k x dim] initial centres instead of k-means++ seeding

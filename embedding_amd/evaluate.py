@@ -391,3 +391,105 @@ def svm_cv_gpu(features, y, n_folds=10, fold=None, select=None, C=1.0, gamma=Non
     check(lib.dge_svm_cv(int(device), p(f), n, dim, p(y), L, p(fold), F, Ct.byref(cfg), p(correct), p(tested), p(iters), p(support), p(conv), p(decision), Ct.byref(inf)))
     return dict(svm_scores(correct, tested), iterations=iters, support=support, converged=conv, decision=decision, gamma=cfg.gamma,
                 info=_info_dict(inf))
+
+
+PAIRWISE_KS = (5, 10, 20, 30, 40, 50, 60, 70)      # the x-axis of the reference's figure (P/embeddingEvaluation_tract.py:789-792)
+
+
+def _as_vectors(rows, device=0):
+    """an engine.Vectors as it is (owned = False), host rows [n x dim] as a new one"""
+    from .engine import Vectors
+    if isinstance(rows, Vectors):
+        return rows, False
+    return Vectors.from_host(rows, device=device), True
+
+
+def pairwise_eval(features, gnd, row_of, ks=PAIRWISE_KS, rel_m=0, test=None, want_rows=False, want_lists=False, device=0):
+    """The reference's per-slice pairwise figure (evalute_by_pairwise_similarity, P/embeddingEvaluation_tract.py:285-367) as the rule of include/dge.h
+    (dge_pairwise_eval_vectors), one call per method: features [V x D] and gnd [n x g] are engine.Vectors or host rows; row_of int64 [n_sets x n] (or [n]: one
+    set) names the feature row of every region in every set (slice), -1 = the set lacks the region (slice_rows / region_rows make it from names).
+    -> dict(ndcg [n_sets x n_k]; precision, the same shape, None with rel_m = 0; members, tested [n_sets]; coverage = members / n; ks; info; with want_rows
+    ratio float64, hits int32 [n_sets x n_k x n] and ideal [n_k x n]; with want_lists lists int32 [n_sets x n x kmax], -1 rows for non-members)."""
+    made = []                                     # the resident rows this call uploads: closed on every way out, a failed second upload included
+    try:
+        f, own = _as_vectors(features, device)
+        if own:
+            made.append(f)
+        g, own = _as_vectors(gnd, device)
+        if own:
+            made.append(g)
+        return f.pairwise_eval(g, row_of, ks=ks, rel_m=rel_m, test=test, want_rows=want_rows, want_lists=want_lists)
+    finally:
+        for v in made:
+            v.close()
+
+
+def pairwise_ground(gnd, m, device=0):
+    """The ground's own m <= 128 nearest regions of every region by the rule's keys (dge_pairwise_ground_vectors): generatePairWiseGT's lists (:63-103) as far as a
+    list goes.  -> (idx int32 [n x m], dist float64 [n x m])."""
+    g, own = _as_vectors(gnd, device)
+    try:
+        return g.pairwise_ground(m)
+    finally:
+        if own:
+            g.close()
+
+
+def _region_index(region_ids):
+    ids = [int(r) for r in region_ids]
+    index = {r: i for i, r in enumerate(ids)}
+    if len(index) != len(ids):
+        raise ValueError("region_ids holds an id twice")
+    return index
+
+
+def _text(name):
+    return name.decode("utf-8", "replace") if isinstance(name, (bytes, bytearray)) else str(name)
+
+
+def slice_rows(names, region_ids, n_slices):
+    """The rows of a cross-interval embedding by slice, as retrieveCrossIntervalEmbeddings reads its names (P/embeddingEvaluation_tract.py:149-160): names[i],
+    "h-id", is the name of feature row i (a Names, or any sequence of str / bytes); region_ids: the n regions in ground order.  A name of a slice outside
+    0 .. n_slices-1 or of a region that is not in region_ids is ignored and counted, as is the later row of a name that comes twice; a name that is not two
+    integers around one "-" is a ValueError.  -> (row_of int64 [n_slices x n], -1 = no row; dict(foreign, unknown, duplicates))."""
+    index = _region_index(region_ids)
+    n_slices = int(n_slices)
+    row_of = np.full((max(n_slices, 0), len(index)), -1, np.int64)
+    counts = dict(foreign=0, unknown=0, duplicates=0)
+    for i, name in enumerate(names):
+        parts = _text(name).split("-")
+        try:
+            if len(parts) != 2:
+                raise ValueError
+            h, rid = int(parts[0]), int(parts[1])
+        except ValueError:
+            raise ValueError("row %d: %r is not a name of the form h-id" % (i, name)) from None
+        if not 0 <= h < n_slices:
+            counts["foreign"] += 1
+        elif rid not in index:
+            counts["unknown"] += 1
+        elif row_of[h, index[rid]] >= 0:
+            counts["duplicates"] += 1
+        else:
+            row_of[h, index[rid]] = i
+    return row_of, counts
+
+
+def region_rows(names, region_ids):
+    """slice_rows for an embedding whose names are plain region ids, one set: the taxi-all.vec column of the reference (:352-355).
+    -> (row_of int64 [1 x n]; dict(unknown, duplicates))."""
+    index = _region_index(region_ids)
+    row_of = np.full((1, len(index)), -1, np.int64)
+    counts = dict(unknown=0, duplicates=0)
+    for i, name in enumerate(names):
+        try:
+            rid = int(_text(name))
+        except ValueError:
+            raise ValueError("row %d: %r is not a region id" % (i, name)) from None
+        if rid not in index:
+            counts["unknown"] += 1
+        elif row_of[0, index[rid]] >= 0:
+            counts["duplicates"] += 1
+        else:
+            row_of[0, index[rid]] = i
+    return row_of, counts

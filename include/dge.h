@@ -1319,6 +1319,58 @@ int  dge_svm_cv(int device, const float* features, int64_t n_rows, int32_t dim, 
                 const dge_svm_cfg* cfg, int64_t* correct, int64_t* tested, int64_t* iterations, int64_t* support, int32_t* converged, double* decision, dge_svm_info* info);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-slice pairwise evaluation (new; additions only, DGE_VERSION unchanged): evalute_by_pairwise_similarity of P/embeddingEvaluation_tract.py:285-367, the
+ * figure behind python/ndcg.pickle — nDCG@k of a method's neighbour lists under the POI ground truth for every slice and every k of the figure at once,
+ * precision@k against the ground's nearest rel_m (precision_atK, :236-246) and coverage (:326-331), from resident rows (csrc/pairwise.hip; the per-element
+ * pieces: csrc/pairwise_rule.h).  The reference takes scipy's cosine and numpy's sums; here the figure is a RULE, restated by the kernels and by
+ * tests/pairwise_ref.py, and the result is a pure function of the inputs.
+ *
+ * Inputs: ground rows gnd [n x g] float32, one row a region, g <= 256; feature rows f [V x D], D <= 256; row_of [n_sets x n] int64, the feature row of region i
+ * in set s, or -1; test [n] bytes or NULL; ks [n_k], strictly ascending, 1 <= k <= 128, n_k <= 16, kmax the last; rel_m (0: no precision, else 1 .. n - 1).
+ *  1. MEMBERS.  Region i is a member of set s iff row_of[s][i] >= 0 and that row is present in f.  A set is scored over its members with test non-zero (NULL:
+ *     all members).  coverage = members / n.
+ *  2. GROUND DISTANCE.  Every value is widened to binary64.  ss[a] is the chain acc = acc + x_j * x_j and dot(a, b) the chain acc = acc + x_aj * x_bj, j
+ *     ascending from 0 (the product of two widened float32 is exact, so a fused multiply-add gives the same bits).  Row a is a ZERO VECTOR iff it is absent or
+ *     ss[a] is not in (0, +inf) — a NaN or an infinity anywhere in the row makes it one.  dist(a, b) = 2 if either is a zero vector, else
+ *     1 - dot / sqrt(ss[a] * ss[b]): one rounded multiply, one rounded sqrt, one rounded divide, one rounded subtract.  It is symmetric bit for bit.
+ *  3. GROUND ORDER of region r: the keys (dist(r, c), c) over ALL c != r in 0 .. n-1, members or not; the distance ascends, then the region number (Python's
+ *     stable sort over rids, :99, NaN -> 2, :96-97).  The ideal list is the kmax least keys; rank(r, j) = the number of c != r with key(r, c) < key(r, j).
+ *  4. DISCOUNTS.  disc[i] = 1 / log2(i + 2), i = 0 .. kmax-1, taken by the host with the C library's log2 and one division, then uploaded.
+ *  5. ESTIMATED LISTS.  The members' feature rows of set s are stacked in region order; the list of a member is exactly what dge_knn_cosine gives for that
+ *     stack with k = kmax, mapped back to region numbers (the stacking is monotone, so ties go to the smaller region number).  A set with fewer than kmax + 1
+ *     members: DGE_ERR_ARG naming the least such set and its member count (the reference raises there).
+ *  6. SCORES of a tested region r in set s.  dcg is the chain acc = acc + (1 - dist(r, nb_i)) * disc[i], i ascending: a rounded subtract, a rounded multiply, a
+ *     rounded add, no fma; its value after i = k-1 is dcg_k, so every k comes from one chain.  ideal_k[r] is the same chain over the ideal list.
+ *     ratio = ideal_k != 0 ? dcg_k / ideal_k : 0 (a zero-vector ground row has every relevance -1 and so ratio 1, as in the reference).
+ *     hits_k = the number of i < k with rank(r, nb_i) < rel_m.
+ *  7. MEANS.  ndcg[s][k] = the plain ascending sum of ratio over the tested regions in region order, taken on the host, divided by their count.
+ *     precision[s][k] = sum(hits_k) / (k * tested), the product an integer.  (The reference divides by the number of ALL regions, :241; `tested` is returned so
+ *     that a caller can rescale.)  A set with no tested region reports 0 and tested = 0.
+ *  8. ERRORS.  DGE_ERR_ARG for: a row_of entry outside [-1, V) (naming the set and the region); a feature row named twice within a set; n - 1 < kmax; ks not
+ *     strictly ascending; f and gnd on different devices; nulls and limits.  All of these are looked at before a device is looked for.  The presence of a
+ *     row, the one check that needs device data, comes after: a row_of entry that names an absent row makes no member, and a set left short is refused (5).
+ *  9. PURITY.  The result is a pure function of the two tables, row_of, test, ks and rel_m; it does not depend on launch geometry or on how the sets are
+ *     spread over calls.
+ * Outputs: ndcg, precision [n_sets x n_k] (precision NULL iff rel_m == 0); members, tested [n_sets]; ratio binary64 and hits int32 [n_sets x n_k x n], 0 where
+ * the region is not tested; lists int32 [n_sets x n x kmax], region numbers, -1 rows for non-members; ideal [n_k x n].  The last four and info may be NULL.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dge_pairwise_info {
+    int64_t regions;         /* n                                                                  */
+    int64_t members;         /* over all sets                                                      */
+    int64_t tested;          /* over all sets                                                      */
+    int64_t threshold_keys;  /* slots of a region's sorted neighbour keys in the rank pass (0: rel_m == 0) */
+    double  knn_ms;          /* HIP-event time of the strip kernels                                */
+    double  ground_ms;       /* of the ground side: norms, ideal pass, rank pass (none: rel_m == 0) */
+    double  score_ms;
+} dge_pairwise_info;         /* 56 bytes */
+int  dge_pairwise_eval_vectors(const dge_vectors* f, const dge_vectors* gnd, const int64_t* row_of, int32_t n_sets /* <= 64 */, const uint8_t* test,
+                               const int32_t* ks, int32_t n_k, int32_t rel_m, double* ndcg, double* precision, int64_t* members, int64_t* tested,
+                               double* ratio, int32_t* hits, int32_t* lists, double* ideal, dge_pairwise_info* info);
+/* the ground's own m <= 128 nearest by steps 2 and 3 (generatePairWiseGT's lists as far as a list goes; beyond 128 the rank of step 3 answers membership):
+   idx int32, dist binary64, host [n x m]; n - 1 < m: DGE_ERR_ARG */
+int  dge_pairwise_ground_vectors(const dge_vectors* gnd, int32_t m, int32_t* idx, double* dist);
+
+/* ------------------------------------------------------------------------------------------------
  * Ablation / test knobs of the trainer (process-wide relaxed atomics; nothing in a normal run sets them).  value < 0 puts
  * a knob back to the library's own rule.
  * ---------------------------------------------------------------------------------------------- */
