@@ -53,13 +53,15 @@ static inline int dge_dev_alloc(T** p, size_t n) {
 }
 static inline void dge_dev_free(void* p) { if (p) (void)hipFree(p); }
 
-// scratch device buffer of one call: freed on every exit path
+// a device buffer with one owner: the scratch of one call, freed on every exit path, or a member of a handle's group, moved in once it is finished
 template <typename T>
 struct dge_tmp {
     T* p = nullptr;
     dge_tmp() = default;
     dge_tmp(const dge_tmp&) = delete;
     dge_tmp& operator=(const dge_tmp&) = delete;
+    dge_tmp(dge_tmp&& o) noexcept : p(o.release()) {}
+    dge_tmp& operator=(dge_tmp&& o) noexcept { if (this != &o) { if (p) (void)hipFree(p); p = o.release(); } return *this; }
     ~dge_tmp() { if (p) (void)hipFree(p); }
     int alloc(size_t n) { if (p) { (void)hipFree(p); p = nullptr; } return dge_dev_alloc(&p, n); }
     T* release() { T* q = p; p = nullptr; return q; }
@@ -77,39 +79,68 @@ struct __attribute__((aligned(32))) dge_slot {
     uint32_t base_alias, k_alias;   // edges of nbr_alias
 };
 
+// What a graph owns on the device, in four groups.  A group frees its arrays when it goes and moves as a whole: assigning an empty one is the free, and an entry
+// that replaces a group builds the new one in a local and moves it in after the last step that can fail (graph.hip).  alloc: the arrays at their sizes, no content.
+struct dge_coo {                   // the COO staging in insertion order (allEdges, J/LayeredGraph.java:142)
+    dge_tmp<int32_t> src, dst;
+    dge_tmp<double> w;
+    int64_t n = 0, cap = 0;
+    int alloc(int64_t c) { cap = c; int rc = src.alloc((size_t)c); if (!rc) rc = dst.alloc((size_t)c); if (!rc) rc = w.alloc((size_t)c); return rc; }
+};
+struct dge_csr {                   // built: row_ptr is there (an allocation is never null, dge_dev_alloc)
+    dge_tmp<int64_t> row_ptr;      // [V + 1]
+    dge_tmp<int32_t> nbr;          // [E]
+    dge_tmp<double> w, outdeg;     // [E], [V]
+    int32_t V = 0;
+    int64_t E = 0;
+    bool built() const { return row_ptr.p != nullptr; }
+    int alloc(int32_t v, int64_t e) {
+        V = v; E = e;
+        int rc = row_ptr.alloc((size_t)v + 1); if (!rc) rc = nbr.alloc((size_t)e); if (!rc) rc = w.alloc((size_t)e); if (!rc) rc = outdeg.alloc((size_t)v);
+        return rc;
+    }
+};
+struct dge_tables {                // alias tables of n slots and the walk kernel's form of them: the edges' (n = E), the sources' (n = S)
+    dge_tmp<double> prob;
+    dge_tmp<int32_t> alias;
+    dge_tmp<dge_slot> slots;
+    int alloc(int64_t n) { int rc = prob.alloc((size_t)n); if (!rc) rc = alias.alloc((size_t)n); if (!rc) rc = slots.alloc((size_t)n); return rc; }
+};
+struct dge_sources {               // J/LayeredGraph.java:145-148
+    dge_tmp<int32_t> srcv;
+    dge_tmp<double> w;
+    dge_tables tables;
+    int64_t S = 0;
+    double weight_sum = 0.0;
+    int stream_sum = 0;            // how set_sources summed (0 running +=, 1 DoubleStream.sum())
+    bool sum_fixed = false;        // the host assigned sourceWeightSum itself (dge_graph_set_source_weight_sum)
+};
+
 struct dge_graph {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    // COO staging in insertion order (allEdges, J/LayeredGraph.java:142)
-    int64_t n_coo = 0, cap_coo = 0;
-    int32_t *d_coo_src = nullptr, *d_coo_dst = nullptr;
-    double* d_coo_w = nullptr;
+    dge_coo coo;
     int32_t max_id = -1;
-    // CSR
-    bool csr_built = false, alias_built = false;
-    int32_t V = 0;
-    int64_t E = 0;
-    int64_t* d_row_ptr = nullptr;
-    int32_t* d_nbr = nullptr;
-    double* d_w = nullptr;
-    double* d_outdeg = nullptr;
-    double* d_prob = nullptr;
-    int32_t* d_alias = nullptr;
-    dge_slot* d_slots = nullptr;
-    // sources (J/LayeredGraph.java:145-148)
-    int64_t S = 0;
-    int32_t* d_srcv = nullptr;
-    double src_weight_sum = 0.0;
-    int src_stream_sum = 0;          // how set_sources summed (0 running +=, 1 DoubleStream.sum())
-    bool src_sum_fixed = false;      // the host assigned sourceWeightSum itself (dge_graph_set_source_weight_sum)
-    double* d_src_w = nullptr;
-    double* d_src_prob = nullptr;
-    int32_t* d_src_alias = nullptr;
-    dge_slot* d_src_slots = nullptr;
+    dge_csr csr;                   // "the CSR is built" is csr.built(): no flag beside it
+    dge_tables tables;
+    dge_sources src;
+    // alias_built: the tables (tables, src.tables) are complete and made from the present CSR, outDegree, sources and weight sum.  It stays a flag
+    // (the trainer reads it by this name): dge_graph_build_alias sets it with the tables it moves in, every entry that changes one of those inputs clears it, and
+    // the CSR never goes without its tables (drop_tables).
+    bool alias_built = false;
+    void drop_tables() { tables = dge_tables{}; alias_built = false; }
     // the region ids of a graph made from .od text (od_read.hip), ascending: vertex h*R + i is region od_regions[i] in slice h
     std::vector<int64_t> od_regions;
 };
+// back to what dge_graph_create left (the device of g is current: the groups free device memory)
+static inline void dge_graph_reset(dge_graph* g) {
+    g->coo = dge_coo{}; g->csr = dge_csr{}; g->src = dge_sources{}; g->drop_tables();
+    g->max_id = -1;
+    g->od_regions.clear();
+}
+// what the builders ask of the graph they fill (od_commit.h, spatial.hip): no edges, no reserved vertices, no sources
+static inline bool dge_graph_fresh(const dge_graph* g) { return g->coo.n == 0 && g->max_id < 0 && g->src.S == 0 && !g->src.srcv.p && g->od_regions.empty(); }
 
 struct dge_walks {
     int device = 0;
@@ -175,9 +206,12 @@ int dge_flows_slot_coo(const dge_flows* f, int32_t T, int32_t mode, int32_t slot
                        dge_tmp<double>& val, int64_t* n_entries, std::vector<int64_t>& regions);
 
 int dge_graph_ensure_csr(dge_graph* g);
-// the end state of keepNearestKVertices (graph.hip): the store becomes the given CSR of n_edges edges (device arrays, taken over; g->d_outdeg already holds the
-// recomputed outDegree), the tables are void, the sources' weights are refreshed.  dge_graph_keep_top_k ends in it; spatial.hip hands its edges over through it.
-int dge_graph_adopt_pruned(dge_graph* g, int64_t* d_row_ptr, double* d_w, int32_t* d_nbr, int64_t n_edges);
+// The two ways another translation unit hands a graph its edges (graph.hip); neither can leave g half-way.
+// The edges of n_vertices vertices as COO arrays of coo.n entries: g stands where dge_graph_add_edges and dge_graph_reserve_vertices would leave it.
+void dge_graph_adopt_coo(dge_graph* g, dge_coo&& coo, int32_t n_vertices);
+// the end state of keepNearestKVertices: the store becomes the given CSR with its recomputed outDegree, the tables are void, the sources' weights are refreshed
+// (DoubleStream.sum(), no host-fixed sum).  dge_graph_keep_top_k ends in it; spatial.hip hands its edges over through it.  On error g is as it was.
+int dge_graph_adopt_pruned(dge_graph* g, dge_csr&& csr);
 // launches the strided walk kernel on `stream`; rows [row0,row0+n) of out (row length L)
 int dge_launch_walks_strided(const dge_graph* g, hipStream_t stream, int32_t* d_out, int64_t n, int32_t L,
                              int64_t seed, int64_t first_index, int32_t* d_deadend_count);

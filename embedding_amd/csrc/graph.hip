@@ -10,7 +10,7 @@
 #include <stdarg.h>
 
 #include "dge_algos.h"
-#include "dge_internal.h"
+#include "dge_device.h"
 
 // ------------------------------------------------------------------------------------------ errors
 static thread_local std::string g_last_error;
@@ -427,8 +427,6 @@ __global__ void k_position_prefix(int32_t* walks, int64_t n, int32_t L, int32_t 
 }
 
 // ------------------------------------------------------------------------------------------ host side
-static inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
 extern "C" int dge_graph_create(dge_graph** out, int device) {
     if (!out) DGE_FAIL(DGE_ERR_ARG, "dge_graph_create: null output");
     *out = nullptr;
@@ -442,28 +440,12 @@ extern "C" int dge_graph_create(dge_graph** out, int device) {
     return DGE_OK;
 }
 
-static void free_csr(dge_graph* g) {
-    dge_dev_free(g->d_row_ptr); dge_dev_free(g->d_nbr); dge_dev_free(g->d_w); dge_dev_free(g->d_outdeg);
-    dge_dev_free(g->d_prob); dge_dev_free(g->d_alias); dge_dev_free(g->d_slots);
-    g->d_row_ptr = nullptr; g->d_nbr = nullptr; g->d_w = nullptr; g->d_outdeg = nullptr;
-    g->d_prob = nullptr; g->d_alias = nullptr; g->d_slots = nullptr;
-    g->csr_built = false; g->alias_built = false;
-}
-static void free_sources(dge_graph* g) {
-    dge_dev_free(g->d_srcv); dge_dev_free(g->d_src_w); dge_dev_free(g->d_src_prob); dge_dev_free(g->d_src_alias);
-    dge_dev_free(g->d_src_slots);
-    g->d_srcv = nullptr; g->d_src_w = nullptr; g->d_src_prob = nullptr; g->d_src_alias = nullptr; g->d_src_slots = nullptr;
-    g->S = 0;
-}
-
 extern "C" void dge_graph_free(dge_graph* g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    free_csr(g); free_sources(g);
-    dge_dev_free(g->d_coo_src); dge_dev_free(g->d_coo_dst); dge_dev_free(g->d_coo_w);
     if (g->own_stream && g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
+    delete g;                                      // the groups free what they own
 }
 
 extern "C" int dge_graph_set_stream(dge_graph* g, void* hip_stream) {
@@ -476,55 +458,66 @@ extern "C" int dge_graph_set_stream(dge_graph* g, void* hip_stream) {
     return DGE_OK;
 }
 
+// Every entry below that replaces a group of g (dge_internal.h) builds the new one in a local, waits for its kernels and moves it in after the last step that can
+// fail: on an error g is as it was before the call.
 static int coo_reserve(dge_graph* g, int64_t extra) {
-    if (g->n_coo + extra <= g->cap_coo) return DGE_OK;
-    int64_t nc = (g->n_coo + extra) + (g->n_coo + extra) / 2 + 1024;
-    dge_tmp<int32_t> ns, nd; dge_tmp<double> nw;
-    int rc;
-    if ((rc = ns.alloc((size_t)nc))) return rc;
-    if ((rc = nd.alloc((size_t)nc))) return rc;
-    if ((rc = nw.alloc((size_t)nc))) return rc;
-    if (g->n_coo) {
-        DGE_HIP(hipMemcpyAsync(ns, g->d_coo_src, g->n_coo * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream));
-        DGE_HIP(hipMemcpyAsync(nd, g->d_coo_dst, g->n_coo * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream));
-        DGE_HIP(hipMemcpyAsync(nw, g->d_coo_w, g->n_coo * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
+    const dge_coo& old = g->coo;
+    if (old.n + extra <= old.cap) return DGE_OK;
+    dge_coo c;
+    c.n = old.n;
+    if (int rc = c.alloc((old.n + extra) + (old.n + extra) / 2 + 1024)) return rc;
+    if (old.n) {
+        DGE_HIP(hipMemcpyAsync(c.src.p, old.src.p, old.n * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream));
+        DGE_HIP(hipMemcpyAsync(c.dst.p, old.dst.p, old.n * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream));
+        DGE_HIP(hipMemcpyAsync(c.w.p, old.w.p, old.n * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
         DGE_HIP(hipStreamSynchronize(g->stream));
     }
-    dge_dev_free(g->d_coo_src); dge_dev_free(g->d_coo_dst); dge_dev_free(g->d_coo_w);
-    g->d_coo_src = ns.release(); g->d_coo_dst = nd.release(); g->d_coo_w = nw.release(); g->cap_coo = nc;
+    g->coo = std::move(c);
     return DGE_OK;
+}
+
+// the store was pruned (keep_top_k, the spatial graph): the CSR no longer is the staged edges', and neither edges nor vertices can join
+static bool pruned(const dge_graph* g) { return g->csr.built() && g->csr.E != g->coo.n; }
+// the staged edges or the vertex count changed: the CSR and the tables are built again on the next use
+static void drop_csr(dge_graph* g) { g->csr = dge_csr{}; g->drop_tables(); }
+
+void dge_graph_adopt_coo(dge_graph* g, dge_coo&& coo, int32_t n_vertices) {
+    g->coo = std::move(coo);
+    g->max_id = n_vertices - 1;
+    drop_csr(g);
 }
 
 static int add_edges_common(dge_graph* g, const int32_t* src, const int32_t* dst, const double* w, int64_t n, hipMemcpyKind kind) {
     if (!g || n < 0 || (n > 0 && (!src || !dst || !w))) DGE_FAIL(DGE_ERR_ARG, "dge_graph_add_edges: bad argument");
     if (n == 0) return DGE_OK;
-    if (g->csr_built && g->E != g->n_coo)
-        DGE_FAIL(DGE_ERR_STATE, "dge_graph_add_edges: edges cannot be added after keep_top_k pruned the store");
+    if (pruned(g)) DGE_FAIL(DGE_ERR_STATE, "dge_graph_add_edges: edges cannot be added after keep_top_k pruned the store");
     DGE_HIP(hipSetDevice(g->device));
     // device sources come from the caller's streams (e.g. torch's): wait for whatever produced them — this handle's
     // stream is non-blocking and would otherwise race with the producer
     if (kind == hipMemcpyDeviceToDevice) DGE_HIP(hipDeviceSynchronize());
     int rc = coo_reserve(g, n);
     if (rc) return rc;
-    DGE_HIP(hipMemcpyAsync(g->d_coo_src + g->n_coo, src, n * sizeof(int32_t), kind, g->stream));
-    DGE_HIP(hipMemcpyAsync(g->d_coo_dst + g->n_coo, dst, n * sizeof(int32_t), kind, g->stream));
-    DGE_HIP(hipMemcpyAsync(g->d_coo_w + g->n_coo, w, n * sizeof(double), kind, g->stream));
+    int32_t* const new_src = g->coo.src.p + g->coo.n;
+    int32_t* const new_dst = g->coo.dst.p + g->coo.n;
+    DGE_HIP(hipMemcpyAsync(new_src, src, n * sizeof(int32_t), kind, g->stream));
+    DGE_HIP(hipMemcpyAsync(new_dst, dst, n * sizeof(int32_t), kind, g->stream));
+    DGE_HIP(hipMemcpyAsync(g->coo.w.p + g->coo.n, w, n * sizeof(double), kind, g->stream));
     // id range check + vertex count (vertex ids are insertion ordinals: V = max id + 1)
     dge_tmp<int32_t> d_mm;
     if ((rc = d_mm.alloc(2))) return rc;
     int32_t init[2] = {-1, 0x7fffffff};
     DGE_HIP(hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, g->stream));
     unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_max_i32, dim3(blocks), dim3(256), 0, g->stream, g->d_coo_src + g->n_coo, g->d_coo_dst + g->n_coo, n, d_mm);
-    hipLaunchKernelGGL(k_min_i32_edges, dim3(blocks), dim3(256), 0, g->stream, g->d_coo_src + g->n_coo, g->d_coo_dst + g->n_coo, n, d_mm + 1);
+    hipLaunchKernelGGL(k_max_i32, dim3(blocks), dim3(256), 0, g->stream, new_src, new_dst, n, d_mm.p);
+    hipLaunchKernelGGL(k_min_i32_edges, dim3(blocks), dim3(256), 0, g->stream, new_src, new_dst, n, d_mm.p + 1);
     int32_t mm[2];
     DGE_HIP(hipMemcpyAsync(mm, d_mm, sizeof(mm), hipMemcpyDeviceToHost, g->stream));
     DGE_HIP(hipStreamSynchronize(g->stream));
     if (mm[1] < 0) DGE_FAIL(DGE_ERR_RANGE, "dge_graph_add_edges: negative vertex id %d", mm[1]);
     if (mm[0] == 0x7fffffff) DGE_FAIL(DGE_ERR_RANGE, "dge_graph_add_edges: vertex id overflow");
     g->max_id = std::max(g->max_id, mm[0]);
-    g->n_coo += n;
-    free_csr(g);
+    g->coo.n += n;
+    drop_csr(g);
     return DGE_OK;
 }
 
@@ -537,40 +530,54 @@ extern "C" int dge_graph_add_edges_device(dge_graph* g, const int32_t* src, cons
 
 // COO (insertion order) -> CSR with insertion order kept inside every vertex: stable radix sort on src
 int dge_graph_ensure_csr(dge_graph* g) {
-    if (g->csr_built) return DGE_OK;
+    if (g->csr.built()) return DGE_OK;
     DGE_HIP(hipSetDevice(g->device));
-    const int64_t E = g->n_coo;
+    const int64_t E = g->coo.n;
     const int32_t V = g->max_id + 1;
+    if (E >= (int64_t)0xFFFFFFFFLL) DGE_FAIL(DGE_ERR_ARG, "edge count %lld exceeds 2^32-1", (long long)E);
     int rc;
-    free_csr(g);
-    if ((rc = dge_dev_alloc(&g->d_row_ptr, (size_t)V + 1))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_nbr, (size_t)E))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_w, (size_t)E))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_outdeg, (size_t)V))) return rc;
+    dge_csr c;
+    if ((rc = c.alloc(V, E))) return rc;
     if (E > 0) {
-        if (E >= (int64_t)0xFFFFFFFFLL) DGE_FAIL(DGE_ERR_ARG, "edge count %lld exceeds 2^32-1", (long long)E);
-        dge_tmp<int32_t> d_keys; dge_tmp<uint32_t> d_idx, d_idx_sorted; dge_tmp<char> d_tmp;
+        dge_tmp<int32_t> d_keys; dge_tmp<uint32_t> d_idx, d_idx_sorted; dge_scratch tmp;
         if ((rc = d_keys.alloc((size_t)E))) return rc;
         if ((rc = d_idx.alloc((size_t)E))) return rc;
         if ((rc = d_idx_sorted.alloc((size_t)E))) return rc;
-        hipLaunchKernelGGL(k_iota_u32, dim3(grid_for(E, 256)), dim3(256), 0, g->stream, d_idx.p, E);
+        hipLaunchKernelGGL(k_iota_u32, dim3(dge_grid(E, 256)), dim3(256), 0, g->stream, d_idx.p, E);
         int end_bit = 1;
         while (end_bit < 31 && (1LL << end_bit) < (int64_t)V) end_bit++;
-        size_t tmp_bytes = 0;
-        DGE_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, g->d_coo_src, d_keys.p, d_idx.p, d_idx_sorted.p, E, 0, end_bit, g->stream));
-        if ((rc = d_tmp.alloc(tmp_bytes))) return rc;
-        DGE_HIP(hipcub::DeviceRadixSort::SortPairs((void*)d_tmp.p, tmp_bytes, g->d_coo_src, d_keys.p, d_idx.p, d_idx_sorted.p, E, 0, end_bit, g->stream));
-        hipLaunchKernelGGL(k_gather_edges, dim3(grid_for(E, 256)), dim3(256), 0, g->stream, d_idx_sorted.p, g->d_coo_dst, g->d_coo_w, g->d_nbr, g->d_w, E);
-        hipLaunchKernelGGL(k_row_ptr, dim3(grid_for((int64_t)V + 1, 256)), dim3(256), 0, g->stream, d_keys.p, E, V, g->d_row_ptr);
-        hipLaunchKernelGGL(k_out_degree, dim3(grid_for(V, 256)), dim3(256), 0, g->stream, g->d_row_ptr, g->d_w, V, g->d_outdeg);
+        rc = dge_two_pass(tmp, [&](void* t, size_t& bytes) {
+            return hipcub::DeviceRadixSort::SortPairs(t, bytes, g->coo.src.p, d_keys.p, d_idx.p, d_idx_sorted.p, E, 0, end_bit, g->stream); }, g->stream, false);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_gather_edges, dim3(dge_grid(E, 256)), dim3(256), 0, g->stream, d_idx_sorted.p, g->coo.dst.p, g->coo.w.p, c.nbr.p, c.w.p, E);
+        hipLaunchKernelGGL(k_row_ptr, dim3(dge_grid((int64_t)V + 1, 256)), dim3(256), 0, g->stream, d_keys.p, E, V, c.row_ptr.p);
+        hipLaunchKernelGGL(k_out_degree, dim3(dge_grid(V, 256)), dim3(256), 0, g->stream, c.row_ptr.p, c.w.p, V, c.outdeg.p);
         DGE_HIP(hipStreamSynchronize(g->stream));
     } else {
-        DGE_HIP(hipMemsetAsync(g->d_row_ptr, 0, ((size_t)V + 1) * sizeof(int64_t), g->stream));
-        if (V > 0) DGE_HIP(hipMemsetAsync(g->d_outdeg, 0, (size_t)V * sizeof(double), g->stream));   // reserved vertices of an edgeless store: outDegree 0
+        DGE_HIP(hipMemsetAsync(c.row_ptr.p, 0, ((size_t)V + 1) * sizeof(int64_t), g->stream));
+        if (V > 0) DGE_HIP(hipMemsetAsync(c.outdeg.p, 0, (size_t)V * sizeof(double), g->stream));   // reserved vertices of an edgeless store: outDegree 0
         DGE_HIP(hipStreamSynchronize(g->stream));
     }
     DGE_HIP(hipGetLastError());
-    g->V = V; g->E = E; g->csr_built = true; g->alias_built = false;
+    g->csr = std::move(c);                         // (no tables to void: they went with the CSR they were made from, drop_csr)
+    return DGE_OK;
+}
+
+// Source weights from outDegree, their sum back to the host: s.w becomes outdeg[s.srcv[.]] and s.weight_sum their sum in the given mode, which s keeps
+// (0 running +=, 1 DoubleStream.sum()).  keep_fixed: a sum the host assigned itself survives; otherwise it is replaced and no longer counts as fixed.
+// The weights are staged: on error s is as it was.  One counted wait.
+static int refresh_source_weights(hipStream_t st, dge_sources& s, const double* outdeg, int stream_sum, bool keep_fixed) {
+    int rc;
+    dge_tmp<double> w, d_sum;
+    if ((rc = w.alloc((size_t)s.S))) return rc;
+    if ((rc = d_sum.alloc(1))) return rc;
+    double sum = 0.0;
+    launch_sources(st, s.srcv.p, s.S, outdeg, w.p, stream_sum, d_sum.p);
+    DGE_HIP(hipMemcpyAsync(&sum, d_sum.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    DGE_HIP(hipStreamSynchronize(st));
+    s.w = std::move(w);
+    s.stream_sum = stream_sum ? 1 : 0;
+    if (!(keep_fixed && s.sum_fixed)) { s.weight_sum = sum; s.sum_fixed = false; }
     return DGE_OK;
 }
 
@@ -579,29 +586,24 @@ extern "C" int dge_graph_set_sources(dge_graph* g, const int32_t* v, int64_t n, 
     int rc = dge_graph_ensure_csr(g);
     if (rc) return rc;
     for (int64_t i = 0; i < n; i++)
-        if (v[i] < 0 || v[i] >= g->V) DGE_FAIL(DGE_ERR_RANGE, "dge_graph_set_sources: vertex %d is not in the graph (V=%d)", v[i], g->V);
-    free_sources(g);
-    if ((rc = dge_dev_alloc(&g->d_srcv, (size_t)n))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_src_w, (size_t)n))) return rc;
-    dge_tmp<double> d_sum;
-    if ((rc = d_sum.alloc(1))) return rc;
-    if (n) DGE_HIP(hipMemcpyAsync(g->d_srcv, v, n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
-    launch_sources(g->stream, g->d_srcv, n, g->d_outdeg, g->d_src_w, stream_sum, d_sum.p);
-    DGE_HIP(hipMemcpyAsync(&g->src_weight_sum, d_sum.p, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    DGE_HIP(hipStreamSynchronize(g->stream));
-    g->S = n;
-    g->src_stream_sum = stream_sum ? 1 : 0; g->src_sum_fixed = false;
-    g->alias_built = false;
+        if (v[i] < 0 || v[i] >= g->csr.V) DGE_FAIL(DGE_ERR_RANGE, "dge_graph_set_sources: vertex %d is not in the graph (V=%d)", v[i], g->csr.V);
+    dge_sources s;
+    s.S = n;
+    if ((rc = s.srcv.alloc((size_t)n))) return rc;
+    if (n) DGE_HIP(hipMemcpyAsync(s.srcv.p, v, n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
+    if ((rc = refresh_source_weights(g->stream, s, g->csr.outdeg.p, stream_sum, false))) return rc;
+    g->src = std::move(s);
+    g->alias_built = false;                        // (the edge tables stay: they do not depend on the sources)
     return DGE_OK;
 }
 
 extern "C" int dge_graph_reserve_vertices(dge_graph* g, int32_t n) {
     if (!g || n < 0) DGE_FAIL(DGE_ERR_ARG, "dge_graph_reserve_vertices: bad argument");
     if (n - 1 > g->max_id) {
-        if (g->csr_built && g->E != g->n_coo) DGE_FAIL(DGE_ERR_STATE, "dge_graph_reserve_vertices: the store was pruned by keep_top_k");
+        if (pruned(g)) DGE_FAIL(DGE_ERR_STATE, "dge_graph_reserve_vertices: the store was pruned by keep_top_k");
         DGE_HIP(hipSetDevice(g->device));
         g->max_id = n - 1;
-        free_csr(g);
+        drop_csr(g);
     }
     return DGE_OK;
 }
@@ -612,18 +614,11 @@ extern "C" int dge_graph_set_out_degree(dge_graph* g, const double* out_degree, 
     if (!g || !out_degree || n < 0) DGE_FAIL(DGE_ERR_ARG, "dge_graph_set_out_degree: bad argument");
     int rc = dge_graph_ensure_csr(g);
     if (rc) return rc;
-    if (n != g->V) DGE_FAIL(DGE_ERR_ARG, "dge_graph_set_out_degree: %d values for %d vertices", n, g->V);
-    if (n) DGE_HIP(hipMemcpyAsync(g->d_outdeg, out_degree, (size_t)n * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    if (n != g->csr.V) DGE_FAIL(DGE_ERR_ARG, "dge_graph_set_out_degree: %d values for %d vertices", n, g->csr.V);
+    if (n) DGE_HIP(hipMemcpyAsync(g->csr.outdeg.p, out_degree, (size_t)n * sizeof(double), hipMemcpyHostToDevice, g->stream));
     g->alias_built = false;
-    if (g->S > 0) {              // source weights are outDegree values: refresh them (and their sum, unless the host fixed it)
-        dge_tmp<double> d_sum;
-        if ((rc = d_sum.alloc(1))) return rc;
-        double sum = 0.0;
-        launch_sources(g->stream, g->d_srcv, g->S, g->d_outdeg, g->d_src_w, g->src_stream_sum, d_sum.p);
-        DGE_HIP(hipMemcpyAsync(&sum, d_sum.p, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-        DGE_HIP(hipStreamSynchronize(g->stream));
-        if (!g->src_sum_fixed) g->src_weight_sum = sum;
-    }
+    // source weights are outDegree values: refresh them (and their sum, unless the host fixed it); its wait covers the copy above
+    if (g->src.S > 0) return refresh_source_weights(g->stream, g->src, g->csr.outdeg.p, g->src.stream_sum, true);
     DGE_HIP(hipStreamSynchronize(g->stream));
     return DGE_OK;
 }
@@ -631,7 +626,7 @@ extern "C" int dge_graph_set_out_degree(dge_graph* g, const double* out_degree, 
 // LayeredGraph.sourceWeightSum is a protected field that subclasses assign (J/SpatialGraph.java:57,83)
 extern "C" int dge_graph_set_source_weight_sum(dge_graph* g, double sum) {
     if (!g) DGE_FAIL(DGE_ERR_ARG, "dge_graph_set_source_weight_sum: null graph");
-    g->src_weight_sum = sum; g->src_sum_fixed = true; g->alias_built = false;
+    g->src.weight_sum = sum; g->src.sum_fixed = true; g->alias_built = false;
     return DGE_OK;
 }
 
@@ -641,18 +636,19 @@ extern "C" int dge_graph_get_csr(const dge_graph* gc, int64_t* row_ptr, int32_t*
     if (!g) DGE_FAIL(DGE_ERR_ARG, "dge_graph_get_csr: null graph");
     int rc = dge_graph_ensure_csr(g);
     if (rc) return rc;
-    if ((row_ptr || out_degree) && cap_vertices < g->V) DGE_FAIL(DGE_ERR_CAP, "dge_graph_get_csr: %d vertices exceed cap %d", g->V, cap_vertices);
-    if ((nbr || weight || prob || alias) && cap_edges < g->E) DGE_FAIL(DGE_ERR_CAP, "dge_graph_get_csr: %lld edges exceed cap %lld", (long long)g->E, (long long)cap_edges);
+    const dge_csr& c = g->csr;
+    if ((row_ptr || out_degree) && cap_vertices < c.V) DGE_FAIL(DGE_ERR_CAP, "dge_graph_get_csr: %d vertices exceed cap %d", c.V, cap_vertices);
+    if ((nbr || weight || prob || alias) && cap_edges < c.E) DGE_FAIL(DGE_ERR_CAP, "dge_graph_get_csr: %lld edges exceed cap %lld", (long long)c.E, (long long)cap_edges);
     if ((prob || alias) && !g->alias_built) DGE_FAIL(DGE_ERR_STATE, "dge_graph_get_csr: alias tables not built");
     DGE_HIP(hipSetDevice(g->device));
     DGE_HIP(hipStreamSynchronize(g->stream));
-    if (row_ptr) DGE_HIP(hipMemcpy(row_ptr, g->d_row_ptr, ((size_t)g->V + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (out_degree && g->V) DGE_HIP(hipMemcpy(out_degree, g->d_outdeg, (size_t)g->V * sizeof(double), hipMemcpyDeviceToHost));
-    if (g->E) {
-        if (nbr) DGE_HIP(hipMemcpy(nbr, g->d_nbr, (size_t)g->E * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (weight) DGE_HIP(hipMemcpy(weight, g->d_w, (size_t)g->E * sizeof(double), hipMemcpyDeviceToHost));
-        if (prob) DGE_HIP(hipMemcpy(prob, g->d_prob, (size_t)g->E * sizeof(double), hipMemcpyDeviceToHost));
-        if (alias) DGE_HIP(hipMemcpy(alias, g->d_alias, (size_t)g->E * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (row_ptr) DGE_HIP(hipMemcpy(row_ptr, c.row_ptr.p, ((size_t)c.V + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (out_degree && c.V) DGE_HIP(hipMemcpy(out_degree, c.outdeg.p, (size_t)c.V * sizeof(double), hipMemcpyDeviceToHost));
+    if (c.E) {
+        if (nbr) DGE_HIP(hipMemcpy(nbr, c.nbr.p, (size_t)c.E * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (weight) DGE_HIP(hipMemcpy(weight, c.w.p, (size_t)c.E * sizeof(double), hipMemcpyDeviceToHost));
+        if (prob) DGE_HIP(hipMemcpy(prob, g->tables.prob.p, (size_t)c.E * sizeof(double), hipMemcpyDeviceToHost));
+        if (alias) DGE_HIP(hipMemcpy(alias, g->tables.alias.p, (size_t)c.E * sizeof(int32_t), hipMemcpyDeviceToHost));
     }
     return DGE_OK;
 }
@@ -661,54 +657,41 @@ extern "C" int dge_graph_keep_top_k(dge_graph* g, int32_t k) {
     if (!g || k < 0) DGE_FAIL(DGE_ERR_ARG, "dge_graph_keep_top_k: bad argument");
     int rc = dge_graph_ensure_csr(g);
     if (rc) return rc;
-    const int32_t V = g->V; const int64_t E = g->E;
+    const dge_csr& c = g->csr;
+    const int32_t V = c.V; const int64_t E = c.E;
     if (V == 0) return DGE_OK;
     dge_tmp<unsigned long long> d_min;
     if ((rc = d_min.alloc(1))) return rc;
-    DGE_HIP(hipMemsetAsync(d_min, 0xFF, sizeof(unsigned long long), g->stream));
-    hipLaunchKernelGGL(k_min_degree, dim3(std::min<unsigned>(grid_for(V, 256), 2048u)), dim3(256), 0, g->stream, g->d_row_ptr, V, d_min.p);
+    DGE_HIP(hipMemsetAsync(d_min.p, 0xFF, sizeof(unsigned long long), g->stream));
+    hipLaunchKernelGGL(k_min_degree, dim3(std::min<unsigned>(dge_grid(V, 256), 2048u)), dim3(256), 0, g->stream, c.row_ptr.p, V, d_min.p);
     unsigned long long mind = 0;
     DGE_HIP(hipMemcpyAsync(&mind, d_min.p, sizeof(mind), hipMemcpyDeviceToHost, g->stream));
     DGE_HIP(hipStreamSynchronize(g->stream));
     if (mind < (unsigned long long)k)
         DGE_FAIL(DGE_ERR_TOPK, "keepNearestKVertices(%d): a vertex has only %llu out-edges (the reference throws IndexOutOfBoundsException)", k, mind);
-    dge_tmp<double> d_ws; dge_tmp<int32_t> d_ns; dge_tmp<char> d_tmp;
+    dge_tmp<double> d_ws; dge_tmp<int32_t> d_ns; dge_scratch tmp;
     if ((rc = d_ws.alloc((size_t)E))) return rc;
     if ((rc = d_ns.alloc((size_t)E))) return rc;
-    size_t tmp_bytes = 0;
-    DGE_HIP(hipcub::DeviceSegmentedRadixSort::SortPairsDescending(nullptr, tmp_bytes, g->d_w, d_ws.p, g->d_nbr, d_ns.p, E, V,
-                                                                  g->d_row_ptr, g->d_row_ptr + 1, 0, 64, g->stream));
-    if ((rc = d_tmp.alloc(tmp_bytes))) return rc;
-    DGE_HIP(hipcub::DeviceSegmentedRadixSort::SortPairsDescending((void*)d_tmp.p, tmp_bytes, g->d_w, d_ws.p, g->d_nbr, d_ns.p, E, V,
-                                                                  g->d_row_ptr, g->d_row_ptr + 1, 0, 64, g->stream));
-    dge_tmp<int64_t> nrp; dge_tmp<double> nw; dge_tmp<int32_t> nn;
-    const int64_t NE = (int64_t)V * k;
-    if ((rc = nrp.alloc((size_t)V + 1))) return rc;
-    if ((rc = nw.alloc((size_t)NE))) return rc;
-    if ((rc = nn.alloc((size_t)NE))) return rc;
-    hipLaunchKernelGGL(k_topk_compact, dim3(grid_for((int64_t)V + 1, 256)), dim3(256), 0, g->stream, g->d_row_ptr, d_ws.p, d_ns.p, V, k,
-                       nrp.p, nw.p, nn.p, g->d_outdeg);
+    rc = dge_two_pass(tmp, [&](void* t, size_t& bytes) {
+        return hipcub::DeviceSegmentedRadixSort::SortPairsDescending(t, bytes, c.w.p, d_ws.p, c.nbr.p, d_ns.p, E, V, c.row_ptr.p, c.row_ptr.p + 1, 0, 64, g->stream); },
+        g->stream, false);
+    if (rc) return rc;
+    dge_csr top;
+    if ((rc = top.alloc(V, (int64_t)V * k))) return rc;
+    hipLaunchKernelGGL(k_topk_compact, dim3(dge_grid((int64_t)V + 1, 256)), dim3(256), 0, g->stream, c.row_ptr.p, d_ws.p, d_ns.p, V, k,
+                       top.row_ptr.p, top.w.p, top.nbr.p, top.outdeg.p);
     DGE_HIP(hipStreamSynchronize(g->stream));
     DGE_HIP(hipGetLastError());
-    return dge_graph_adopt_pruned(g, nrp.release(), nw.release(), nn.release(), NE);
+    return dge_graph_adopt_pruned(g, std::move(top));
 }
 
-int dge_graph_adopt_pruned(dge_graph* g, int64_t* d_row_ptr, double* d_w, int32_t* d_nbr, int64_t n_edges) {
-    dge_dev_free(g->d_row_ptr); dge_dev_free(g->d_w); dge_dev_free(g->d_nbr);
-    dge_dev_free(g->d_prob); dge_dev_free(g->d_alias); dge_dev_free(g->d_slots);
-    g->d_prob = nullptr; g->d_alias = nullptr; g->d_slots = nullptr;
-    g->d_row_ptr = d_row_ptr; g->d_w = d_w; g->d_nbr = d_nbr; g->E = n_edges;
-    g->alias_built = false;
+int dge_graph_adopt_pruned(dge_graph* g, dge_csr&& csr) {
     // source weights depend on outDegree: refresh them if sources were already set
-    if (g->S > 0) {
-        int rc;
-        dge_tmp<double> d_sum;
-        if ((rc = d_sum.alloc(1))) return rc;
-        launch_sources(g->stream, g->d_srcv, g->S, g->d_outdeg, g->d_src_w, 1, d_sum.p);
-        DGE_HIP(hipMemcpyAsync(&g->src_weight_sum, d_sum.p, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-        DGE_HIP(hipStreamSynchronize(g->stream));
-        g->src_stream_sum = 1; g->src_sum_fixed = false;
-    }
+    if (g->src.S > 0)
+        if (int rc = refresh_source_weights(g->stream, g->src, csr.outdeg.p, 1, false)) return rc;
+    g->csr = std::move(csr);
+    g->max_id = g->csr.V - 1;
+    g->drop_tables();
     return DGE_OK;
 }
 
@@ -716,17 +699,11 @@ extern "C" int dge_graph_build_alias(dge_graph* g, int exact) {
     if (!g) DGE_FAIL(DGE_ERR_ARG, "dge_graph_build_alias: null graph");
     int rc = dge_graph_ensure_csr(g);
     if (rc) return rc;
-    const int32_t V = g->V; const int64_t E = g->E; const int64_t S = g->S;
-    dge_dev_free(g->d_prob); dge_dev_free(g->d_alias); dge_dev_free(g->d_slots);
-    dge_dev_free(g->d_src_prob); dge_dev_free(g->d_src_alias); dge_dev_free(g->d_src_slots);
-    g->d_prob = nullptr; g->d_alias = nullptr; g->d_slots = nullptr;
-    g->d_src_prob = nullptr; g->d_src_alias = nullptr; g->d_src_slots = nullptr;
-    if ((rc = dge_dev_alloc(&g->d_prob, (size_t)E))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_alias, (size_t)E))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_slots, (size_t)E))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_src_prob, (size_t)S))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_src_alias, (size_t)S))) return rc;
-    if ((rc = dge_dev_alloc(&g->d_src_slots, (size_t)S))) return rc;
+    const dge_csr& c = g->csr;
+    const int32_t V = c.V; const int64_t E = c.E; const int64_t S = g->src.S;
+    dge_tables t, st;                              // the edges', the sources'
+    if ((rc = t.alloc(E))) return rc;
+    if ((rc = st.alloc(S))) return rc;
     dge_tmp<uint64_t> d_bs; dge_tmp<int32_t> d_vs;
     if (exact) {
         size_t words = (size_t)std::max<int64_t>(2 * (E / 32 + 6 * (int64_t)V) + 64, 2 * dge_bs_words(S) + 64);
@@ -736,62 +713,64 @@ extern "C" int dge_graph_build_alias(dge_graph* g, int exact) {
     }
     if (V > 0) {
         const int64_t hub_min = exact ? 0 : ALIAS_WAVE_MIN;
-        hipLaunchKernelGGL(k_alias_vertices, dim3(grid_for(V, 64)), dim3(64), 0, g->stream, V, g->d_row_ptr, g->d_w,
-                           g->d_outdeg, g->d_prob, g->d_alias, exact, d_bs.p, d_vs.p, hub_min);
+        hipLaunchKernelGGL(k_alias_vertices, dim3(dge_grid(V, 64)), dim3(64), 0, g->stream, V, c.row_ptr.p, c.w.p,
+                           c.outdeg.p, t.prob.p, t.alias.p, exact, d_bs.p, d_vs.p, hub_min);
         if (hub_min > 0 && E >= hub_min) {
             const int64_t max_hubs = E / hub_min;
             dge_tmp<int32_t> d_hubs;
             if ((rc = d_hubs.alloc((size_t)max_hubs + 1))) return rc;
             int32_t n_hubs = 0;
             DGE_HIP(hipMemsetAsync(d_hubs.p + max_hubs, 0, sizeof(int32_t), g->stream));
-            hipLaunchKernelGGL(k_hub_list, dim3(grid_for(V, 256)), dim3(256), 0, g->stream, V, g->d_row_ptr, hub_min, d_hubs.p, d_hubs.p + max_hubs);
+            hipLaunchKernelGGL(k_hub_list, dim3(dge_grid(V, 256)), dim3(256), 0, g->stream, V, c.row_ptr.p, hub_min, d_hubs.p, d_hubs.p + max_hubs);
             DGE_HIP(hipMemcpyAsync(&n_hubs, d_hubs.p + max_hubs, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
             DGE_HIP(hipStreamSynchronize(g->stream));
             if (n_hubs > 0)
-                hipLaunchKernelGGL(k_alias_hubs, dim3((unsigned)n_hubs), dim3(64), 0, g->stream, d_hubs.p, g->d_row_ptr, g->d_w, g->d_outdeg, g->d_prob,
-                                   g->d_alias, d_vs.p);
+                hipLaunchKernelGGL(k_alias_hubs, dim3((unsigned)n_hubs), dim3(64), 0, g->stream, d_hubs.p, c.row_ptr.p, c.w.p, c.outdeg.p, t.prob.p,
+                                   t.alias.p, d_vs.p);
             DGE_HIP(hipStreamSynchronize(g->stream));
         }
     }
     if (S > 0)
-        hipLaunchKernelGGL(k_alias_sources, dim3(1), dim3(64), 0, g->stream, S, g->d_src_w, g->src_weight_sum,
-                           g->d_src_prob, g->d_src_alias, exact, d_bs.p, d_vs.p);
+        hipLaunchKernelGGL(k_alias_sources, dim3(1), dim3(64), 0, g->stream, S, g->src.w.p, g->src.weight_sum,
+                           st.prob.p, st.alias.p, exact, d_bs.p, d_vs.p);
     if (E > 0) {
         // the table an edge slot belongs to: the vertices mark their first slot, a running maximum carries the mark along the row
-        dge_tmp<int32_t> d_owner_own; dge_tmp<char> d_tmp;
+        dge_tmp<int32_t> d_owner_own;
         int32_t* d_owner = d_vs.p;                                        // (Vose order: the stacks are done with once the stream gets here — E + 1 ints)
         if (!d_owner) { if ((rc = d_owner_own.alloc((size_t)E))) return rc; d_owner = d_owner_own.p; }
         DGE_HIP(hipMemsetAsync(d_owner, 0, (size_t)E * sizeof(int32_t), g->stream));
-        hipLaunchKernelGGL(k_owner_mark, dim3(grid_for(V, 256)), dim3(256), 0, g->stream, V, g->d_row_ptr, d_owner);
+        hipLaunchKernelGGL(k_owner_mark, dim3(dge_grid(V, 256)), dim3(256), 0, g->stream, V, c.row_ptr.p, d_owner);
+        dge_scratch tmp;                                                  // the first piece's, with slack: the later pieces, none longer, run in it too
+        auto tmp_once = [&](size_t bytes, void** p) -> int { if (tmp.t.p) { *p = tmp.t.p; return DGE_OK; } return tmp(bytes + 256, p); };
         for (int64_t e0 = 0; e0 < E; e0 += (1ll << 30)) {                 // (the scan counts in 32 bits; a later piece starts from its predecessor's last mark)
             const int64_t ne = std::min<int64_t>(E - e0, 1ll << 30);
             const int64_t lo = e0 > 0 ? e0 - 1 : 0;
-            size_t tb = 0;
-            DGE_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb, d_owner + lo, d_owner + lo, MaxI32(), (int)(e0 + ne - lo), g->stream));
-            if (!d_tmp.p && (rc = d_tmp.alloc(tb + 256))) return rc;
-            DGE_HIP(hipcub::DeviceScan::InclusiveScan((void*)d_tmp.p, tb, d_owner + lo, d_owner + lo, MaxI32(), (int)(e0 + ne - lo), g->stream));
+            rc = dge_two_pass(tmp_once, [&](void* s, size_t& bytes) {
+                return hipcub::DeviceScan::InclusiveScan(s, bytes, d_owner + lo, d_owner + lo, MaxI32(), (int)(e0 + ne - lo), g->stream); }, g->stream, false);
+            if (rc) return rc;
         }
-        hipLaunchKernelGGL(k_fill_slots, dim3(grid_for(E, 256)), dim3(256), 0, g->stream, E, (const int32_t*)d_owner, g->d_row_ptr, g->d_prob, g->d_alias,
-                           g->d_nbr, g->d_slots);
+        hipLaunchKernelGGL(k_fill_slots, dim3(dge_grid(E, 256)), dim3(256), 0, g->stream, E, (const int32_t*)d_owner, c.row_ptr.p, t.prob.p, t.alias.p,
+                           c.nbr.p, t.slots.p);
         DGE_HIP(hipStreamSynchronize(g->stream));
     }
     if (S > 0)
-        hipLaunchKernelGGL(k_fill_slots, dim3(grid_for(S, 256)), dim3(256), 0, g->stream, S, (const int32_t*)nullptr, g->d_row_ptr, g->d_src_prob,
-                           g->d_src_alias, g->d_srcv, g->d_src_slots);
+        hipLaunchKernelGGL(k_fill_slots, dim3(dge_grid(S, 256)), dim3(256), 0, g->stream, S, (const int32_t*)nullptr, c.row_ptr.p, st.prob.p,
+                           st.alias.p, g->src.srcv.p, st.slots.p);
     DGE_HIP(hipStreamSynchronize(g->stream));
     DGE_HIP(hipGetLastError());
+    g->tables = std::move(t); g->src.tables = std::move(st);
     g->alias_built = true;
     return DGE_OK;
 }
 
 extern "C" int dge_graph_num_vertices(const dge_graph* g, int32_t* n) {
     if (!g || !n) DGE_FAIL(DGE_ERR_ARG, "dge_graph_num_vertices: bad argument");
-    *n = g->csr_built ? g->V : g->max_id + 1;
+    *n = g->csr.built() ? g->csr.V : g->max_id + 1;
     return DGE_OK;
 }
 extern "C" int dge_graph_num_edges(const dge_graph* g, int64_t* n) {
     if (!g || !n) DGE_FAIL(DGE_ERR_ARG, "dge_graph_num_edges: bad argument");
-    *n = g->csr_built ? g->E : g->n_coo;
+    *n = g->csr.built() ? g->csr.E : g->coo.n;
     return DGE_OK;
 }
 
@@ -801,54 +780,54 @@ extern "C" int dge_graph_get_alias(const dge_graph* gc, int32_t v, double* prob,
     if (!g) DGE_FAIL(DGE_ERR_ARG, "dge_graph_get_alias: null graph");
     int rc = dge_graph_ensure_csr(g);
     if (rc) return rc;
-    if (v < 0 || v >= g->V) DGE_FAIL(DGE_ERR_RANGE, "dge_graph_get_alias: vertex %d not in graph (V=%d)", v, g->V);
+    if (v < 0 || v >= g->csr.V) DGE_FAIL(DGE_ERR_RANGE, "dge_graph_get_alias: vertex %d not in graph (V=%d)", v, g->csr.V);
     DGE_HIP(hipSetDevice(g->device));
     int64_t rp[2];
-    DGE_HIP(hipMemcpy(rp, g->d_row_ptr + v, sizeof(rp), hipMemcpyDeviceToHost));
+    DGE_HIP(hipMemcpy(rp, g->csr.row_ptr.p + v, sizeof(rp), hipMemcpyDeviceToHost));
     int64_t d = rp[1] - rp[0];
     if (k) *k = (int32_t)d;
-    if (out_degree) DGE_HIP(hipMemcpy(out_degree, g->d_outdeg + v, sizeof(double), hipMemcpyDeviceToHost));
+    if (out_degree) DGE_HIP(hipMemcpy(out_degree, g->csr.outdeg.p + v, sizeof(double), hipMemcpyDeviceToHost));
     if (d > cap) {
         if (prob || alias || nbr || weight) DGE_FAIL(DGE_ERR_CAP, "dge_graph_get_alias: degree %lld exceeds cap %d", (long long)d, cap);
         return DGE_OK;
     }
     if (d == 0) return DGE_OK;
     if ((prob || alias) && !g->alias_built) DGE_FAIL(DGE_ERR_STATE, "dge_graph_get_alias: alias tables not built");
-    if (prob) DGE_HIP(hipMemcpy(prob, g->d_prob + rp[0], d * sizeof(double), hipMemcpyDeviceToHost));
-    if (alias) DGE_HIP(hipMemcpy(alias, g->d_alias + rp[0], d * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (nbr) DGE_HIP(hipMemcpy(nbr, g->d_nbr + rp[0], d * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (weight) DGE_HIP(hipMemcpy(weight, g->d_w + rp[0], d * sizeof(double), hipMemcpyDeviceToHost));
+    if (prob) DGE_HIP(hipMemcpy(prob, g->tables.prob.p + rp[0], d * sizeof(double), hipMemcpyDeviceToHost));
+    if (alias) DGE_HIP(hipMemcpy(alias, g->tables.alias.p + rp[0], d * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (nbr) DGE_HIP(hipMemcpy(nbr, g->csr.nbr.p + rp[0], d * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (weight) DGE_HIP(hipMemcpy(weight, g->csr.w.p + rp[0], d * sizeof(double), hipMemcpyDeviceToHost));
     return DGE_OK;
 }
 
 extern "C" int dge_graph_get_source_alias(const dge_graph* g, double* prob, int32_t* alias, int32_t* src, int32_t cap, int32_t* k,
                                           double* weight_sum) {
     if (!g) DGE_FAIL(DGE_ERR_ARG, "dge_graph_get_source_alias: null graph");
-    if (k) *k = (int32_t)g->S;
-    if (weight_sum) *weight_sum = g->src_weight_sum;
-    if (g->S > cap) {
-        if (prob || alias || src) DGE_FAIL(DGE_ERR_CAP, "dge_graph_get_source_alias: %lld sources exceed cap %d", (long long)g->S, cap);
+    if (k) *k = (int32_t)g->src.S;
+    if (weight_sum) *weight_sum = g->src.weight_sum;
+    if (g->src.S > cap) {
+        if (prob || alias || src) DGE_FAIL(DGE_ERR_CAP, "dge_graph_get_source_alias: %lld sources exceed cap %d", (long long)g->src.S, cap);
         return DGE_OK;
     }
-    if (g->S == 0) return DGE_OK;
+    if (g->src.S == 0) return DGE_OK;
     DGE_HIP(hipSetDevice(g->device));
     if ((prob || alias) && !g->alias_built) DGE_FAIL(DGE_ERR_STATE, "dge_graph_get_source_alias: alias tables not built");
-    if (prob) DGE_HIP(hipMemcpy(prob, g->d_src_prob, g->S * sizeof(double), hipMemcpyDeviceToHost));
-    if (alias) DGE_HIP(hipMemcpy(alias, g->d_src_alias, g->S * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (src) DGE_HIP(hipMemcpy(src, g->d_srcv, g->S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (prob) DGE_HIP(hipMemcpy(prob, g->src.tables.prob.p, g->src.S * sizeof(double), hipMemcpyDeviceToHost));
+    if (alias) DGE_HIP(hipMemcpy(alias, g->src.tables.alias.p, g->src.S * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (src) DGE_HIP(hipMemcpy(src, g->src.srcv.p, g->src.S * sizeof(int32_t), hipMemcpyDeviceToHost));
     return DGE_OK;
 }
 
 extern "C" int dge_graph_sample_next(const dge_graph* g, int32_t v, double x, int32_t* next) {
     if (!g || !next) DGE_FAIL(DGE_ERR_ARG, "dge_graph_sample_next: bad argument");
     if (!g->alias_built) DGE_FAIL(DGE_ERR_STATE, "dge_graph_sample_next: call dge_graph_build_alias first");
-    if (v < 0 || v >= g->V) DGE_FAIL(DGE_ERR_RANGE, "dge_graph_sample_next: vertex %d not in graph (V=%d)", v, g->V);
+    if (v < 0 || v >= g->csr.V) DGE_FAIL(DGE_ERR_RANGE, "dge_graph_sample_next: vertex %d not in graph (V=%d)", v, g->csr.V);
     if (!(x >= 0.0 && x < 1.0)) DGE_FAIL(DGE_ERR_ARG, "dge_graph_sample_next: x must be in [0,1)");
     DGE_HIP(hipSetDevice(g->device));
     dge_tmp<int32_t> d_out;
     int rc = d_out.alloc(1);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_sample_next, dim3(1), dim3(64), 0, g->stream, g->d_row_ptr, g->d_slots, v, x, d_out.p);
+    hipLaunchKernelGGL(k_sample_next, dim3(1), dim3(64), 0, g->stream, g->csr.row_ptr.p, g->tables.slots.p, v, x, d_out.p);
     DGE_HIP(hipMemcpyAsync(next, d_out.p, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     DGE_HIP(hipStreamSynchronize(g->stream));
     return DGE_OK;
@@ -870,8 +849,8 @@ int dge_launch_walks_strided(const dge_graph* g, hipStream_t stream, int32_t* d_
     if (rc) return rc;
     if (n == 0) return DGE_OK;
     size_t lds = (size_t)WALK_BLOCK * (size_t)(L | 1) * sizeof(int32_t);
-    hipLaunchKernelGGL(k_walks, dim3(grid_for(n, WALK_BLOCK)), dim3(WALK_BLOCK), lds, stream, g->d_row_ptr, g->d_slots, g->d_src_slots,
-                       g->S, d_out, n, L, dge_jr_scramble(seed), first_index * (int64_t)L, (int64_t)L, (const int64_t*)nullptr, (uint8_t*)nullptr, d_deadend_count);
+    hipLaunchKernelGGL(k_walks, dim3(dge_grid(n, WALK_BLOCK)), dim3(WALK_BLOCK), lds, stream, g->csr.row_ptr.p, g->tables.slots.p, g->src.tables.slots.p,
+                       g->src.S, d_out, n, L, dge_jr_scramble(seed), first_index * (int64_t)L, (int64_t)L, (const int64_t*)nullptr, (uint8_t*)nullptr, d_deadend_count);
     DGE_HIP(hipGetLastError());
     return DGE_OK;
 }
@@ -909,13 +888,13 @@ static int sample_walks_impl(const dge_graph* g, int64_t n_walks, int32_t max_le
     if (dead == 0) { if (draws_consumed) *draws_consumed = n_walks * (int64_t)max_len; return DGE_OK; }
     // some walk dead-ended (or the stream offset is unaligned): draw counts are data dependent
     int64_t draws = 0;
-    if (g->S == 0) {                  // no source: every walk is empty and consumes nothing
+    if (g->src.S == 0) {                  // no source: every walk is empty and consumes nothing
         DGE_HIP(hipMemsetAsync(d_out, 0xFF, (size_t)(n_walks * max_len) * sizeof(int32_t), g->stream));
         DGE_HIP(hipStreamSynchronize(g->stream));
     } else if (n_walks < 2048) {      // short corpora: one lane chains the walks
         dge_tmp<int64_t> d_draws;
         if ((rc = d_draws.alloc(1))) return rc;
-        hipLaunchKernelGGL(k_walks_sequential, dim3(1), dim3(64), 0, g->stream, g->d_row_ptr, g->d_slots, g->d_src_slots, g->S, d_out,
+        hipLaunchKernelGGL(k_walks_sequential, dim3(1), dim3(64), 0, g->stream, g->csr.row_ptr.p, g->tables.slots.p, g->src.tables.slots.p, g->src.S, d_out,
                            n_walks, max_len, dge_jr_scramble(seed), first_index, d_draws.p);
         DGE_HIP(hipMemcpyAsync(&draws, d_draws.p, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
         DGE_HIP(hipStreamSynchronize(g->stream));
@@ -932,12 +911,12 @@ static int sample_walks_impl(const dge_graph* g, int64_t n_walks, int32_t max_le
         if ((rc = d_starts.alloc((size_t)n_walks))) return rc;
         if ((rc = d_draws.alloc(1))) return rc;
         const size_t lds = (size_t)WALK_BLOCK * (size_t)(max_len | 1) * sizeof(int32_t);
-        hipLaunchKernelGGL(k_walks, dim3(grid_for(N, WALK_BLOCK)), dim3(WALK_BLOCK), lds, g->stream, g->d_row_ptr, g->d_slots, g->d_src_slots, g->S,
+        hipLaunchKernelGGL(k_walks, dim3(dge_grid(N, WALK_BLOCK)), dim3(WALK_BLOCK), lds, g->stream, g->csr.row_ptr.p, g->tables.slots.p, g->src.tables.slots.p, g->src.S,
                            (int32_t*)nullptr, N, max_len, dge_jr_scramble(seed), first_index, (int64_t)1, (const int64_t*)nullptr, d_lens.p, (int32_t*)nullptr);
-        hipLaunchKernelGGL(k_seq_block_exits, dim3(grid_for(n_blocks * max_len, 256)), dim3(256), 0, g->stream, d_lens.p, N, max_len, n_blocks, d_exit.p, d_hops.p);
+        hipLaunchKernelGGL(k_seq_block_exits, dim3(dge_grid(n_blocks * max_len, 256)), dim3(256), 0, g->stream, d_lens.p, N, max_len, n_blocks, d_exit.p, d_hops.p);
         hipLaunchKernelGGL(k_seq_chain, dim3(1), dim3(64), 0, g->stream, d_exit.p, d_hops.p, max_len, n_blocks, d_se.p, d_si.p);
-        hipLaunchKernelGGL(k_seq_starts, dim3(grid_for(n_blocks, 256)), dim3(256), 0, g->stream, d_lens.p, N, n_blocks, d_se.p, d_si.p, first_index, n_walks, d_starts.p, d_draws.p);
-        hipLaunchKernelGGL(k_walks, dim3(grid_for(n_walks, WALK_BLOCK)), dim3(WALK_BLOCK), lds, g->stream, g->d_row_ptr, g->d_slots, g->d_src_slots, g->S,
+        hipLaunchKernelGGL(k_seq_starts, dim3(dge_grid(n_blocks, 256)), dim3(256), 0, g->stream, d_lens.p, N, n_blocks, d_se.p, d_si.p, first_index, n_walks, d_starts.p, d_draws.p);
+        hipLaunchKernelGGL(k_walks, dim3(dge_grid(n_walks, WALK_BLOCK)), dim3(WALK_BLOCK), lds, g->stream, g->csr.row_ptr.p, g->tables.slots.p, g->src.tables.slots.p, g->src.S,
                            d_out, n_walks, max_len, dge_jr_scramble(seed), (int64_t)0, (int64_t)0, (const int64_t*)d_starts.p, (uint8_t*)nullptr, (int32_t*)nullptr);
         DGE_HIP(hipMemcpyAsync(&draws, d_draws.p, sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
         DGE_HIP(hipStreamSynchronize(g->stream));
@@ -1023,7 +1002,7 @@ extern "C" int dge_walks_add_position_prefix(dge_walks* w, int32_t region_count)
     if ((int64_t)region_count * w->L > 0x7fffffffLL) DGE_FAIL(DGE_ERR_RANGE, "position prefix overflows int32 ids");
     DGE_HIP(hipSetDevice(w->device));
     w->gen = dge_next_generation();
-    if (w->n) hipLaunchKernelGGL(k_position_prefix, dim3(grid_for(w->n * w->L, 256)), dim3(256), 0, 0, w->d, w->n, w->L, region_count);
+    if (w->n) hipLaunchKernelGGL(k_position_prefix, dim3(dge_grid(w->n * w->L, 256)), dim3(256), 0, 0, w->d, w->n, w->L, region_count);
     DGE_HIP(hipDeviceSynchronize());
     return DGE_OK;
 }

@@ -51,21 +51,6 @@ static __global__ void __launch_bounds__(SEQ_BLOCK) k_od_sources(const int64_t* 
 
 namespace {
 
-bool od_fresh(const dge_graph* g) { return g->n_coo == 0 && g->max_id < 0 && g->S == 0 && !g->d_srcv && g->od_regions.empty(); }
-
-// back to what dge_graph_create left: everything this call put into g goes
-void od_reset(dge_graph* g) {
-    void* mine[] = {g->d_coo_src, g->d_coo_dst, g->d_coo_w, g->d_row_ptr, g->d_nbr, g->d_w, g->d_outdeg, g->d_prob, g->d_alias, g->d_slots,
-                    g->d_srcv, g->d_src_w, g->d_src_prob, g->d_src_alias, g->d_src_slots};
-    for (void* p : mine) dge_dev_free(p);
-    g->d_coo_src = g->d_coo_dst = nullptr; g->d_coo_w = nullptr; g->n_coo = g->cap_coo = 0; g->max_id = -1;
-    g->d_row_ptr = nullptr; g->d_nbr = nullptr; g->d_w = nullptr; g->d_outdeg = nullptr; g->d_prob = nullptr; g->d_alias = nullptr; g->d_slots = nullptr;
-    g->csr_built = g->alias_built = false; g->V = 0; g->E = 0;
-    g->d_srcv = nullptr; g->d_src_w = nullptr; g->d_src_prob = nullptr; g->d_src_alias = nullptr; g->d_src_slots = nullptr;
-    g->S = 0; g->src_weight_sum = 0.0; g->src_stream_sum = 0; g->src_sum_fixed = false;
-    g->od_regions.clear();
-}
-
 // On success g holds the graph, names (may be NULL) the T*Rn vertex names, *n_regions = Rn and *n_sources = S.  On error g and names are as they were.
 [[maybe_unused]] int od_commit(SeqRun& R, dge_graph* g, dge_names* names, int64_t rows, int64_t E, int64_t T, const int64_t* src_id, const int64_t* dst_id, const uint64_t* w_bits,
                               const int32_t* slice, const int64_t* keepx, const char* who, int64_t* n_regions_out, int64_t* n_sources_out) {
@@ -100,19 +85,19 @@ void od_reset(dge_graph* g) {
     const int64_t Rn = n_regions;
 
     // ---- the edges into the graph's own staging, the layer-0 endpoints
-    dge_tmp<int32_t> coo_src, coo_dst, srcv;
-    dge_tmp<double> coo_w;
+    dge_coo coo;
+    dge_tmp<int32_t> srcv;
     dge_tmp<uint8_t> mark;
     dge_tmp<int64_t> markx;
-    SEQ_TRY(seq_alloc(R, coo_src, E, "the edges' sources"));
-    SEQ_TRY(seq_alloc(R, coo_dst, E, "the edges' destinations"));
-    SEQ_TRY(seq_alloc(R, coo_w, E, "the edges' weights"));
+    SEQ_TRY(seq_alloc(R, coo.src, E, "the edges' sources"));
+    SEQ_TRY(seq_alloc(R, coo.dst, E, "the edges' destinations"));
+    SEQ_TRY(seq_alloc(R, coo.w, E, "the edges' weights"));
     SEQ_TRY(seq_alloc(R, mark, Rn, "the layer-0 vertices"));
     SEQ_TRY(seq_alloc(R, markx, Rn + 1, "the layer-0 vertices' numbers"));
     SEQ_TRY(seq_kernels_begin(R));
     DGE_HIP(hipMemsetAsync(mark.p, 0, (size_t)std::max<int64_t>(Rn, 1), R.stream));
-    if (E) hipLaunchKernelGGL(k_od_edges, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, src_id, dst_id, w_bits, slice, keepx, rows, regions.p, Rn, T, coo_src.p, coo_dst.p,
-                              coo_w.p, mark.p);
+    if (E) hipLaunchKernelGGL(k_od_edges, dim3(seq_grid(rows)), dim3(SEQ_BLOCK), 0, R.stream, src_id, dst_id, w_bits, slice, keepx, rows, regions.p, Rn, T, coo.src.p, coo.dst.p,
+                              coo.w.p, mark.p);
     SEQ_TRY(seq_scan(R, rocprim::make_transform_iterator(rocprim::counting_iterator<int64_t>(0), SeqByteFlag{mark.p, Rn}), markx.p, Rn + 1));
     SEQ_TRY(seq_kernels_end(R));
     int64_t S = 0;
@@ -147,12 +132,10 @@ void od_reset(dge_graph* g) {
     }
 
     // ---- the graph takes the edges over, then stands where a host stands after add_edges, reserve_vertices and set_sources
-    od_reset(g);                                   // (a fresh graph may hold an empty CSR from a read-back: set_sources must build the real one)
-    g->d_coo_src = coo_src.release(); g->d_coo_dst = coo_dst.release(); g->d_coo_w = coo_w.release();
-    g->n_coo = E; g->cap_coo = std::max<int64_t>(E, 1);
-    g->max_id = (int32_t)(T * Rn) - 1;
+    coo.n = E; coo.cap = std::max<int64_t>(E, 1);
+    dge_graph_adopt_coo(g, std::move(coo), (int32_t)(T * Rn));      // (a fresh graph may hold an empty CSR from a read-back: it goes, set_sources builds the real one)
     const int rc = dge_graph_set_sources(g, host_srcv.data(), S, 0);
-    if (rc) { od_reset(g); return rc; }
+    if (rc) { dge_graph_reset(g); return rc; }
     // nothing can fail from here on
     g->od_regions = std::move(host_regions);
     if (names && T * Rn > 0) names_append(names, std::move(name_blob), off.data(), T * Rn);
@@ -163,7 +146,7 @@ void od_reset(dge_graph* g) {
 // what both entries check before a device is looked for (the pieces' own arguments are the caller's)
 int od_check(const dge_graph* g, const dge_names* names, const char* who) {
     if (names && !names->ptr.empty()) DGE_FAIL(DGE_ERR_ARG, "%s: names must be empty: it receives the vertex names, it holds %lld", who, (long long)names->ptr.size());
-    if (!od_fresh(g)) DGE_FAIL(DGE_ERR_STATE, "%s: the graph must be fresh: it already holds edges, sources or reserved vertices", who);
+    if (!dge_graph_fresh(g)) DGE_FAIL(DGE_ERR_STATE, "%s: the graph must be fresh: it already holds edges, sources or reserved vertices", who);
     return DGE_OK;
 }
 

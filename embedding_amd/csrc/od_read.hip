@@ -16,7 +16,7 @@
 //   od_commit.h, which dge_graph_add_flows (trip_map.hip) runs too:
 //   k_od_endpoints, radix sort, k_od_unique around a scan
 //                              the kept endpoints' ids sorted as signed 64-bit integers, each distinct one once: the R regions, ascending
-//   k_od_edges                 rank by binary search -> d_coo_src / d_coo_dst / d_coo_w of the graph, edge h*R + rank(src) -> ((h+1) % T)*R + rank(dst);
+//   k_od_edges                 rank by binary search -> the COO staging the graph takes over (dge_graph_adopt_coo), edge h*R + rank(src) -> ((h+1) % T)*R + rank(dst);
 //                              marks the layer-0 endpoints
 //   k_od_sources around a scan the marked layer-0 vertices, ascending
 // Every error is the LEAST position of its kind, found with atomicMin on a row or a byte offset: which lane gets there first does not matter.

@@ -166,18 +166,17 @@ int sp_build(dge_graph* g, const double* d_cent, const int64_t* ids, int64_t R, 
     SeqRun Rn;
     SEQ_TRY(seq_open(Rn, g->device, who));
     const int64_t E = R * (int64_t)k;
-    dge_tmp<int64_t> row_ptr;
-    dge_tmp<int32_t> nbr;
-    dge_tmp<double> w, outdeg;
+    dge_csr csr;
+    csr.V = (int32_t)R; csr.E = E;
     dge_tmp<unsigned long long> counters;
-    SEQ_TRY(seq_alloc(Rn, row_ptr, R + 1, "the row pointers"));
-    SEQ_TRY(seq_alloc(Rn, nbr, E, "the edges' destinations"));
-    SEQ_TRY(seq_alloc(Rn, w, E, "the edges' weights"));
-    SEQ_TRY(seq_alloc(Rn, outdeg, R, "the out-degrees"));
+    SEQ_TRY(seq_alloc(Rn, csr.row_ptr, R + 1, "the row pointers"));
+    SEQ_TRY(seq_alloc(Rn, csr.nbr, E, "the edges' destinations"));
+    SEQ_TRY(seq_alloc(Rn, csr.w, E, "the edges' weights"));
+    SEQ_TRY(seq_alloc(Rn, csr.outdeg, R, "the out-degrees"));
     SEQ_TRY(seq_alloc(Rn, counters, 2, "the counters"));
     DGE_HIP(hipMemsetAsync(counters.p, 0, 2 * sizeof(unsigned long long), Rn.stream));
     SEQ_TRY(seq_kernels_begin(Rn));
-    hipLaunchKernelGGL(k_sp_topk, dim3((unsigned)((R + SP_ROWS - 1) / SP_ROWS)), dim3(SEQ_BLOCK), 0, Rn.stream, d_cent, R, k, scale, row_ptr.p, nbr.p, w.p, outdeg.p, counters.p);
+    hipLaunchKernelGGL(k_sp_topk, dim3((unsigned)((R + SP_ROWS - 1) / SP_ROWS)), dim3(SEQ_BLOCK), 0, Rn.stream, d_cent, R, k, scale, csr.row_ptr.p, csr.nbr.p, csr.w.p, csr.outdeg.p, counters.p);
     SEQ_TRY(seq_kernels_end(Rn));
     DGE_HIP(hipGetLastError());
     unsigned long long c[2] = {0, 0};
@@ -203,13 +202,9 @@ int sp_build(dge_graph* g, const double* d_cent, const int64_t* ids, int64_t R, 
     for (int64_t r = 0; r < R; r++) srcv[(size_t)r] = (int32_t)r;
 
     // ---- the graph takes the edges over in the state keep_top_k leaves (dge_graph_adopt_pruned), then the sources
-    od_reset(g);                                   // (a fresh graph may hold an empty CSR from a read-back)
-    g->max_id = (int32_t)R - 1; g->V = (int32_t)R;
-    g->d_outdeg = outdeg.release();
-    g->csr_built = true;
-    int rc = dge_graph_adopt_pruned(g, row_ptr.release(), w.release(), nbr.release(), E);
+    int rc = dge_graph_adopt_pruned(g, std::move(csr));           // (a fresh graph may hold an empty CSR from a read-back: it goes)
     if (!rc) rc = dge_graph_set_sources(g, srcv.data(), R, 1);
-    if (rc) { od_reset(g); return rc; }
+    if (rc) { dge_graph_reset(g); return rc; }
     // nothing can fail from here on
     if (names) names_append(names, std::move(name_blob), off.data(), R);
     if (info) { info->regions = R; info->edges = E; info->weights = (int64_t)c[0]; info->zero_weights = (int64_t)c[1]; info->kernel_ms = Rn.kernel_ms; }

@@ -275,3 +275,218 @@ def test_host_held_public_fields_are_honoured(dge, oracle, exact):
     assert sa["weight_sum"] == sb["weight_sum"] and np.array_equal(bits(sa["prob"]), bits(sb["prob"]))
     with pytest.raises(dge.DgeError):
         dg.set_out_degree(od[:-1])                                    # one value per vertex
+
+
+# ------------------------------------------------------------------------------------------ the handle's state: refusals, sequences, builders, waits
+def snapshot(g, L=3):
+    """everything a host can read of a built graph, doubles as bits: the CSR with its tables, the source table, walks of both stream layouts."""
+    c, s = g.get_csr(), g.get_source_alias()
+    out = [np.int64([g.num_vertices, g.num_edges])] + [c[k] for k in ("row_ptr", "nbr", "weight", "out_degree", "prob", "alias")]
+    out += [s["prob"], s["alias"], s["src"], np.float64([s["weight_sum"]])] + [g.sample_walks(64, L, seed=2, rng_mode=m) for m in (0, 1)]
+    return [(a.shape, a.dtype, np.ascontiguousarray(a).tobytes()) for a in (np.asarray(x) for x in out)]
+
+
+def refused(dge, code, call):
+    with pytest.raises(dge.DgeError) as ei:
+        call()
+    assert ei.value.code == code, str(ei.value)
+
+
+def test_every_reachable_refusal_leaves_the_graph_as_it_was(dge):
+    """A refused call changes nothing a host can read: CSR, tables, source table and the walks of both modes are the bytes they were.  The builders are aimed at the
+    used handle through the C entries (the classes only ever hand them a new one).  The pruned copy keeps min(2, least degree) edges a vertex: this graph has
+    vertices with one edge, which keep_top_k(2) itself refuses."""
+    import ctypes as C
+    from embedding_amd._native import check
+    from embedding_amd.engine import _text_args
+    lib, p = dge.lib, lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    src, dst, w, sources = layered_graph(R=12, T=3, deg=3, seed=5)
+
+    def built():
+        g = dge.DeviceGraph(0); g.add_edges(src, dst, w); g.set_sources(sources); g.build_alias(True)
+        return g
+    g = built()
+    V = g.num_vertices
+    least = int(np.diff(g.get_csr()["row_ptr"]).min())
+    assert V == 36 and least >= 1
+    before = snapshot(g)
+    rg = dge.Regions.from_arrays([7], [0, 1], [0, 5], [(0, 0), (0, 1), (1, 1), (1, 0), (0, 0)])
+    flows = dge.Flows(rg); flows.add_entries([0], [0], [0], [1])
+    _keep, texts, sizes, n = _text_args([b"1 2 3"])
+    ids, xy = np.arange(3, dtype=np.int64), np.array([[0.0, 0.0], [1.0, 0.0], [0.0, 1.0]])
+    for code, call in [(2, lambda: g.set_sources([V])), (2, lambda: g.add_edges([-1], [0], [1.0])), (2, lambda: g.add_edges([0], [0x7fffffff], [1.0])),
+                       (1, lambda: g.set_out_degree(np.ones(V - 1))), (3, lambda: g.keep_top_k(least + 1)),
+                       (1, lambda: g.sample_walks(4, 64, seed=1, rng_mode=0)), (1, lambda: g.sample_walks(4, 64, seed=1, rng_mode=1)),
+                       (5, lambda: check(lib.dge_graph_add_od_texts(g._h, texts, sizes, n, None, None))),
+                       (5, lambda: check(lib.dge_graph_add_flows(g._h, flows._h, 1, 0, None, None))),
+                       (5, lambda: check(lib.dge_graph_add_spatial_points(g._h, p(ids), p(xy), 3, 2, 100.0, None, None)))]:
+        refused(dge, code, call)
+        assert snapshot(g) == before, code
+    cut = built()
+    cut.keep_top_k(min(2, least)); cut.build_alias(True)
+    before = snapshot(cut)
+    assert cut.num_edges == V * min(2, least) < len(src)
+    for call in (lambda: cut.add_edges([0], [1], [1.0]), lambda: cut.reserve_vertices(V + 1)):
+        refused(dge, 5, call)
+        assert snapshot(cut) == before
+
+
+def op_sequences():
+    """24 seeded sequences of at most 8 operations on at most 40 vertices and 200 edges, as (name, arguments) lists, and the sources and build order of the final
+    build.  Four cores by construction, six sequences each: set_out_degree before and after set_sources; set_source_weight_sum, then set_sources (the fixed sum
+    goes); add_edges after build_alias; keep_top_k after set_sources.  The rest is drawn.  The arguments are made legal on a host model of the store (vertex
+    count, least degree, pruned or not): no edges or new vertices after a prune, k within the least degree."""
+    seqs = []
+    for i in range(24):
+        rng = np.random.default_rng(1000 + i)
+        V0 = int(rng.integers(6, 25))
+        deg = np.zeros(40, np.int64)
+        st = dict(V=0, E=0, pruned=False, sources=[])
+        ops = []
+
+        def weights(n):
+            return rng.integers(1, 1000, n) * 10.0 ** rng.integers(-3, 3, n)
+
+        def add_edges(n, cover=False):
+            n = min(n, 200 - st["E"])
+            s = np.concatenate([np.tile(np.arange(V0), 2), rng.integers(0, V0, n - 2 * V0)]) if cover else rng.integers(0, max(st["V"], 2), n)
+            d = rng.integers(0, max(st["V"], V0) + (0 if cover or st["V"] >= 40 else 1), n)
+            s, d = rng.permutation(s).astype(np.int32), d.astype(np.int32)
+            np.add.at(deg, s, 1)
+            st["V"] = max(st["V"], int(max(s.max(), d.max())) + 1); st["E"] += n
+            ops.append(("add_edges", (s, d, weights(n))))
+
+        def set_sources(empty_ok=True):
+            n = int(rng.integers(0 if empty_ok else 1, min(st["V"], 9) + 1))
+            st["sources"] = rng.integers(0, st["V"], n).astype(np.int32)               # repeats allowed, as addSourceVertex allows them
+            ops.append(("set_sources", (st["sources"], bool(rng.integers(0, 2)))))
+
+        def op(name, core=False):
+            least = int(deg[:st["V"]].min())
+            if name == "add_edges" and not st["pruned"] and st["E"] < 190:
+                add_edges(int(rng.integers(1, 9)))
+            elif name == "reserve_vertices" and not st["pruned"] and st["V"] < 40:
+                st["V"] = int(rng.integers(st["V"], 41)); ops.append((name, (st["V"],)))
+            elif name == "set_sources":
+                set_sources(empty_ok=not core)
+            elif name == "set_out_degree":
+                ops.append((name, (weights(st["V"]),)))
+            elif name == "set_source_weight_sum":
+                ops.append((name, (float(weights(1)[0]),)))
+            elif name == "build_alias":
+                ops.append((name, (bool(rng.integers(0, 2)),)))
+            elif name == "keep_top_k" and least >= 1:
+                k = int(rng.integers(1, least + 1))
+                deg[:st["V"]] = k; st["pruned"] = True; st["E"] = st["V"] * k
+                ops.append((name, (k,)))
+            else:
+                ops.append(("get_csr", ()))
+        add_edges(int(rng.integers(3 * V0, 5 * V0)), cover=True)           # every vertex has two out-edges and more: a prune is possible and cuts
+        for name in (["set_out_degree", "set_sources", "set_out_degree"], ["set_sources", "set_source_weight_sum", "set_sources"],
+                     ["set_sources", "build_alias", "add_edges"], ["set_sources", "keep_top_k"])[i % 4]:
+            op(name, core=True)
+        names = ["add_edges", "reserve_vertices", "set_sources", "set_out_degree", "set_source_weight_sum", "build_alias", "keep_top_k", "get_csr"]
+        while len(ops) < 8:
+            op(names[int(rng.integers(0, len(names)))])
+        set_sources(empty_ok=False)                                        # sources set after the last edge, as the reference asks (J/LayeredGraph.java:177)
+        seqs.append((ops, ops.pop()[1], bool(i & 1)))
+    return seqs
+
+
+def apply_op(g, name, args, sources, is_oracle):
+    """keep_top_k on a graph with sources: the library refreshes the sources' weights and sums them as DoubleStream.sum() with no fixed sum (csrc/dge_internal.h:
+    dge_graph_adopt_pruned), which is keep_top_k followed by set_sources(the same, stream_sum) — the reference never prunes after addSourceVertex, so the oracle is
+    given that second call in words."""
+    if name == "get_csr":
+        g.get_csr(tables=False)
+        return
+    getattr(g, name)(*args)
+    if name == "keep_top_k" and is_oracle and len(sources):
+        g.set_sources(sources, True)
+
+
+def weight_sum(g):
+    """get_source_alias()["weight_sum"]; the device hands its tables out only once they are built, the sum at any time (cap 0, no arrays)."""
+    if not hasattr(g, "device"):
+        return g.get_source_alias()["weight_sum"]
+    import ctypes as C
+    from embedding_amd._native import check, lib
+    k, ws = C.c_int32(0), C.c_double(0)
+    check(lib.dge_graph_get_source_alias(g._h, None, None, None, 0, C.byref(k), C.byref(ws)))
+    return ws.value
+
+
+def read_state(g):
+    counts = np.int64([g.num_vertices, g.num_edges])              # read first: the CSR may not be built yet
+    c = g.get_csr(tables=False)
+    return [(np.asarray(a).shape, np.ascontiguousarray(a).tobytes()) for a in
+            (counts, c["row_ptr"], c["nbr"], c["weight"], c["out_degree"], np.float64([weight_sum(g)]))]
+
+
+@pytest.mark.parametrize("i", range(24))
+def test_operation_sequences_against_the_oracle(dge, oracle, i):
+    ops, final_sources, exact = op_sequences()[i]
+    assert len(ops) <= 8
+    og, dg = oracle.Graph(), dge.DeviceGraph(0)
+    sources = []
+    for step, (name, args) in enumerate(ops):
+        for g in (og, dg):
+            apply_op(g, name, args, sources, g is og)
+        if name == "set_sources":
+            sources = args[0]
+        assert read_state(og) == read_state(dg), (step, name)
+        assert og.num_vertices <= 40 and og.num_edges <= 200
+    for g in (og, dg):
+        g.set_sources(*final_sources); g.build_alias(exact)
+    a, b = og.get_csr(), dg.get_csr()
+    for k in a:
+        assert np.ascontiguousarray(a[k]).tobytes() == np.ascontiguousarray(b[k]).tobytes(), k
+    a, b = og.get_source_alias(), dg.get_source_alias()
+    for k in a:
+        assert np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes(), k
+    for mode in (0, 1):
+        assert np.array_equal(og.sample_walks(64, 5, seed=3, rng_mode=mode), dg.sample_walks(64, 5, seed=3, rng_mode=mode)), mode
+
+
+def test_a_flow_table_ends_where_a_host_ends(dge):
+    """from_flows against a second graph fed the same slot edges by add_edges, reserve_vertices and set_sources: 5 regions, ids not in order, 8 slices.  (The .od
+    reader and the spatial graph have this comparison in test_gpu_od_read.py: check, and test_gpu_spatial.py: check_against_old_path.)"""
+    ids = [50, 10, 40, 20, 30]
+    ring = [(0.0, 0.0), (0.0, 1.0), (1.0, 1.0), (1.0, 0.0), (0.0, 0.0)]
+    xy = [(x + 2.0 * r, y) for r in range(5) for x, y in ring]
+    rg = dge.Regions.from_arrays(ids, np.arange(6), np.arange(6) * 5, xy)
+    rng = np.random.default_rng(8)
+    f = dge.Flows(rg)
+    f.add_entries(rng.integers(0, 24, 60), rng.integers(0, 4, 60), rng.integers(1, 5, 60), rng.integers(1, 9, 60))     # region 0 never a source, region 4 never a destination
+    T = 8
+    g, _, info = dge.DeviceGraph.from_flows(f, T, dge.Flows.EVEN, names=False)
+    slot, sid, did, w = f.slot_edges(T, dge.Flows.EVEN)
+    regions = np.unique(np.concatenate([sid, did]))
+    R = len(regions)
+    assert R == 5 and info["edges"] == len(slot) > 20 and np.array_equal(g.regions(), regions)
+    src = slot * R + np.searchsorted(regions, sid); nxt = (slot + 1) % T
+    dst = nxt * R + np.searchsorted(regions, did)
+    h = dge.DeviceGraph(0)
+    h.add_edges(src, dst, w.astype(np.float64)); h.reserve_vertices(T * R); h.set_sources(np.unique(np.concatenate([src[slot == 0], dst[nxt == 0]])))
+    g.build_alias(True); h.build_alias(True)
+    assert snapshot(g, L=T + 1) == snapshot(h, L=T + 1)
+
+
+def test_counted_host_waits_of_the_graph_entries(dge):
+    """dge_host_sync_count around one call, on layered_graph(R=60, T=5, deg=9, seed=0): 1550 edges, so build_alias(False) takes its hub-list path, and no vertex
+    with 1024 edges, so there is no hub.  The figures are those of the build of commit 8cce4c7, the last one before the handle's groups, measured on an MI355X:
+    upper bounds, but for sample_walks_into, which the trainer's zero-wait episode counts on."""
+    src, dst, w, sources = layered_graph(R=60, T=5, deg=9, seed=0)
+    assert len(src) >= 1024 and np.bincount(src).max() < 1024
+
+    def waits(call):
+        c0 = dge.host_sync_count(); call()
+        return dge.host_sync_count() - c0
+    g = dge.DeviceGraph(0); g.add_edges(src, dst, w)
+    assert waits(lambda: g.set_sources(sources)) <= 2              # 8cce4c7: 2 (the CSR is built in the call)
+    assert waits(lambda: g.set_sources(sources)) <= 1              # 8cce4c7: 1
+    assert waits(lambda: g.build_alias(True)) <= 2                 # 8cce4c7: 2
+    assert waits(lambda: g.build_alias(False)) <= 4                # 8cce4c7: 4
+    corpus = dge.WalkCorpus.from_host(np.zeros((256, 5), np.int32), 0)
+    assert waits(lambda: g.sample_walks_into(corpus, 0, 256, 7, 0)) == 1        # 8cce4c7: 1
+    assert waits(lambda: g.keep_top_k(1)) <= 3                     # 8cce4c7: 3 (least degree, compaction, the sources' refresh)
