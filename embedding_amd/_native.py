@@ -178,7 +178,19 @@ class TripletInfo(C.Structure):
     _fields_ = [("pairs_12", C.c_int64), ("pairs_23", C.c_int64), ("pairs_31", C.c_int64), ("candidates", C.c_int64), ("triplets", C.c_int64), ("kernel_ms", C.c_double)]
 
 
+class FlowSlices(C.Structure):
+    """struct dge_flow_slices (include/dge.h): K == 0 — the slots of (T, mode); K >= 1 — the windows win[0 .. K), T = mode = 0."""
+    _fields_ = [("T", C.c_int32), ("mode", C.c_int32), ("K", C.c_int32), ("reserved", C.c_int32), ("win", C.POINTER(HourWindow))]
+
+
+class FlowTextInfo(C.Structure):
+    """struct dge_flow_text_info (include/dge.h) — what the flow table's text writers report."""
+    _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("edges", C.c_int64), ("zeros", C.c_int64), ("slices", C.c_int32), ("reserved", C.c_int32),
+                ("kernel_ms", C.c_double), ("write_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
+DGE_FLOW_TEXT_OD, DGE_FLOW_TEXT_OD_LAYERED, DGE_FLOW_TEXT_MATRIX = 0, 1, 2
 DGE_NMF_DIVERGENCE, DGE_NMF_EUCLIDEAN = 0, 1
 DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
 
@@ -229,6 +241,11 @@ SIGNATURES = {
     "dge_triplet_rule_default": (_int, [_P(TripletRule)]),
     "dge_triplet_rule_check": (_int, [_P(TripletRule), _vp, _P(_i32)]),
     "dge_flows_triplets": (_int, [_vp, _P(TripletRule), _vp, _vp, _vp, _i64, _P(_i64), _P(TripletInfo)]),
+    "dge_flows_to_text": (_int, [_vp, _P(FlowSlices), _i32, _i32, _vp, _i32, _vp, _i64, _P(_i64), _P(FlowTextInfo)]),
+    "dge_flows_write_text": (_int, [_vp, _P(FlowSlices), _i32, _vp, _i32, _vp, _i32, _P(FlowTextInfo)]),
+    "dge_flows_time_series": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
+    "dge_flows_time_series_text": (_int, [_vp, _vp, _vp, _i64, _P(_i64), _P(FlowTextInfo)]),
+    "dge_flows_write_time_series": (_int, [_vp, _vp, C.c_char_p, _P(FlowTextInfo)]),
     "dge_regions_centroids": (_int, [_vp, _vp, _i64, _P(_i64)]),
     "dge_graph_add_spatial": (_int, [_vp, _vp, _i32, _dbl, _vp, _P(SpatialInfo)]),
     "dge_graph_add_spatial_points": (_int, [_vp, _vp, _vp, _i64, _i32, _dbl, _vp, _P(SpatialInfo)]),

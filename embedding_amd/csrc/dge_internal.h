@@ -205,6 +205,14 @@ int dge_flows_merge(dge_flows* f, const dge_flows* part);          // part's tab
 int dge_flows_slot_coo(const dge_flows* f, int32_t T, int32_t mode, int32_t slot, const uint8_t* select, const char* who, dge_tmp<int32_t>& row, dge_tmp<int32_t>& col,
                        dge_tmp<double>& val, int64_t* n_entries, std::vector<int64_t>& regions);
 
+// The two edge sources of the flow table as flow_text.hip takes them: the edges of dge_flows_slot_edges (trip_map.hip) and of dge_flows_window_edges
+// (flow_windows.hip) as they stand on the device before the decode — the keys (slice * R + rank of the src id) * R + rank of the dst id, R = max(regions, 1),
+// ascending, with their int64 weights; *n of them (0: the arrays may be null).  The two checks are those entries' own; kernel_ms is added to.
+int dge_flows_slot_check(int32_t T, int32_t mode, const char* who);
+int dge_flows_windows_check(const dge_hour_window* win, int32_t K, const char* who);
+int dge_flows_slot_keys(const dge_flows* f, int32_t T, int32_t mode, const char* who, dge_tmp<uint64_t>& key, dge_tmp<int64_t>& w, int64_t* n, double* kernel_ms);
+int dge_flows_window_keys(const dge_flows* f, const dge_hour_window* win, int32_t K, const char* who, dge_tmp<uint64_t>& key, dge_tmp<int64_t>& w, int64_t* n, double* kernel_ms);
+
 int dge_graph_ensure_csr(dge_graph* g);
 // The two ways another translation unit hands a graph its edges (graph.hip); neither can leave g half-way.
 // The edges of n_vertices vertices as COO arrays of coo.n entries: g stands where dge_graph_add_edges and dge_graph_reserve_vertices would leave it.

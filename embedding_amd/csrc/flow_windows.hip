@@ -311,6 +311,17 @@ extern "C" int dge_flows_window_edges(const dge_flows* f, const dge_hour_window*
     return seq_read_back(R, w, ow.p, (size_t)E * 8);
 }
 
+int dge_flows_windows_check(const dge_hour_window* win, int32_t K, const char* who) { return windows_check(win, K, who); }
+
+int dge_flows_window_keys(const dge_flows* f, const dge_hour_window* win, int32_t K, const char* who, dge_tmp<uint64_t>& key, dge_tmp<int64_t>& w, int64_t* n, double* kernel_ms) {
+    *n = 0;
+    SeqRun R;
+    if (f->n > 0) SEQ_TRY(seq_open(R, f->regions->device, who));
+    const int rc = win_edges(R, f, win, K, who, key, w, n);         // (an empty table still gets the range check of K R R)
+    *kernel_ms += R.kernel_ms;
+    return rc;
+}
+
 extern "C" int dge_graph_add_flow_windows(dge_graph* g, const dge_flows* f, const dge_hour_window* win, int32_t K, dge_names* names, dge_od_info* info) {
     const char* who = "dge_graph_add_flow_windows";
     SEQ_TRY(windows_check(win, K, who));

@@ -19,18 +19,13 @@
 // which lane of which launch does it (tile and slab size, the order of the long-token list) changes nothing in the output.
 //
 // Host side: the text leaves in slabs of SEQ_OUT_SLAB output bytes.  The device holds two slab buffers, the host two pinned ones; slab s + 1 is formatted while
-// slab s is copied out and slab s - 1 goes to write() or to the caller's memory.  Nothing is staged through pageable memory.
-#include <errno.h>
-#include <fcntl.h>
-#include <string.h>
-#include <unistd.h>
-
+// slab s is copied out and slab s - 1 goes to write() or to the caller's memory.  Nothing is staged through pageable memory.  That loop and the sink are
+// text_out_pump.h, shared with flow_text.hip.
 #include <algorithm>
 #include <chrono>
 #include <hipcub/hipcub.hpp>
 
-#include "dge_device.h"
-#include "seq_out_plan.h"
+#include "text_out_pump.h"
 
 // ------------------------------------------------------------------------------------------ kernels
 constexpr int SQW_BLOCK = 256;
@@ -165,77 +160,15 @@ namespace {
 
 #define SQW_TRY(expr) do { int rc__ = (expr); if (rc__) return rc__; } while (0)
 
-struct SqwRun {
-    hipStream_t ks = nullptr, cs = nullptr;                       // kernels; copies to the host
-    hipEvent_t ka[2] = {nullptr, nullptr}, kb[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-    uint8_t* pin[2] = {nullptr, nullptr};
-    dge_tmp<uint8_t> blob, text, scratch;
+struct SqwRun : TextPump {                                          // the streams, the events and the slab buffers: text_out_pump.h
+    dge_tmp<uint8_t> blob, scratch;
     dge_tmp<int64_t> name_off, row_len, row_off;
     dge_tmp<int32_t> row_last;
     dge_tmp<unsigned long long> counters;
-    double kernel_ms = 0;
-    ~SqwRun() {
-        if (cs) (void)hipStreamSynchronize(cs);
-        if (ks) (void)hipStreamSynchronize(ks);
-        for (int i = 0; i < 2; i++) {
-            if (pin[i]) (void)hipHostFree(pin[i]);
-            if (ka[i]) (void)hipEventDestroy(ka[i]);
-            if (kb[i]) (void)hipEventDestroy(kb[i]);
-            if (copied[i]) (void)hipEventDestroy(copied[i]);
-        }
-        if (cs) (void)hipStreamDestroy(cs);
-        if (ks) (void)hipStreamDestroy(ks);
-    }
+    ~SqwRun() { drain(); }                                          // the streams rest before the arrays above go
 };
 
-int sqw_add_kernel_ms(SqwRun& R, int b) {
-    float ms = 0.f;
-    DGE_HIP(hipEventElapsedTime(&ms, R.ka[b], R.kb[b]));
-    R.kernel_ms += ms;
-    return DGE_OK;
-}
-
-// where the text goes: the caller's memory or a file
-struct SqwSink {
-    const char* who;
-    char* text = nullptr; int64_t cap = 0;       // text leg
-    const char* path = nullptr; int append = 0;  // file leg
-    int fd = -1;
-    int64_t at = 0;
-    ~SqwSink() { if (fd >= 0) close(fd); }
-    // 1: nothing more to do (a size query), *status is the call's result
-    int begin(int64_t total, int64_t* n_bytes, int* done) {
-        *done = 0;
-        if (n_bytes) *n_bytes = total;
-        if (path) {
-            fd = open(path, O_WRONLY | O_CREAT | O_CLOEXEC | (append ? O_APPEND : O_TRUNC), 0666);
-            if (fd < 0) DGE_FAIL(DGE_ERR_IO, "%s: cannot open %s: %s", who, path, strerror(errno));
-            return DGE_OK;
-        }
-        if (!text) { *done = 1; return DGE_OK; }                  // cap == 0: a size query
-        if (total > cap) DGE_FAIL(DGE_ERR_CAP, "%s: text holds %lld of %lld bytes", who, (long long)cap, (long long)total);
-        return DGE_OK;
-    }
-    int put(const uint8_t* p, int64_t n) {
-        if (!path) { memcpy(text + at, p, (size_t)n); at += n; return DGE_OK; }
-        for (int64_t done = 0; done < n;) {
-            const ssize_t r = write(fd, p + done, (size_t)(n - done));
-            if (r < 0 && errno == EINTR) continue;
-            if (r <= 0) DGE_FAIL(DGE_ERR_IO, "%s: cannot write %s: %s after %lld bytes", who, path, r < 0 ? strerror(errno) : "nothing was taken", (long long)(at + done));
-            done += (int64_t)r;
-        }
-        at += n;
-        return DGE_OK;
-    }
-    int end() {
-        if (fd >= 0) {
-            const int rc = close(fd);
-            fd = -1;
-            if (rc != 0) DGE_FAIL(DGE_ERR_IO, "%s: cannot close %s: %s", who, path, strerror(errno));
-        }
-        return DGE_OK;
-    }
-};
+using SqwSink = TextSink;
 
 // what both entries check before a device is looked for
 int sqw_check(const char* who, const dge_walks* w, int64_t row0, int64_t n_rows, bool null_or_negative) {
@@ -249,13 +182,7 @@ int sqw_run(const dge_walks* w, int64_t row0, int64_t n_rows, const dge_names* n
     const char* who = sink.who;
     SQW_TRY(dge_require_device(w->device));
     SqwRun R;
-    DGE_HIP(hipStreamCreateWithFlags(&R.ks, hipStreamNonBlocking));
-    DGE_HIP(hipStreamCreateWithFlags(&R.cs, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) {
-        DGE_HIP(hipEventCreate(&R.ka[i]));
-        DGE_HIP(hipEventCreate(&R.kb[i]));
-        DGE_HIP(hipEventCreateWithFlags(&R.copied[i], hipEventDisableTiming));
-    }
+    SQW_TRY(R.open());
     const int32_t L = w->L;
     const int32_t* walks = w->d + row0 * L;
     prefix = prefix ? 1 : 0;
@@ -304,7 +231,7 @@ int sqw_run(const dge_walks* w, int64_t row0, int64_t n_rows, const dge_names* n
         DGE_HIP(hipMemcpyAsync(counters, R.counters.p, sizeof counters, hipMemcpyDeviceToHost, R.ks));
         DGE_HIP(hipMemcpyAsync(&total, R.row_off.p + n_rows, 8, hipMemcpyDeviceToHost, R.ks));
         DGE_HIP(hipStreamSynchronize(R.ks));
-        SQW_TRY(sqw_add_kernel_ms(R, 0));
+        SQW_TRY(R.add_kernel_ms(0));
         if (counters[2] != SQW_NONE) {
             const int64_t key = (int64_t)counters[2];
             int32_t id = 0;
@@ -318,33 +245,11 @@ int sqw_run(const dge_walks* w, int64_t row0, int64_t n_rows, const dge_names* n
     int done = 0;
     SQW_TRY(sink.begin(total, n_bytes, &done));
     const auto t0 = clock::now();
-    const int64_t S = done ? 0 : seq_out_slab_count(total);
-    if (S > 0) {
-        const int64_t buf = seq_out_buffer_bytes(total);
-        SQW_TRY(R.text.alloc((size_t)(2 * buf)));
-        for (int i = 0; i < 2 && i < S; i++) DGE_HIP(hipHostMalloc((void**)&R.pin[i], (size_t)buf, hipHostMallocDefault));
-        for (int64_t i = 0; i <= S; i++) {
-            if (i < S) {
-                const int b = (int)(i & 1);
-                const int64_t s0 = seq_out_slab_begin(i), s1 = seq_out_slab_end(total, i);
-                if (i >= 2) DGE_HIP(hipStreamWaitEvent(R.ks, R.copied[b], 0));            // the device buffer's last tenant has left
-                DGE_HIP(hipEventRecord(R.ka[b], R.ks));
-                hipLaunchKernelGGL(k_sqw_emit, dim3((unsigned)seq_out_tiles(s1 - s0)), dim3(SQW_BLOCK), 0, R.ks, walks, L, n_rows, N, prefix, R.row_off.p, R.row_last.p, s0, s1,
-                                   R.text.p + (int64_t)b * buf);
-                DGE_HIP(hipGetLastError());
-                DGE_HIP(hipEventRecord(R.kb[b], R.ks));
-                DGE_HIP(hipStreamWaitEvent(R.cs, R.kb[b], 0));
-                DGE_HIP(hipMemcpyAsync(R.pin[b], R.text.p + (int64_t)b * buf, (size_t)(s1 - s0), hipMemcpyDeviceToHost, R.cs));      // (the host is done with pin[b]: slab i - 2 went out below)
-                DGE_HIP(hipEventRecord(R.copied[b], R.cs));
-            }
-            if (i >= 1) {
-                const int p = (int)((i - 1) & 1);
-                DGE_HIP(hipEventSynchronize(R.copied[p]));
-                SQW_TRY(sqw_add_kernel_ms(R, p));
-                SQW_TRY(sink.put(R.pin[p], seq_out_slab_end(total, i - 1) - seq_out_slab_begin(i - 1)));
-            }
-        }
-    }
+    if (!done)
+        SQW_TRY(R.run(total, sink, nullptr, [&](int64_t s0, int64_t s1, uint8_t* out) -> int {
+            hipLaunchKernelGGL(k_sqw_emit, dim3((unsigned)seq_out_tiles(s1 - s0)), dim3(SQW_BLOCK), 0, R.ks, walks, L, n_rows, N, prefix, R.row_off.p, R.row_last.p, s0, s1, out);
+            return DGE_OK;
+        }));
     SQW_TRY(sink.end());
     if (info) {
         info->bytes = total; info->lines = n_rows; info->tokens = (int64_t)counters[0]; info->empty_lines = (int64_t)counters[1];

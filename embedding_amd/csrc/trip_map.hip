@@ -616,6 +616,18 @@ int dge_flows_slot_coo(const dge_flows* f, int32_t T, int32_t mode, int32_t slot
     return DGE_OK;
 }
 
+int dge_flows_slot_check(int32_t T, int32_t mode, const char* who) { return slot_check(T, mode, who); }
+
+int dge_flows_slot_keys(const dge_flows* f, int32_t T, int32_t mode, const char* who, dge_tmp<uint64_t>& key, dge_tmp<int64_t>& w, int64_t* n, double* kernel_ms) {
+    *n = 0;
+    if (f->n == 0) return DGE_OK;
+    SeqRun R;
+    SEQ_TRY(seq_open(R, f->regions->device, who));
+    const int rc = trip_slot_edges(R, f, T, mode, key, w, n);
+    *kernel_ms += R.kernel_ms;
+    return rc;
+}
+
 extern "C" void dge_flows_free(dge_flows* f) {
     if (!f) return;
     dge_dev_free(f->d_key); dge_dev_free(f->d_cnt);

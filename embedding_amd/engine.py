@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, SvmCfg, SvmInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_FLOW_TEXT_MATRIX, DGE_FLOW_TEXT_OD, DGE_FLOW_TEXT_OD_LAYERED, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowSlices, FlowTextInfo, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, SvmCfg, SvmInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
 from .evaluate import _info_dict, _select_mask
 
 
@@ -550,6 +550,101 @@ class Flows:
         info = _info_dict(inf)
         info["region_index"] = index
         return X, Y, touched.astype(bool), (ids[index] if ids is not None else index), info
+
+    # ---- the table out as text, sized and spelled on the device (include/dge.h: "flow table out as text")
+    def _slices(self, T, mode, windows):
+        """(T, mode) or windows -> (struct dge_flow_slices, what it points at, the number of slices)"""
+        if windows is not None:
+            if T is not None:
+                raise ValueError("T or windows, not both")
+            win = _windows(windows)
+            return FlowSlices(0, 0, len(win), 0, C.cast(win, C.POINTER(HourWindow))), win, len(win)
+        if T is None:
+            raise ValueError("T or windows is needed")
+        return FlowSlices(int(T), int(mode), 0, 0, None), None, int(T)
+
+    def _select(self, select):
+        if select is None:
+            return None
+        select = np.ascontiguousarray(np.asarray(select) != 0, np.uint8)
+        if select.shape != (self.regions.info()["regions"],):
+            raise ValueError("select must hold one entry per region")
+        return select
+
+    def _text(self, sl, kind, k, select, sep, return_info=False):
+        need = C.c_int64(0); inf = FlowTextInfo()
+        check(lib.dge_flows_to_text(self._h, C.byref(sl), kind, k, _ptr(select), sep, None, 0, C.byref(need), None))          # a size query
+        buf = np.empty(max(need.value, 1), np.uint8)
+        check(lib.dge_flows_to_text(self._h, C.byref(sl), kind, k, _ptr(select), sep, _ptr(buf), need.value, C.byref(need), C.byref(inf)))
+        text = buf[:need.value].tobytes()
+        return (text, _info_dict(inf)) if return_info else text
+
+    def _write(self, paths, sl, kind, select, sep):
+        if isinstance(paths, (str, os.PathLike)):
+            paths = [paths]
+        arr = (C.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        inf = FlowTextInfo()
+        check(lib.dge_flows_write_text(self._h, C.byref(sl), kind, _ptr(select), sep, arr, len(paths), C.byref(inf)))
+        return _info_dict(inf)
+
+    def od_text(self, T=None, mode=DGE_SLOTS_EVEN, windows=None, layered=False):
+        """The .od texts of the slots (T, mode) or of the hour windows [(start, hours), ..] (dge_flows_to_text; J/Tracts.java:236-264): a list of bytes, one per
+        slice, the lines "src dst w" ascending by (src id, dst id).  layered: ONE bytes for all slices, the lines "k-src (k+1)%S-dst w"
+        (outputEdgeGraph_crossInterval, J/Tracts.java:314-330).  od_text(T=1) is [taxi-all.od].  Every text is a size query and a call, and each forms the
+        edges: for many slices of a large table write_od, which forms them once, is the way."""
+        sl, _keep, S = self._slices(T, mode, windows)
+        if layered:
+            return self._text(sl, DGE_FLOW_TEXT_OD_LAYERED, 0, None, 0)
+        return [self._text(sl, DGE_FLOW_TEXT_OD, k, None, 0) for k in range(S)]
+
+    def write_od(self, paths, T=None, mode=DGE_SLOTS_EVEN, windows=None, layered=False):
+        """The same texts into files, one path per slice (one path when layered); the edges are formed once (dge_flows_write_text).  Files are created or
+        truncated, in slice order.  -> the fields of struct dge_flow_text_info, summed over the files"""
+        sl, _keep, _ = self._slices(T, mode, windows)
+        return self._write(paths, sl, DGE_FLOW_TEXT_OD_LAYERED if layered else DGE_FLOW_TEXT_OD, None, 0)
+
+    def matrix_text(self, slice, T=None, mode=DGE_SLOTS_EVEN, windows=None, sep=",", select=None):
+        """The .matrix text of one slice (Tracts.outputAdjacencyMatrix, J/Tracts.java:269-301; CommunityAreas', J/CommunityAreas.java:148-166): n lines of n
+        decimals, 0 for an absent pair, joined by sep (",", " " or a tab), over all regions in ascending id or those select marks (one entry per region, by
+        region index).  Nothing of size n^2 is formed on the device."""
+        sl, _keep, _ = self._slices(T, mode, windows)
+        return self._text(sl, DGE_FLOW_TEXT_MATRIX, int(slice), self._select(select), ord(sep))
+
+    def write_matrix(self, paths, T=None, mode=DGE_SLOTS_EVEN, windows=None, sep=",", select=None):
+        """Every slice's .matrix into its own file -> the fields of struct dge_flow_text_info, summed over the files."""
+        sl, _keep, _ = self._slices(T, mode, windows)
+        return self._write(paths, sl, DGE_FLOW_TEXT_MATRIX, self._select(select), ord(sep))
+
+    def time_series(self, select=None):
+        """Tracts.timeSeries_traffic as numbers (dge_flows_time_series; J/Tracts.java:187-224) -> (ids int64 [n], in int64 [n, 24], out int64 [n, 24]) for the
+        regions select marks (None: all), ascending by id.  out sums over ALL destinations, in over the SELECTED sources — the reference's asymmetry, kept.
+        ids are region indices when the regions were not made by Regions.from_arrays."""
+        select = self._select(select)
+        n = C.c_int64(0)
+        rc = lib.dge_flows_time_series(self._h, _ptr(select), None, None, None, 0, C.byref(n))          # a size query
+        if rc not in (0, DGE_ERR_CAP):
+            check(rc)
+        m = n.value
+        fin = np.zeros((m, 24), np.int64); fout = np.zeros((m, 24), np.int64); index = np.zeros(m, np.int64)
+        if m:
+            check(lib.dge_flows_time_series(self._h, _ptr(select), _ptr(fin), _ptr(fout), _ptr(index), m, C.byref(n)))
+        ids = getattr(self.regions, "ids", None)
+        return (ids[index] if ids is not None else index), fin, fout
+
+    def time_series_text(self, select=None):
+        """taxi-flow-time-series.txt (dge_flows_time_series_text): two lines per region, "id,in_0,..,in_23" and "-id,out_0,..,out_23"."""
+        select = self._select(select)
+        need = C.c_int64(0)
+        check(lib.dge_flows_time_series_text(self._h, _ptr(select), None, 0, C.byref(need), None))          # a size query
+        buf = np.empty(max(need.value, 1), np.uint8)
+        check(lib.dge_flows_time_series_text(self._h, _ptr(select), _ptr(buf), need.value, C.byref(need), None))
+        return buf[:need.value].tobytes()
+
+    def write_time_series(self, path, select=None):
+        """The same text into a file (created or truncated) -> the fields of struct dge_flow_text_info."""
+        inf = FlowTextInfo()
+        check(lib.dge_flows_write_time_series(self._h, _ptr(self._select(select)), os.fsencode(path), C.byref(inf)))
+        return _info_dict(inf)
 
     def to_od_bytes(self, T, mode=DGE_SLOTS_EVEN):
         """The T .od texts (J/Tracts.java:236-260), formatted on the host from slot_edges: the tables are small."""

@@ -314,6 +314,72 @@ int  dge_triplet_rule_check(const dge_triplet_rule* rule /* NULL: the default */
 int  dge_flows_triplets(const dge_flows* f, const dge_triplet_rule* rule /* NULL: the default */, int64_t* id1, int64_t* id2, int64_t* id3, int64_t cap, int64_t* n,
                         dge_triplet_info* info /* may be NULL */);
 
+/* ---- flow table out as text (new; additions only, DGE_VERSION unchanged): the files the reference writes from taxiFlows and its later stages open — the
+ * .od edge files (Tracts.outputEdgeFile / outputStaticEdgeFile, J/Tracts.java:236-264; CommunityAreas.outputStaticFlowGraph, J/CommunityAreas.java:127-146),
+ * the .matrix adjacency files (Tracts.outputAdjacencyMatrix, J/Tracts.java:269-301, comma-separated; CommunityAreas.outputAdjacencyMatrix,
+ * J/CommunityAreas.java:148-166, blank-separated), the layered edge text of outputEdgeGraph_crossInterval (J/Tracts.java:314-330) and the in / out traffic
+ * time series (Tracts.timeSeries_traffic, J/Tracts.java:187-224) — sized and spelled on the device (csrc/flow_text.hip, csrc/flow_text_plan.h); the host only
+ * moves bytes.  Everything is integer arithmetic; every text is a pure function of the table and the arguments, whatever calls built the table, and nothing
+ * depends on timing, launch geometry, tile size or slab size.  The rule:
+ *   - SLICES.  A dge_flow_slices names S edge sets.  K == 0: the S = T slot-edge sets of dge_flows_slot_edges(T, mode).  K >= 1: the S = K window-edge sets of
+ *     dge_flows_window_edges(win, K); T and mode must then be 0.  reserved is 0.  The checks and statuses are those two entries' own.
+ *   - DECIMALS.  An integer is written as %lld writes it: a '-' when negative, no '+', no leading zeros.  Region ids are int64 of any sign; weights are
+ *     positive int64 (a key holds 2^40 at most, so a sum reaches 24 * 2^40: 14 digits).
+ *   - DGE_FLOW_TEXT_OD.  Slice k is one text: the lines "<src id> <dst id> <w>\n" of the slice's edges, ascending by (src id, dst id) — the text the contracts
+ *     of dge_graph_add_flows and dge_graph_add_flow_windows describe.  A slice without edges is the empty text.  T = 1, DGE_SLOTS_EVEN gives taxi-all.od.
+ *   - DGE_FLOW_TEXT_OD_LAYERED.  ONE text for all S slices: the lines "<k>-<src id> <(k+1) mod S>-<dst id> <w>\n", ascending by (k, src id, dst id).  With
+ *     the 24 windows (h, 1) it is taxi-crossInterval.od up to the reference's HashMap order, which is not an order.
+ *   - DGE_FLOW_TEXT_MATRIX.  Slice k is one text of n lines: line i holds the n decimals W_k[r_i, r_j], j ascending, 0 for an absent pair, each followed by ONE
+ *     byte: sep, or '\n' behind the last.  r_0 .. r_{n-1} are all R regions in ascending id (select == NULL) or the regions with a non-zero select byte (one
+ *     byte per region, by region index) in ascending id; entries whose other endpoint is not selected play no part.  sep is ',' (tracts, CA static), ' ' (CA
+ *     hourly) or '\t'.  n = 0 gives the empty text.  No header.  Nothing of size n^2 is formed on the device: its memory is bounded by the edges and two slabs.
+ *     For the two .od kinds sep must be 0 and select NULL.
+ *   - The TIME SERIES.  For the selected regions (as above; the reference's focusKeys) in ascending id and every hour h = 0 .. 23: out[r][h] is the sum of
+ *     c(h, r, e) over ALL destinations e; in[r][h] is the sum of c(h, s, r) over the SELECTED sources s, r itself included.  The asymmetry is the
+ *     reference's as written (J/Tracts.java:200-206: the flows into a focus tract are looked up in the focus tracts only) and is kept.  The text has two lines
+ *     per region: "<id>,<in_0>,..,<in_23>\n" and "<-id>,<out_0>,..,<out_23>\n"; <-id> is the decimal of the negated id, so id 0 gives 0 twice.  A selected id
+ *     of -2^63 cannot be negated: DGE_ERR_RANGE naming the region.  Sums are int64 and may be 0.
+ *   - NOT CARRIED OVER: CommunityAreas.outputEdgeGraph_LINE (J/CommunityAreas.java:171-186) writes zero-weight lines and stops one column short (j < size): a
+ *     quirk with no consumer in either tree.  The three-node .dot case files (J/Tracts.java:127-182) are host work on nine numbers.
+ * dge_flow_text_info: edges are the table-derived numbers spelled with their value (.od lines, non-zero matrix entries, the 48 sums of a region's two series
+ * lines), zeros the matrix entries written as "0"; over dge_flows_write_text everything is summed over the files.
+ * Statuses, those of the .seq writer:
+ *   - Null or negative arguments, a bad kind, sep, select, slice, n_paths or slices struct: DGE_ERR_ARG.  Plain values are checked before handles, and all of it
+ *     before a device is looked for.
+ *   - cap smaller than the text: DGE_ERR_CAP with *n_bytes set and text untouched; text == NULL with cap == 0 is a size query.
+ *   - Everything the sizing pass can find is found before a file is created or truncated.  A file is created or truncated, never appended to; files are written
+ *     in slice order; an open or write failure is DGE_ERR_IO with the path and the OS error, and the files finished before it stay.
+ *   - Out of device memory: DGE_ERR_CAP with the bytes asked for.
+ *   - The entries only read the table: after any call dge_flows_to_host and dge_flows_info give what they gave before. */
+enum { DGE_FLOW_TEXT_OD = 0, DGE_FLOW_TEXT_OD_LAYERED = 1, DGE_FLOW_TEXT_MATRIX = 2 };
+typedef struct dge_flow_slices {
+    int32_t T;                    /* K == 0: the slots of dge_flows_slot_edges(T, mode)                     */
+    int32_t mode;
+    int32_t K;                    /* K >= 1: the windows win[0 .. K) of dge_flows_window_edges; T = mode = 0 */
+    int32_t reserved;             /* 0                                                                      */
+    const dge_hour_window* win;
+} dge_flow_slices;                /* 24 bytes */
+typedef struct dge_flow_text_info {
+    int64_t bytes;
+    int64_t lines;
+    int64_t edges;                /* table-derived entries that were spelled with their weight              */
+    int64_t zeros;                /* MATRIX: entries written as "0"                                         */
+    int32_t slices;               /* texts produced                                                         */
+    int32_t reserved;
+    double  kernel_ms;            /* as in dge_seq_out_info: the edges' passes, sizing, every slab's emit   */
+    double  write_ms;             /* the slab loops: copies to pinned memory and write() / memcpy           */
+} dge_flow_text_info;             /* 56 bytes */
+/* one text into host memory; slice is ignored (must be 0) for OD_LAYERED.  text == NULL with cap == 0: size query */
+int  dge_flows_to_text(const dge_flows* f, const dge_flow_slices* s, int32_t kind, int32_t slice, const uint8_t* select, int32_t sep,
+                       char* text, int64_t cap, int64_t* n_bytes /* required */, dge_flow_text_info* info /* may be NULL */);
+/* every slice to its own file: n_paths == number of slices (1 for OD_LAYERED); the edges are formed once */
+int  dge_flows_write_text(const dge_flows* f, const dge_flow_slices* s, int32_t kind, const uint8_t* select, int32_t sep,
+                          const char* const* paths, int32_t n_paths, dge_flow_text_info* info /* may be NULL */);
+/* in_flow / out_flow: host int64[cap * 24], region_index int64[cap]; cap too small: DGE_ERR_CAP with *n set; cap == 0 with nulls: size query */
+int  dge_flows_time_series(const dge_flows* f, const uint8_t* select, int64_t* in_flow, int64_t* out_flow, int64_t* region_index, int64_t cap, int64_t* n);
+int  dge_flows_time_series_text(const dge_flows* f, const uint8_t* select, char* text, int64_t cap, int64_t* n_bytes, dge_flow_text_info* info /* may be NULL */);
+int  dge_flows_write_time_series(const dge_flows* f, const uint8_t* select, const char* path, dge_flow_text_info* info /* may be NULL */);
+
 /* ---- taxi trip text in (new; additions only, DGE_VERSION unchanged): the lines the reference reads in TaxiTrip(String line) and ShortDate
  * (J/TaxiTrip.java:39-78,199-223; the loops J/TaxiTrip.java:123-143 and J/TaxiTripIterator.java:32-62) are parsed on the device (csrc/trip_text.hip, csrc/trip_parse.h)
  * and go into a flow table without per-trip work on the host.  The rule; the result is a pure function of the bytes, the format and the header flag — nothing
