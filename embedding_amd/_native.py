@@ -189,6 +189,18 @@ class FlowTextInfo(C.Structure):
                 ("kernel_ms", C.c_double), ("write_ms", C.c_double)]
 
 
+class MatrixReadOptions(C.Structure):
+    """struct dge_matrix_read_options (include/dge.h): sep is the byte's code; slab_bytes 0 is the default."""
+    _fields_ = [("sep", C.c_int32), ("reserved", C.c_int32), ("slab_bytes", C.c_int64)]
+
+
+class MatrixReadInfo(C.Structure):
+    """struct dge_matrix_read_info (include/dge.h) — what dge_flows_add_matrix_texts / dge_flows_add_matrix_files report."""
+    _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("rows", C.c_int64), ("values", C.c_int64), ("entries", C.c_int64), ("zeros", C.c_int64),
+                ("total", C.c_int64), ("pieces", C.c_int32), ("n", C.c_int32), ("tile_bytes", C.c_int32), ("slabs", C.c_int32), ("read_ms", C.c_double),
+                ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
 DGE_FLOW_TEXT_OD, DGE_FLOW_TEXT_OD_LAYERED, DGE_FLOW_TEXT_MATRIX = 0, 1, 2
 DGE_NMF_DIVERGENCE, DGE_NMF_EUCLIDEAN = 0, 1
@@ -246,6 +258,8 @@ SIGNATURES = {
     "dge_flows_time_series": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _P(_i64)]),
     "dge_flows_time_series_text": (_int, [_vp, _vp, _vp, _i64, _P(_i64), _P(FlowTextInfo)]),
     "dge_flows_write_time_series": (_int, [_vp, _vp, C.c_char_p, _P(FlowTextInfo)]),
+    "dge_flows_add_matrix_texts": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _P(MatrixReadOptions), _P(MatrixReadInfo)]),
+    "dge_flows_add_matrix_files": (_int, [_vp, _vp, _vp, _i32, _vp, _P(MatrixReadOptions), _P(MatrixReadInfo)]),
     "dge_regions_centroids": (_int, [_vp, _vp, _i64, _P(_i64)]),
     "dge_graph_add_spatial": (_int, [_vp, _vp, _i32, _dbl, _vp, _P(SpatialInfo)]),
     "dge_graph_add_spatial_points": (_int, [_vp, _vp, _vp, _i64, _i32, _dbl, _vp, _P(SpatialInfo)]),

@@ -27,7 +27,7 @@
 
 constexpr int TRI_WAVE = 64;                                 // gfx950: a wave is 64 lanes
 constexpr int TRI_WAVES = SEQ_BLOCK / TRI_WAVE;              // E12 edges a block lists
-enum { FW_PAIRS_12 = 0, FW_PAIRS_23, FW_PAIRS_31, FW_CANDIDATES, FW_OVER, FW_N };
+enum { FW_PAIRS_12 = 0, FW_PAIRS_23, FW_PAIRS_31, FW_CANDIDATES, FW_N };
 
 // ------------------------------------------------------------------------------------------ kernels
 struct WinCount { const uint64_t* key; const int32_t* hour_first; uint64_t R; int64_t n;
@@ -50,14 +50,6 @@ __global__ void __launch_bounds__(SEQ_BLOCK) k_win_items(const uint64_t* key, co
 __global__ void __launch_bounds__(SEQ_BLOCK) k_win_bounds(const uint64_t* key, int64_t n, uint64_t R, int64_t K, int64_t* first) {
     const int64_t w = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
     if (w <= K) first[w] = coo_lower_bound(key, n, (uint64_t)w * R * R);
-}
-
-// is any count above the limit?
-__global__ void __launch_bounds__(SEQ_BLOCK) k_win_over(const int64_t* cnt, int64_t n, int64_t limit, unsigned long long* counters) {
-    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
-    unsigned long long v[1] = {i < n && cnt[i] > limit ? 1ull : 0ull};
-    const int which[1] = {FW_OVER};
-    trip_count(v, which, counters);
 }
 
 // W[s, e] of window w in the sorted sums (ranks): absent = 0
@@ -260,30 +252,14 @@ extern "C" int dge_flows_add_entries(dge_flows* f, const int32_t* hour, const in
     if (n == 0) return DGE_OK;
     SeqRun R;
     SEQ_TRY(seq_open(R, rg->device, who));
-    dge_tmp<uint64_t> d_key, nkey;
-    dge_tmp<int64_t> d_cnt, ncnt;
-    dge_tmp<unsigned long long> counters;
-    int64_t nn = 0;
+    dge_tmp<uint64_t> d_key;
+    dge_tmp<int64_t> d_cnt;
     SEQ_TRY(seq_alloc(R, d_key, n, "the entries' keys"));
     SEQ_TRY(seq_alloc(R, d_cnt, n, "the entries' counts"));
-    SEQ_TRY(seq_alloc(R, counters, FW_N, "the counters"));
     DGE_HIP(hipMemcpyAsync(d_key.p, key.data(), (size_t)n * 8, hipMemcpyHostToDevice, R.stream));
     DGE_HIP(hipMemcpyAsync(d_cnt.p, count, (size_t)n * 8, hipMemcpyHostToDevice, R.stream));
-    DGE_HIP(hipMemsetAsync(counters.p, 0, FW_N * 8, R.stream));
     DGE_HIP(hipStreamSynchronize(R.stream));
-    SEQ_TRY(trip_join(R, f->d_key, f->d_cnt, f->n, d_key.p, d_cnt.p, n, Ru, nkey, ncnt, &nn));
-    SEQ_TRY(seq_kernels_begin(R));
-    hipLaunchKernelGGL(k_win_over, dim3(seq_grid(nn)), dim3(SEQ_BLOCK), 0, R.stream, ncnt.p, nn, (int64_t)FR_MAX_COUNT, counters.p);
-    SEQ_TRY(seq_kernels_end(R));
-    unsigned long long over = 0;
-    SEQ_TRY(seq_read_back(R, &over, counters.p + FW_OVER, 8));
-    DGE_HIP(hipGetLastError());
-    if (over) DGE_FAIL(DGE_ERR_RANGE, "%s: %llu keys would hold a total above 2^40", who, over);
-    // nothing can fail from here on
-    dge_dev_free(f->d_key); dge_dev_free(f->d_cnt);
-    f->d_key = nkey.release(); f->d_cnt = ncnt.release(); f->n = nn;
-    f->info.trips += added; f->info.mapped += added; f->info.entries = nn; f->info.kernel_ms += R.kernel_ms;
-    return DGE_OK;
+    return trip_commit_entries(R, f, d_key.p, d_cnt.p, n, added, (int64_t)FR_MAX_COUNT, who);
 }
 
 extern "C" int dge_flows_window_edges(const dge_flows* f, const dge_hour_window* win, int32_t K, int32_t* k, int64_t* src_id, int64_t* dst_id, int64_t* w, int64_t cap, int64_t* n) {

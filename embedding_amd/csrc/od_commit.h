@@ -144,7 +144,7 @@ namespace {
 }
 
 // what both entries check before a device is looked for (the pieces' own arguments are the caller's)
-int od_check(const dge_graph* g, const dge_names* names, const char* who) {
+[[maybe_unused]] int od_check(const dge_graph* g, const dge_names* names, const char* who) {
     if (names && !names->ptr.empty()) DGE_FAIL(DGE_ERR_ARG, "%s: names must be empty: it receives the vertex names, it holds %lld", who, (long long)names->ptr.size());
     if (!dge_graph_fresh(g)) DGE_FAIL(DGE_ERR_STATE, "%s: the graph must be fresh: it already holds edges, sources or reserved vertices", who);
     return DGE_OK;

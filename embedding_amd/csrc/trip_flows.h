@@ -1,6 +1,7 @@
-// trip_flows.h — the resident flow table and the passes over it that trip_map.hip (trips in, slots out) and flow_windows.hip (entries in, hour windows and
-// triplets out) share: the table's layout, the counters' block reduction, sort / reduce-by-key under a run's accounting, the join of a table with more
-// (key, count) pairs, and the decode of sorted (slice, rank, rank) keys into the arrays od_commit.h takes.  Everything is static, as in od_commit.h: each
+// trip_flows.h — the resident flow table and the passes over it that trip_map.hip (trips in, slots out), flow_windows.hip (entries in, hour windows and
+// triplets out) and matrix_read.hip (.matrix text in) share: the table's layout, the counters' block reduction, sort / reduce-by-key under a run's accounting,
+// the join of a table with more (key, count) pairs, the commit of such pairs into a table (trip_commit_entries: what dge_flows_add_entries ends with), and
+// the decode of sorted (slice, rank, rank) keys into the arrays od_commit.h takes.  Everything is static, as in od_commit.h: each
 // translation unit gets its own copy and the library exports nothing from here.  Outside the build stamp.
 #pragma once
 #include <algorithm>
@@ -42,6 +43,14 @@ static __global__ void __launch_bounds__(SEQ_BLOCK) k_slot_decode(const uint64_t
     dst_id[i] = id_by_rank[k % R];
     w_bits[i] = (uint64_t)__double_as_longlong((double)w[i]);     // round to nearest even: the binary64 nearest the decimal, as the .od reader gives
     iota[i] = i;
+}
+
+// is any count above the limit?
+static __global__ void __launch_bounds__(SEQ_BLOCK) k_win_over(const int64_t* cnt, int64_t n, int64_t limit, unsigned long long* over) {
+    const int64_t i = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
+    unsigned long long v[1] = {i < n && cnt[i] > limit ? 1ull : 0ull};
+    const int which[1] = {0};
+    trip_count(v, which, over);
 }
 
 namespace {
@@ -94,10 +103,35 @@ int trip_join(SeqRun& R, const uint64_t* old_key, const int64_t* old_cnt, int64_
     return DGE_OK;
 }
 
+// u >= 1 checked (key, count) pairs on the device into f, under one commit: the join, the test of every key's total against limit, the swap and the counters.
+// added: the sum of the counts.  On any error f is as it was.  dge_flows_add_entries (flow_windows.hip) and the .matrix reader (matrix_read.hip) end here.
+[[maybe_unused]] int trip_commit_entries(SeqRun& R, dge_flows* f, const uint64_t* add_key, const int64_t* add_cnt, int64_t u, int64_t added, int64_t limit, const char* who) {
+    const uint64_t Ru = (uint64_t)std::max<int64_t>(f->regions->R, 1);
+    dge_tmp<uint64_t> nkey;
+    dge_tmp<int64_t> ncnt;
+    dge_tmp<unsigned long long> over_at;
+    int64_t nn = 0;
+    SEQ_TRY(seq_alloc(R, over_at, 1, "the counters"));
+    DGE_HIP(hipMemsetAsync(over_at.p, 0, 8, R.stream));
+    SEQ_TRY(trip_join(R, f->d_key, f->d_cnt, f->n, add_key, add_cnt, u, Ru, nkey, ncnt, &nn));
+    SEQ_TRY(seq_kernels_begin(R));
+    hipLaunchKernelGGL(k_win_over, dim3(seq_grid(nn)), dim3(SEQ_BLOCK), 0, R.stream, ncnt.p, nn, limit, over_at.p);
+    SEQ_TRY(seq_kernels_end(R));
+    unsigned long long over = 0;
+    SEQ_TRY(seq_read_back(R, &over, over_at.p, 8));
+    DGE_HIP(hipGetLastError());
+    if (over) DGE_FAIL(DGE_ERR_RANGE, "%s: %llu keys would hold a total above 2^40", who, over);
+    // nothing can fail from here on
+    dge_dev_free(f->d_key); dge_dev_free(f->d_cnt);
+    f->d_key = nkey.release(); f->d_cnt = ncnt.release(); f->n = nn;
+    f->info.trips += added; f->info.mapped += added; f->info.entries = nn; f->info.kernel_ms += R.kernel_ms;
+    return DGE_OK;
+}
+
 struct SlotArrays { dge_tmp<int32_t> slot; dge_tmp<int64_t> src_id, dst_id, iota; dge_tmp<uint64_t> w_bits; };
 
 // sorted keys (slice, rank of src id, rank of dst id) with their weights -> the arrays od_commit takes and the caller's read-back gives
-int trip_slot_decode(SeqRun& R, const dge_flows* f, const uint64_t* okey, const int64_t* ow, int64_t n, SlotArrays& A) {
+[[maybe_unused]] int trip_slot_decode(SeqRun& R, const dge_flows* f, const uint64_t* okey, const int64_t* ow, int64_t n, SlotArrays& A) {
     SEQ_TRY(seq_alloc(R, A.slot, n, "the edges' slots"));
     SEQ_TRY(seq_alloc(R, A.src_id, n, "the edges' sources"));
     SEQ_TRY(seq_alloc(R, A.dst_id, n, "the edges' destinations"));

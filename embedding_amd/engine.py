@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_FLOW_TEXT_MATRIX, DGE_FLOW_TEXT_OD, DGE_FLOW_TEXT_OD_LAYERED, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowSlices, FlowTextInfo, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, SvmCfg, SvmInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
+from ._native import DGE_ERR_CAP, DGE_FLOW_TEXT_MATRIX, DGE_FLOW_TEXT_OD, DGE_FLOW_TEXT_OD_LAYERED, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowSlices, FlowTextInfo, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, MatrixReadInfo, MatrixReadOptions, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, SvmCfg, SvmInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
 from .evaluate import _info_dict, _select_mask
 
 
@@ -299,6 +299,13 @@ class Regions:
         self.ids = ids.copy()              # region index -> id (Flows.nmf names its rows with it)
         return self
 
+    @classmethod
+    def from_ids(cls, ids, device=0):
+        """Regions that are ids and nothing else: no rings, so no point lies in any of them.  What a host that holds only the reference's sortedId and its
+        .matrix or .od files needs to get a Flows (Flows.add_matrix, Flows.add_entries)."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        return cls.from_arrays(ids, np.zeros(len(ids) + 1, np.int64), np.zeros(1, np.int64), np.zeros((0, 2), np.float64), device=device)
+
     def close(self):
         if getattr(self, "_h", None):
             lib.dge_regions_free(self._h)
@@ -427,6 +434,31 @@ class Flows:
         if not (h.shape == s.shape == d.shape == c.shape and h.ndim == 1):
             raise ValueError("hour / src / dst / count are four arrays of one length")
         check(lib.dge_flows_add_entries(self._h, _ptr(h), _ptr(s), _ptr(d), _ptr(c), len(h)))
+
+    def add_matrix(self, paths_or_bytes, hours, sep=",", select=None, slab_bytes=0):
+        """.matrix adjacency text read and added on the device (include/dge.h: dge_flows_add_matrix_texts / dge_flows_add_matrix_files): one piece — a path, or a
+        bytes-like — or a sequence of pieces, and for each its hour (0 .. 23; an int for one piece).  A piece is n lines of n decimals joined by sep (",", " "
+        or a tab) over all regions in ascending id or those select marks, as matrix_text writes them; value j of line i, when > 0, adds itself to the count
+        of (hour, r_i, r_j).  The table stands where add_entries leaves it on those entries; on any error (DgeError naming kind, piece, offset, line and
+        column of the first offence) it is as it was.  -> the fields of struct dge_matrix_read_info.
+
+        What replaces matrixFactorization_tract.NMFfeatures (np.loadtxt of taxi-h%d.matrix, f[idx,:][:,idx], NMF) for a host that holds sortedId, the 24
+        files and the mask of the tracts it keeps:
+            flows = Flows(Regions.from_ids(sortedId))
+            flows.add_matrix(["taxi-h%d.matrix" % h for h in range(24)], range(24))
+            W, H, ids, info = flows.nmf(slot, T=24, select=mask)"""
+        kind, _keep, ptrs, sizes, n = _piece_args(paths_or_bytes)
+        hours = np.ascontiguousarray([hours] if np.isscalar(hours) else list(hours), np.int32)
+        if len(hours) != n:
+            raise ValueError("one hour per piece is needed")
+        opt = MatrixReadOptions(ord(sep), 0, int(slab_bytes))
+        select = self._select(select)
+        inf = MatrixReadInfo()
+        if kind == "texts":
+            check(lib.dge_flows_add_matrix_texts(self._h, ptrs, sizes, _ptr(hours), n, _ptr(select), C.byref(opt), C.byref(inf)))
+        else:
+            check(lib.dge_flows_add_matrix_files(self._h, ptrs, _ptr(hours), n, _ptr(select), C.byref(opt), C.byref(inf)))
+        return _info_dict(inf)
 
     @staticmethod
     def windows_cross_time(T):

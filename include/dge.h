@@ -380,6 +380,73 @@ int  dge_flows_time_series(const dge_flows* f, const uint8_t* select, int64_t* i
 int  dge_flows_time_series_text(const dge_flows* f, const uint8_t* select, char* text, int64_t cap, int64_t* n_bytes, dge_flow_text_info* info /* may be NULL */);
 int  dge_flows_write_time_series(const dge_flows* f, const uint8_t* select, const char* path, dge_flow_text_info* info /* may be NULL */);
 
+/* ---- .matrix adjacency text in (new; additions only, DGE_VERSION unchanged): the files DGE_FLOW_TEXT_MATRIX writes, and the reference's taxi-h%d.matrix that
+ * P/matrixFactorization_tract.py:35 reads with np.loadtxt(delimiter=",") and indexes by f[idx,:][:,idx] (P/flowFeatureGeneration_tract.py:29-40 and
+ * P/flowFeatureGeneration_CA.py:30-41 do the same), go back into a flow table on the device (csrc/matrix_read.hip, csrc/matrix_parse.h, csrc/matrix_feed.h).  The
+ * text streams through the device in slabs; only the values > 0 leave it, and nothing of size n^2 or one record per value is formed.  A text is BYTES.  The rule:
+ *   - PARAMETERS.  sep is ',', ' ' or '\t', the three separators of DGE_FLOW_TEXT_MATRIX.  select is one byte per region index, NULL meaning all R regions, as
+ *     in dge_flows_to_text; n is the number of selected regions and r_0 .. r_{n-1} are they in ascending id.
+ *   - LINES.  A line ends at '\n'; a '\r' directly before that '\n' belongs to the terminator.  The last line of a piece may lack its terminator; nothing
+ *     follows a final terminator.  No line crosses a piece.  A line of zero bytes is skipped: it is counted in info.lines and not in info.rows.  There is no
+ *     limit on a line's length.
+ *   - VALUES.  A non-empty line is values separated by exactly one sep byte; its VALUE COUNT is its separators + 1.  A value is 1 to 19 decimal digits; leading
+ *     zeros are allowed (007 is 7).  No sign, no blank, no fraction, no exponent: Integer.toString of a flow count and the writer's %lld both fall inside this.
+ *   - MEANING.  Piece k belongs to hour hour[k] in 0 .. 23; several pieces may share an hour.  Each piece must hold exactly n non-empty lines of exactly n
+ *     values.  Value j of non-empty line i, when > 0, adds itself to c(hour[k], r_i, r_j); the diagonal is included; zeros add nothing.
+ *   - THE TABLE AFTER A CALL stands bit for bit where dge_flows_add_entries leaves it on the same (hour, region index, region index, value) entries;
+ *     info.trips and info.mapped of dge_flows_info grow by the sum of the values, the other counters do not move.
+ *   - OFFENCES.  Each has a PLACE, a byte offset inside its piece.  The call reports the offence at the least (piece, offset), and of two at one place the one
+ *     listed first here.  The message names the kind, the piece (and its path), the offset, the LINE — 1 + the '\n' bytes of the piece in front of the place,
+ *     so empty lines count — and the COLUMN — the sep bytes between the start of that line and the place, so columns count from 0:
+ *       "<entry>: <kind> at piece <k>[ (<path>)], offset <o>, line <l>, column <c>[: ..]".
+ *        bad byte          anything that is not a digit, sep, '\n', or a '\r' directly followed by '\n'; a NUL is a bad byte.  Place: that byte.  DGE_ERR_IO.
+ *        empty value       a sep at the start of a line, or a sep, a terminator or the piece's end directly after a sep.  Place: that byte (of "\r\n" the
+ *                          '\r'), or the piece's size at the piece's end.  DGE_ERR_IO.
+ *        long value        the 20th consecutive digit.  Place: that digit.  DGE_ERR_IO.  A run of 20 digits or more is no value: it is never "above 2^40".
+ *        value above 2^40  a maximal run of 1 .. 19 digits greater than 2^40, whatever stands around it.  Place: its first byte, a leading zero included.
+ *                          DGE_ERR_RANGE.
+ *        ragged line       a non-empty line whose value count is not n.  Place: its terminator's first byte, or the piece's size.  DGE_ERR_IO, with the
+ *                          count found and the count expected.
+ *        too many rows     place: the first byte of non-empty line n + 1.  DGE_ERR_IO.
+ *        too few rows      place: the piece's size (0 for a piece without a byte).  DGE_ERR_IO.
+ *   - OTHER STATUSES.  A key's total above 2^40, or the values adding up beyond 2^62: DGE_ERR_RANGE, as in dge_flows_add_entries.  Null or negative arguments, a
+ *     bad sep, a bad hour, n_pieces < 1, a select array when R = 0, non-zero reserved fields and a slab_bytes that is neither 0 nor in 256 .. 16 MiB:
+ *     DGE_ERR_ARG; plain values are checked before handles, and all of it before a device is looked for or a file is opened.  A missing or unreadable file:
+ *     DGE_ERR_IO with its path.  Out of device memory: DGE_ERR_CAP.  On any error the table is as it was: all pieces are staged and there is one commit at the end.
+ *   - PURITY.  The result — table, counters, the offence reported — is a pure function of the bytes, hour, select and sep.  It does not depend on slab_bytes,
+ *     the tile size, launch geometry or timing.
+ *   - NOT CARRIED OVER: signs, floats (np.savetxt's default %.18e), padding blanks and headers are bad bytes here; the time-series text
+ *     (taxi-flow-time-series.txt is 1 602 short lines) has no device reader.
+ * dge_matrix_read_info: lines counts every line, rows the non-empty ones, values = rows * n, entries the values > 0, zeros the others, total the sum of the
+ * values; tile_bytes is the text one workgroup takes, slabs the slabs sent; read_ms is the host's reading into pinned memory, kernel_ms the kernels of the slabs
+ * and of the commit.  It is filled on success only. */
+typedef struct dge_matrix_read_options {
+    int32_t sep;                  /* ',', ' ' or '\t'                                                       */
+    int32_t reserved;             /* 0                                                                      */
+    int64_t slab_bytes;           /* 0: the default, 16 MiB (the most); else 256 at least                   */
+} dge_matrix_read_options;        /* 16 bytes */
+typedef struct dge_matrix_read_info {
+    int64_t bytes;                /* offset 0                                                               */
+    int64_t lines;                /* 8                                                                      */
+    int64_t rows;                 /* 16                                                                     */
+    int64_t values;               /* 24                                                                     */
+    int64_t entries;              /* 32: values > 0                                                         */
+    int64_t zeros;                /* 40                                                                     */
+    int64_t total;                /* 48: the sum of the values                                              */
+    int32_t pieces;               /* 56                                                                     */
+    int32_t n;                    /* 60                                                                     */
+    int32_t tile_bytes;           /* 64: bytes of text one workgroup takes                                  */
+    int32_t slabs;                /* 68                                                                     */
+    double  read_ms;              /* 72                                                                     */
+    double  kernel_ms;            /* 80                                                                     */
+} dge_matrix_read_info;           /* 88 bytes */
+/* texts[k]: n_bytes[k] bytes, piece k of hour hour[k] */
+int  dge_flows_add_matrix_texts(dge_flows* f, const char* const* texts, const int64_t* n_bytes, const int32_t* hour, int32_t n_pieces,
+                                const uint8_t* select, const dge_matrix_read_options* opt, dge_matrix_read_info* info /* may be NULL */);
+/* the same for files, streamed: the host holds two slabs of a file at a time */
+int  dge_flows_add_matrix_files(dge_flows* f, const char* const* paths, const int32_t* hour, int32_t n_pieces,
+                                const uint8_t* select, const dge_matrix_read_options* opt, dge_matrix_read_info* info /* may be NULL */);
+
 /* ---- taxi trip text in (new; additions only, DGE_VERSION unchanged): the lines the reference reads in TaxiTrip(String line) and ShortDate
  * (J/TaxiTrip.java:39-78,199-223; the loops J/TaxiTrip.java:123-143 and J/TaxiTripIterator.java:32-62) are parsed on the device (csrc/trip_text.hip, csrc/trip_parse.h)
  * and go into a flow table without per-trip work on the host.  The rule; the result is a pure function of the bytes, the format and the header flag — nothing
