@@ -58,6 +58,7 @@ template <typename T>
 struct dge_tmp {
     T* p = nullptr;
     dge_tmp() = default;
+    dge_tmp(std::nullptr_t) {}                         // `= nullptr` in a handle reads as the raw member did
     dge_tmp(const dge_tmp&) = delete;
     dge_tmp& operator=(const dge_tmp&) = delete;
     dge_tmp(dge_tmp&& o) noexcept : p(o.release()) {}
@@ -65,8 +66,11 @@ struct dge_tmp {
     ~dge_tmp() { if (p) (void)hipFree(p); }
     int alloc(size_t n) { if (p) { (void)hipFree(p); p = nullptr; } return dge_dev_alloc(&p, n); }
     T* release() { T* q = p; p = nullptr; return q; }
+    template <typename U>             // takes over the buffer of o, whose elements are as wide as T (bits parsed as uint32_t that are float32 from here on)
+    void adopt(dge_tmp<U>&& o) { static_assert(sizeof(U) == sizeof(T), "adopt: the element sizes differ"); if (p) (void)hipFree(p); p = reinterpret_cast<T*>(o.release()); }
     operator T*() const { return p; }
 };
+static_assert(sizeof(dge_tmp<float>) == sizeof(float*), "a dge_tmp member lies in a handle as the raw pointer did");
 
 // One alias slot as the walk kernel reads it: 32 bytes (two 16-byte loads of one aligned sector), the ONLY memory access of a walk
 // step.  nbr_alias already resolves alias[i] to the neighbour it points at ("alias == -1" -> nbr itself), and the slot carries the
@@ -142,11 +146,12 @@ static inline void dge_graph_reset(dge_graph* g) {
 // what the builders ask of the graph they fill (od_commit.h, spatial.hip): no edges, no reserved vertices, no sources
 static inline bool dge_graph_fresh(const dge_graph* g) { return g->coo.n == 0 && g->max_id < 0 && g->src.S == 0 && !g->src.srcv.p && g->od_regions.empty(); }
 
+// dge_walks and dge_vectors own their arrays as dge_tmp members: delete is the free; a creator builds the handle in a unique_ptr and releases it into *out last
 struct dge_walks {
     int device = 0;
     int64_t n = 0;
     int32_t L = 0;
-    int32_t* d = nullptr;
+    dge_tmp<int32_t> d = nullptr;
     uint64_t gen = 0;          // changes whenever the library writes the corpus (a trainer may keep what it derived from an unchanged one)
 };
 uint64_t dge_next_generation();
@@ -166,8 +171,8 @@ struct dge_vectors {
     int device = 0;
     int64_t rows = 0;
     int32_t dim = 0;
-    float* d = nullptr;
-    uint8_t* d_present = nullptr;
+    dge_tmp<float> d = nullptr;
+    dge_tmp<uint8_t> d_present = nullptr;
     int64_t n_present = 0;
 };
 

@@ -931,13 +931,12 @@ extern "C" int dge_sample_walks_device(const dge_graph* g, int64_t n_walks, int3
     if (!g || !out || n_walks < 0 || max_len <= 0 || first_index < 0) DGE_FAIL(DGE_ERR_ARG, "dge_sample_walks_device: bad argument");
     *out = nullptr;
     DGE_HIP(hipSetDevice(g->device));
-    dge_walks* w = new dge_walks();
+    std::unique_ptr<dge_walks> w(new dge_walks());
     w->device = g->device; w->n = n_walks; w->L = max_len; w->gen = dge_next_generation();
-    int rc = dge_dev_alloc(&w->d, (size_t)(n_walks * max_len));
-    if (rc) { delete w; return rc; }
-    rc = sample_walks_impl(g, n_walks, max_len, seed, rng_mode, first_index, w->d, draws_consumed);
-    if (rc) { dge_walks_free(w); return rc; }
-    *out = w;
+    int rc = w->d.alloc((size_t)(n_walks * max_len));
+    if (!rc) rc = sample_walks_impl(g, n_walks, max_len, seed, rng_mode, first_index, w->d, draws_consumed);
+    if (rc) return rc;
+    *out = w.release();
     return DGE_OK;
 }
 
@@ -969,15 +968,13 @@ extern "C" int dge_walks_from_host(int device, const int32_t* walks, int64_t n_w
     *out = nullptr;
     int rc = dge_require_device(device);
     if (rc) return rc;
-    dge_walks* w = new dge_walks();
+    std::unique_ptr<dge_walks> w(new dge_walks());
     w->device = device; w->n = n_walks; w->L = max_len; w->gen = dge_next_generation();
-    rc = dge_dev_alloc(&w->d, (size_t)(n_walks * max_len));
-    if (rc) { delete w; return rc; }
-    if (n_walks && hipMemcpy(w->d, walks, (size_t)(n_walks * max_len) * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
-        dge_walks_free(w);
+    rc = w->d.alloc((size_t)(n_walks * max_len));
+    if (rc) return rc;
+    if (n_walks && hipMemcpy(w->d, walks, (size_t)(n_walks * max_len) * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess)
         DGE_FAIL(DGE_ERR_DEVICE, "dge_walks_from_host: copy to the device failed");
-    }
-    *out = w;
+    *out = w.release();
     return DGE_OK;
 }
 
@@ -1010,6 +1007,5 @@ extern "C" int dge_walks_add_position_prefix(dge_walks* w, int32_t region_count)
 extern "C" void dge_walks_free(dge_walks* w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
-    dge_dev_free(w->d);
     delete w;
 }

@@ -76,11 +76,12 @@ int seq_ingest(SeqRun& R, const dge_names* names, const SeqOptions& opt, const c
 int seq_finish(SeqRun& R, dge_names* names, int intern, dge_walks** out, dge_seq_info* info, const char* who) {
     const int64_t T = R.T, P = R.P;
     if (R.max_len > 0x7fffffffLL) DGE_FAIL(DGE_ERR_RANGE, "%s: a line of %lld tokens does not fit a corpus row", who, (long long)R.max_len);
-    dge_tmp<int32_t> walks;
-    SEQ_TRY(seq_alloc(R, walks, R.rows * R.max_len, "the corpus"));
+    std::unique_ptr<dge_walks> w(new dge_walks());
+    w->device = R.device; w->n = R.rows; w->L = (int32_t)R.max_len;
+    SEQ_TRY(seq_alloc(R, w->d, R.rows * R.max_len, "the corpus"));
     SEQ_TRY(seq_kernels_begin(R));
-    DGE_HIP(hipMemsetAsync(walks.p, 0xFF, (size_t)std::max<int64_t>(R.rows * R.max_len, 1) * sizeof(int32_t), R.stream));
-    if (T > P) hipLaunchKernelGGL(k_seq_pack, dim3(seq_grid(T - P)), dim3(SEQ_BLOCK), 0, R.stream, R.tok_id.p, R.rowx.p, R.row_first.p, P, T, R.max_len, walks.p);
+    DGE_HIP(hipMemsetAsync(w->d.p, 0xFF, (size_t)std::max<int64_t>(R.rows * R.max_len, 1) * sizeof(int32_t), R.stream));
+    if (T > P) hipLaunchKernelGGL(k_seq_pack, dim3(seq_grid(T - P)), dim3(SEQ_BLOCK), 0, R.stream, R.tok_id.p, R.rowx.p, R.row_first.p, P, T, R.max_len, w->d.p);
     SEQ_TRY(seq_kernels_end(R));
     // ---- the new names' bytes
     const int64_t n_new = intern ? R.n_names - P : 0;
@@ -89,13 +90,12 @@ int seq_finish(SeqRun& R, dge_names* names, int intern, dge_walks** out, dge_seq
     SEQ_TRY(seq_new_names(R, R.tok_start.p, n_new, off, host_blob));
     // nothing can fail from here on: the names and the corpus change hands together
     if (n_new > 0) names_append(names, std::move(host_blob), off.data(), n_new);
-    dge_walks* w = new dge_walks();
-    w->device = R.device; w->n = R.rows; w->L = (int32_t)R.max_len; w->d = walks.release(); w->gen = dge_next_generation();
-    *out = w;
+    w->gen = dge_next_generation();
     if (info) {
         info->bytes = R.L.text_bytes; info->lines = R.lines; info->rows = R.rows; info->tokens = T - P; info->unknown = R.unknown; info->names_added = n_new;
         info->max_len = (int32_t)R.max_len; info->reserved = 0; info->read_ms = R.read_ms; info->kernel_ms = R.kernel_ms;
     }
+    *out = w.release();
     return DGE_OK;
 }
 

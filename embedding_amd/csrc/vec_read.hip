@@ -269,17 +269,17 @@ int vec_read(SeqRun& R, int header, dge_names* names, int intern, dge_vectors** 
     std::vector<int64_t> off;
     std::unique_ptr<char[]> host_blob;
     SEQ_TRY(seq_new_names(R, ent_start.p, n_new, off, host_blob));
+    std::unique_ptr<dge_vectors> v(new dge_vectors());
     DGE_HIP(hipStreamSynchronize(R.stream));
     // nothing can fail from here on: the names and the vectors change hands together
     if (n_new > 0) names_append(names, std::move(host_blob), off.data(), n_new);
-    dge_vectors* v = new dge_vectors();
-    v->device = R.device; v->rows = rows_out; v->dim = (int32_t)dim; v->d = reinterpret_cast<float*>(vals.release()); v->d_present = present.release();
+    v->device = R.device; v->rows = rows_out; v->dim = (int32_t)dim; v->d.adopt(std::move(vals)); v->d_present = std::move(present);
     v->n_present = n_data - dropped;
-    *out = v;
     if (info) {
         info->bytes = R.L.text_bytes; info->lines = R.lines; info->rows = n_data; info->values = n_data * dim; info->dropped = dropped; info->missing = rows_out - v->n_present;
         info->names_added = n_new; info->host_values = n_host; info->dim = (int32_t)dim; info->reserved = 0; info->read_ms = R.read_ms; info->kernel_ms = R.kernel_ms;
     }
+    *out = v.release();
     return DGE_OK;
 }
 
@@ -311,25 +311,23 @@ extern "C" int dge_vectors_from_host(int device, const float* rows, int64_t n_ro
     if (!out || n_rows < 0 || dim < 0 || (n_rows > 0 && dim > 0 && !rows)) DGE_FAIL(DGE_ERR_ARG, "dge_vectors_from_host: null or negative argument");
     *out = nullptr;
     SEQ_TRY(dge_require_device(device));
-    dge_tmp<float> d; dge_tmp<uint8_t> pr;
-    SEQ_TRY(d.alloc((size_t)n_rows * (size_t)dim));
-    SEQ_TRY(pr.alloc((size_t)n_rows));
-    if (n_rows * dim) DGE_HIP(hipMemcpy(d.p, rows, (size_t)n_rows * (size_t)dim * sizeof(float), hipMemcpyHostToDevice));
-    int64_t held = n_rows;
+    std::unique_ptr<dge_vectors> v(new dge_vectors());
+    v->device = device; v->rows = n_rows; v->dim = dim; v->n_present = n_rows;
+    SEQ_TRY(v->d.alloc((size_t)n_rows * (size_t)dim));
+    SEQ_TRY(v->d_present.alloc((size_t)n_rows));
+    if (n_rows * dim) DGE_HIP(hipMemcpy(v->d.p, rows, (size_t)n_rows * (size_t)dim * sizeof(float), hipMemcpyHostToDevice));
     if (n_rows) {
         if (present) {
             std::vector<uint8_t> norm((size_t)n_rows);
-            held = 0;
-            for (int64_t i = 0; i < n_rows; i++) { norm[(size_t)i] = present[i] ? 1 : 0; held += norm[(size_t)i]; }
-            DGE_HIP(hipMemcpy(pr.p, norm.data(), (size_t)n_rows, hipMemcpyHostToDevice));
+            v->n_present = 0;
+            for (int64_t i = 0; i < n_rows; i++) { norm[(size_t)i] = present[i] ? 1 : 0; v->n_present += norm[(size_t)i]; }
+            DGE_HIP(hipMemcpy(v->d_present.p, norm.data(), (size_t)n_rows, hipMemcpyHostToDevice));
         } else {
-            DGE_HIP(hipMemset(pr.p, 1, (size_t)n_rows));
+            DGE_HIP(hipMemset(v->d_present.p, 1, (size_t)n_rows));
             DGE_HIP(hipDeviceSynchronize());
         }
     }
-    dge_vectors* v = new dge_vectors();
-    v->device = device; v->rows = n_rows; v->dim = dim; v->d = d.release(); v->d_present = pr.release(); v->n_present = held;
-    *out = v;
+    *out = v.release();
     return DGE_OK;
 }
 
@@ -354,7 +352,5 @@ extern "C" int dge_vectors_to_host(const dge_vectors* v, float* out, uint8_t* pr
 extern "C" void dge_vectors_free(dge_vectors* v) {
     if (!v) return;
     (void)hipSetDevice(v->device);
-    dge_dev_free(v->d);
-    dge_dev_free(v->d_present);
     delete v;
 }

@@ -490,3 +490,47 @@ def test_counted_host_waits_of_the_graph_entries(dge):
     corpus = dge.WalkCorpus.from_host(np.zeros((256, 5), np.int32), 0)
     assert waits(lambda: g.sample_walks_into(corpus, 0, 256, 7, 0)) == 1        # 8cce4c7: 1
     assert waits(lambda: g.keep_top_k(1)) <= 3                     # 8cce4c7: 3 (least degree, compaction, the sources' refresh)
+
+
+def test_walk_handles_made_and_dropped_on_every_path(dge, oracle, tmp_path):
+    """Every creator of a walk corpus with no row and with one row, and the .seq reader refused after the device has worked (a NUL byte in the last line of the
+    last piece): the handle comes back null, the message names the entry, and the next good call on the device gives what the text says."""
+    import ctypes as C
+    W = dge.WalkCorpus
+    # from_host
+    for rows in (np.zeros((0, 4), np.int32), np.array([[3, 1, 2, -1]], np.int32)):
+        c = W.from_host(rows, 0)
+        assert c.shape == rows.shape and np.array_equal(c.to_host(), rows)
+        c.close()
+    # sample_walks_device
+    src, dst, w, sources = layered_graph(R=20, T=4, deg=3, seed=5)
+    og, dg = build_both(oracle, dge, src, dst, w, sources)
+    for n in (0, 1):
+        c = dg.sample_walks_device(n, 6, seed=9)
+        assert c.shape == (n, 6) and np.array_equal(c.to_host(), og.sample_walks(1, 6, seed=9, rng_mode=1)[:n])
+        c.close()
+    # from_seq
+    c, names, info = W.from_seq(b"")
+    assert c.shape[0] == 0 and c.to_host().size == 0 and len(names) == 0 and info["rows"] == 0
+    c.close()
+    c, names, info = W.from_seq(b"a b c\n")
+    assert c.to_host().tolist() == [[0, 1, 2]] and names.as_bytes() == [b"a", b"b", b"c"]
+    c.close()
+    ok, bad, good = (str(tmp_path / name) for name in ("ok.seq", "bad.seq", "good.seq"))
+    open(ok, "wb").write(b"a b c\nb a\n")
+    open(bad, "wb").write(b"c d\nd \0e\n")
+    open(good, "wb").write(b"c d\n")
+    names = dge.Names(["a"])
+    text = b"a b\nb \0c\n"
+    for entry, call in (("dge_walks_from_seq_text", lambda out: dge.lib.dge_walks_from_seq_text(0, text, len(text), names._h, 1, C.byref(out), None)),
+                        ("dge_walks_from_seq_files", lambda out: dge.lib.dge_walks_from_seq_files(0, (C.c_char_p * 2)(ok.encode(), bad.encode()), 2, names._h, 1, C.byref(out), None))):
+        out = C.c_void_p(0xdead)
+        assert call(out) == 7 and not out.value
+        msg = dge.lib.dge_last_error().decode()
+        assert entry in msg and "NUL" in msg, msg
+    assert names.as_bytes() == [b"a"]                                # a refused text adds no names
+    c, names, info = W.from_seq([ok, good], names=names)
+    from embedding_amd import io
+    want, want_names = io.read_seq([ok, good])                       # the host reader: "a", the name held before, is also the first it meets
+    assert np.array_equal(c.to_host(), want) and list(names) == want_names == ["a", "b", "c", "d"] and info["rows"] == len(want) == 3
+    c.close()

@@ -422,3 +422,42 @@ def test_a_ragged_row_is_named_as_before(dge, row):
     — at row 256 (text row 257 with the header: the second workgroup) and at the last row.  The message — offset, piece, line, column, counts — is the one
     the library gave before the kernel and the read-back were shared."""
     assert fails(dge, lambda: dge.Vectors.from_vec(ragged_text(row), header=True)) == RAGGED[row]
+
+
+def test_vector_handles_made_and_dropped_on_every_path(dge, tmp_path):
+    """Both creators of resident vectors with no row and with one row, and the .vec reader refused after the device has worked (a value that is no number in the
+    last line of the last piece): the handle comes back null, the message names the entry, and the next good call on the device gives what the text says."""
+    V = dge.Vectors
+    # from_host
+    for rows in (np.zeros((0, 3), np.float32), np.array([[1.5, -2.0, 0.25]], np.float32)):
+        v = V.from_host(rows)
+        assert v.shape == rows.shape and np.array_equal(v.to_host(), rows) and v.present().tolist() == [True] * len(rows)
+        v.close()
+    v = V.from_host(np.array([[7.0, 8.0]], np.float32), present=[0])
+    assert v.present().tolist() == [False]
+    v.close()
+    # from_vec
+    v, names, info = V.from_vec(b"")
+    assert v.shape == (0, 0) and len(names) == 0 and info["rows"] == 0
+    v.close()
+    v, names, info = V.from_vec(b"a 1.5 -2\n")
+    assert v.to_host().tolist() == [[1.5, -2.0]] and v.present().tolist() == [True] and names.as_bytes() == [b"a"]
+    v.close()
+    ok, bad, good = (str(tmp_path / name) for name in ("ok.vec", "bad.vec", "good.vec"))
+    open(ok, "wb").write(b"a 1 2\nb 3 4\n")
+    open(bad, "wb").write(b"c 5 6\nd 7 zz\n")
+    open(good, "wb").write(b"c 5 6\nd 7 0.5\n")
+    names = dge.Names(["b"])
+    text = b"a 1 2\nb 3 zz\n"
+    for entry, call in (("dge_vectors_from_vec_text", lambda out: dge.lib.dge_vectors_from_vec_text(0, text, len(text), 0, names._h, 1, C.byref(out), None)),
+                        ("dge_vectors_from_vec_files", lambda out: dge.lib.dge_vectors_from_vec_files(0, (C.c_char_p * 2)(ok.encode(), bad.encode()), 2, 0, names._h, 1, C.byref(out), None))):
+        out = C.c_void_p(0xdead)
+        assert call(out) == 7 and not out.value
+        msg = dge.lib.dge_last_error().decode()
+        assert entry in msg and "not a decimal number" in msg, msg
+    assert names.as_bytes() == [b"b"]                                # a refused text adds no names
+    v, names, info = V.from_vec([ok, good], names=names)
+    from embedding_amd import io
+    by_name = {n: row for path in (ok, good) for n, row in zip(*io.read_vec(path))}                 # the host reader; row i is the vector of names[i]
+    assert list(names) == ["b", "a", "c", "d"] and np.array_equal(v.to_host(), np.stack([by_name[n] for n in names])) and v.present().all() and info["rows"] == 4
+    v.close()
