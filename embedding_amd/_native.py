@@ -201,7 +201,26 @@ class MatrixReadInfo(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+class CountsInfo(C.Structure):
+    """struct dge_counts_info (include/dge.h)."""
+    _fields_ = [("regions", C.c_int64), ("cols", C.c_int64), ("nonzero", C.c_int64), ("total", C.c_int64)]
+
+
+class TableReadOptions(C.Structure):
+    """struct dge_table_read_options (include/dge.h): sep is the byte's code; neg_col_offset -1 refuses a signed key; slab_bytes 0 is the default."""
+    _fields_ = [("sep", C.c_int32), ("skip_lines", C.c_int32), ("key_field", C.c_int32), ("key_lo", C.c_int32), ("key_hi", C.c_int32), ("col_lo", C.c_int32),
+                ("n_cols", C.c_int32), ("col_offset", C.c_int32), ("neg_col_offset", C.c_int32), ("reserved", C.c_int32), ("slab_bytes", C.c_int64),
+                ("reserved2", C.c_int64)]
+
+
+class TableReadInfo(C.Structure):
+    """struct dge_table_read_info (include/dge.h) — what dge_counts_add_table_texts / dge_counts_add_table_files report."""
+    _fields_ = [("bytes", C.c_int64), ("lines", C.c_int64), ("skipped", C.c_int64), ("empty", C.c_int64), ("rows", C.c_int64), ("foreign", C.c_int64),
+                ("values", C.c_int64), ("total", C.c_int64), ("pieces", C.c_int32), ("slabs", C.c_int32), ("read_ms", C.c_double), ("kernel_ms", C.c_double)]
+
+
 DGE_SLOTS_EVEN, DGE_SLOTS_AS_TRACTS = 0, 1
+DGE_COUNTS_PRESENT_ALL, DGE_COUNTS_PRESENT_NONZERO = 0, 1
 DGE_FLOW_TEXT_OD, DGE_FLOW_TEXT_OD_LAYERED, DGE_FLOW_TEXT_MATRIX = 0, 1, 2
 DGE_NMF_DIVERGENCE, DGE_NMF_EUCLIDEAN = 0, 1
 DGE_TRIPS_TYPE1, DGE_TRIPS_TYPE2, DGE_TRIPS_TYPE3 = 1, 2, 3
@@ -260,6 +279,16 @@ SIGNATURES = {
     "dge_flows_write_time_series": (_int, [_vp, _vp, C.c_char_p, _P(FlowTextInfo)]),
     "dge_flows_add_matrix_texts": (_int, [_vp, _vp, _vp, _vp, _i32, _vp, _P(MatrixReadOptions), _P(MatrixReadInfo)]),
     "dge_flows_add_matrix_files": (_int, [_vp, _vp, _vp, _i32, _vp, _P(MatrixReadOptions), _P(MatrixReadInfo)]),
+    "dge_counts_create": (_int, [_vp, _i32, _P(_vp)]),
+    "dge_counts_destroy": (None, [_vp]),
+    "dge_counts_info": (_int, [_vp, _P(CountsInfo)]),
+    "dge_counts_to_host": (_int, [_vp, _vp]),
+    "dge_counts_add_entries": (_int, [_vp, _vp, _vp, _vp, _i64]),
+    "dge_counts_add_table_texts": (_int, [_vp, _vp, _vp, _i32, _P(TableReadOptions), _P(TableReadInfo)]),
+    "dge_counts_add_table_files": (_int, [_vp, _vp, _i32, _P(TableReadOptions), _P(TableReadInfo)]),
+    "dge_counts_add_points": (_int, [_vp, _vp, _vp, _i64, _P(_i64)]),
+    "dge_counts_merge": (_int, [_vp, _vp, _vp, _P(_vp)]),
+    "dge_counts_vectors": (_int, [_vp, _i32, _i32, _i32, _i32, _P(_vp)]),
     "dge_regions_centroids": (_int, [_vp, _vp, _i64, _P(_i64)]),
     "dge_graph_add_spatial": (_int, [_vp, _vp, _i32, _dbl, _vp, _P(SpatialInfo)]),
     "dge_graph_add_spatial_points": (_int, [_vp, _vp, _vp, _i64, _i32, _dbl, _vp, _P(SpatialInfo)]),

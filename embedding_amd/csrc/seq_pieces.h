@@ -115,7 +115,10 @@ inline int64_t trip_last_terminator(const uint8_t* b, int64_t n) {
     return cr ? cr - b : a;
 }
 
-// the pieces' bytes, cut into slabs of whole lines (the head of trip_text.hip states what a slab is)
+// the pieces' bytes, cut into slabs of whole lines (the head of trip_text.hip states what a slab is).
+// A reader that reports byte offsets (TabReader::fill of the counts reader) reads k, at, n_tail, opens and pending_cr after next() to place a slab in its
+// piece: `at - n_tail` is the offset behind the bytes sent or dropped so far, `opens` after a call says the slab was its piece's last.  Keep those meanings,
+// or change fill() with them; it refuses with DGE_ERR_STATE when they no longer add up.
 struct TripFeeder {
     std::vector<SeqPiece>& pieces;
     int64_t S;

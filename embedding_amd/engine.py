@@ -4,7 +4,7 @@ import os
 
 import numpy as np
 
-from ._native import DGE_ERR_CAP, DGE_FLOW_TEXT_MATRIX, DGE_FLOW_TEXT_OD, DGE_FLOW_TEXT_OD_LAYERED, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, EvalResult, FlowSlices, FlowTextInfo, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, MatrixReadInfo, MatrixReadOptions, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, SvmCfg, SvmInfo, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
+from ._native import DGE_COUNTS_PRESENT_ALL, DGE_COUNTS_PRESENT_NONZERO, DGE_ERR_CAP, DGE_FLOW_TEXT_MATRIX, DGE_FLOW_TEXT_OD, DGE_FLOW_TEXT_OD_LAYERED, DGE_SLOTS_AS_TRACTS, DGE_SLOTS_EVEN, CountsInfo, EvalResult, FlowSlices, FlowTextInfo, FlowsInfo, HourWindow, KmeansCfg, KmeansInfo, LocateInfo, MatrixReadInfo, MatrixReadOptions, OdInfo, RegionsInfo, RidgeInfo, SeqInfo, SeqOutInfo, SpatialInfo, SvmCfg, SvmInfo, TableReadInfo, TableReadOptions, TrainConfig, TrainStats, TreeCfg, TreeInfo, TripTextInfo, TripTextOptions, TripletInfo, TripletRule, VecInfo, check, lib
 from .evaluate import _info_dict, _select_mask
 
 
@@ -685,6 +685,99 @@ class Flows:
         for k, s, d, x in zip(slot.tolist(), src.tolist(), dst.tolist(), w.tolist()):
             out[k].append(b"%d %d %d\n" % (s, d, x))
         return [b"".join(lines) for lines in out]
+
+
+class Counts:
+    """An int64 table [regions x n_cols] in HBM (struct dge_counts, include/dge.h): the per-tract rows the reference's label builders keep in a dict of numpy
+    arrays (getLEHDfeatures_helper, P/embeddingEvaluation_tract.py:512-536, and its siblings).  Row i belongs to the region with the i-th least id.  Every
+    call that fills the table stages and commits once: after a DgeError the table is as it was.
+
+    What replaces generateLEHD_ac_clusteringLabel("both") and the KMeans behind it:
+        counts = Counts(Regions.from_ids(sortedId), 40)
+        counts.add_table("il_rac_S000_JT00_2013.csv", skip_lines=1, key=(5, 11), cols=(8, 20))
+        counts.add_table("il_wac_S000_JT00_2013.csv", skip_lines=1, key=(5, 11), cols=(8, 20), col_offset=20)
+        labels, centres, info = counts.vectors(present="nonzero").kmeans(k)"""
+    ALL, NONZERO = DGE_COUNTS_PRESENT_ALL, DGE_COUNTS_PRESENT_NONZERO
+
+    def __init__(self, regions, n_cols, _handle=None):
+        h = _handle
+        if h is None:
+            h = C.c_void_p(0)
+            check(lib.dge_counts_create(regions._h, int(n_cols), C.byref(h)))
+        self._h = h
+        self.regions = regions
+        self.shape = (regions.info()["regions"], int(n_cols))       # (rows, columns): host numbers, no kernel behind them
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib.dge_counts_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def info(self):
+        inf = CountsInfo()
+        check(lib.dge_counts_info(self._h, C.byref(inf)))
+        return _info_dict(inf)
+
+    def to_host(self):
+        """-> int64 [regions, n_cols]"""
+        out = np.zeros(self.shape, np.int64)
+        check(lib.dge_counts_to_host(self._h, _ptr(out)))
+        return out
+
+    def add_entries(self, row, col, value):
+        """row / col int32, value int64 in 0 .. 2^40 — in any order, with repeats: value adds itself to cell (row, col) (dge_counts_add_entries)."""
+        r = np.ascontiguousarray(row, np.int32); c = np.ascontiguousarray(col, np.int32); v = np.ascontiguousarray(value, np.int64)
+        if not (r.shape == c.shape == v.shape and r.ndim == 1):
+            raise ValueError("row / col / value are three arrays of one length")
+        check(lib.dge_counts_add_entries(self._h, _ptr(r), _ptr(c), _ptr(v), len(r)))
+
+    def add_table(self, paths_or_bytes, sep=",", skip_lines=0, key_field=0, key=(0, 0), cols=(1, 1), col_offset=0, neg_col_offset=None, slab_bytes=0, return_info=False):
+        """Delimited text read and added on the device (include/dge.h: dge_counts_add_table_texts / dge_counts_add_table_files): one piece — a path, or a
+        bytes-like — or a sequence of pieces.  Of every line behind the skip_lines headers of its piece the key is characters [key[0], key[1]) of field
+        key_field (key[1] == 0: to the field's end), the values are the cols[1] fields from field cols[0] on, and value j adds itself to column
+        col_offset + j of the row whose region id is the key.  Lines whose key is no region's id are skipped (info["foreign"]).  neg_col_offset: the column
+        the values of a line whose key starts with '-' land at (None: such a key is an offence).  A DgeError names kind, piece, offset, line and field of
+        the first offence."""
+        kind, _keep, ptrs, sizes, n = _piece_args(paths_or_bytes)
+        opt = TableReadOptions(ord(sep), int(skip_lines), int(key_field), int(key[0]), int(key[1]), int(cols[0]), int(cols[1]), int(col_offset),
+                               -1 if neg_col_offset is None else int(neg_col_offset), 0, int(slab_bytes), 0)
+        inf = TableReadInfo()
+        if kind == "texts":
+            check(lib.dge_counts_add_table_texts(self._h, ptrs, sizes, n, C.byref(opt), C.byref(inf)))
+        else:
+            check(lib.dge_counts_add_table_files(self._h, ptrs, n, C.byref(opt), C.byref(inf)))
+        return _info_dict(inf) if return_info else None
+
+    def add_points(self, xy, col):
+        """xy float64 [n, 2], col int32 [n]: every point located as Regions.locate does adds 1 to (its region's row, col) — Tweets.mapTweetsIntoTracts
+        (J/Tweets.java:43-88) with col the hour.  -> the points in no region, which are dropped"""
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2); col = np.ascontiguousarray(col, np.int32)
+        if col.shape != (len(xy),):
+            raise ValueError("one column per point is needed")
+        dropped = C.c_int64(0)
+        check(lib.dge_counts_add_points(self._h, _ptr(xy), _ptr(col), len(col), C.byref(dropped)))
+        return dropped.value
+
+    def merge(self, groups, group_of):
+        """-> a new Counts over the Regions `groups` whose row g is the sum of the rows i with group_of[i] == g; -1 drops a row
+        (get_CAfeatures_from_tractFeatures, P/embeddingCaseStudy_CA.py:56-74)."""
+        g = np.ascontiguousarray(group_of, np.int32)
+        if g.shape != (self.shape[0],):
+            raise ValueError("group_of must hold one entry per row")
+        h = C.c_void_p(0)
+        check(lib.dge_counts_merge(self._h, groups._h, _ptr(g), C.byref(h)))
+        return Counts(groups, self.shape[1], _handle=h)
+
+    def vectors(self, cols=None, normalise=True, present="all"):
+        """Columns cols = (lo, n) (None: all) as a Vectors of float32 rows: row / row.sum() in float64, rounded once to float32, when normalise, else the
+        counts themselves.  present="nonzero" marks only the rows whose sum is not 0, which the evaluators then leave out."""
+        lo, n = (0, self.shape[1]) if cols is None else (int(cols[0]), int(cols[1]))
+        mode = {"all": DGE_COUNTS_PRESENT_ALL, "nonzero": DGE_COUNTS_PRESENT_NONZERO}[present]
+        h = C.c_void_p(0)
+        check(lib.dge_counts_vectors(self._h, lo, n, 1 if normalise else 0, mode, C.byref(h)))
+        return Vectors(h, self.regions.device)
 
 
 class Names:

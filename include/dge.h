@@ -416,7 +416,7 @@ int  dge_flows_write_time_series(const dge_flows* f, const uint8_t* select, cons
  *   - PURITY.  The result — table, counters, the offence reported — is a pure function of the bytes, hour, select and sep.  It does not depend on slab_bytes,
  *     the tile size, launch geometry or timing.
  *   - NOT CARRIED OVER: signs, floats (np.savetxt's default %.18e), padding blanks and headers are bad bytes here; the time-series text
- *     (taxi-flow-time-series.txt is 1 602 short lines) has no device reader.
+ *     (taxi-flow-time-series.txt is 1 602 short lines) is read by dge_counts_add_table_texts (the count tables below), not here.
  * dge_matrix_read_info: lines counts every line, rows the non-empty ones, values = rows * n, entries the values > 0, zeros the others, total the sum of the
  * values; tile_bytes is the text one workgroup takes, slabs the slabs sent; read_ms is the host's reading into pinned memory, kernel_ms the kernels of the slabs
  * and of the commit.  It is filled on success only. */
@@ -1336,7 +1336,7 @@ int  dge_tree_cv(int device, const float* features, int64_t n_rows, int32_t dim,
  *     read.  For a fit on one select mask applied to the other rows.
  *   - NOT TensorFlow's FTRL regressor.  NOT a standardising pipeline: the columns are taken as they are, and a host that wants them scaled scales them.  NOT
  *     order-free: it is a function of the used rows in row order, as k-means is.  No search for lambda, no k-fold, no wide-and-deep model
- *     (P/tf_hybrid_regression.py); reading the target tables stays with the host.
+ *     (P/tf_hybrid_regression.py); the target tables are read by the count tables' reader (dge_counts_*) where they are delimited text.
  *   - Device memory for the moments' block partials is bounded by a chunk of blocks (64; the knob DGE_TUNE_RIDGE_CHUNK sets it by hand), not by n; the result
  *     is the same for every chunk size.
  * ---------------------------------------------------------------------------------------------- */
@@ -1535,6 +1535,117 @@ enum {
 };
 int  dge_set_tuning(int32_t knob, int64_t value);
 int  dge_get_tuning(int32_t knob, int64_t* value);   /* -1 = the library's own rule */
+
+/* ------------------------------------------------------------------------------------------------
+ * Count tables (new; additions only, DGE_VERSION unchanged): the ground-truth tables the evaluators are scored against — a resident int64 table c[R][C] over a
+ * dge_regions handle, filled from delimited text, from points and from entries, merged along a region map and handed on as dge_vectors
+ * (csrc/table_read.hip, csrc/table_parse.h).  The reference builds them line by line on the host: getLEHDfeatures_helper
+ * (P/embeddingEvaluation_tract.py:512-536), generateLEHD_ac_clusteringLabel (:473-509), generateCrimeClusteringlabel (:435-449),
+ * generateTweetsClusteringlabel (:398-407), get_CAfeatures_from_tractFeatures (P/embeddingCaseStudy_CA.py:56-74), Tweets.mapTweetsIntoTracts
+ * (J/Tweets.java:43-88) and the read of taxi-flow-time-series.txt (P/caseStudy.py:44-48).  Each ends in row / row.sum() and KMeans: dge_counts_vectors and
+ * dge_kmeans_vectors.  Pickles and shapefiles stay with the host, which puts what it unpickled in through dge_counts_add_entries.  The rule:
+ *   - THE TABLE.  R is the regions' count; ROW i belongs to the region with the i-th least id (with ids given ascending, as Regions.from_ids usually gets
+ *     them, that is the region index).  1 <= C <= 1024.  Everything that fills the table is 64-bit integer addition: the table is a pure function of the
+ *     multiset of contributions — not of slab_bytes, launch geometry or timing.  A call stages its contributions and commits once: a call that would leave a
+ *     cell above 2^62, or whose own values add up to more than 2^62, is DGE_ERR_RANGE, and on ANY refusal the table is as it was.
+ *   - dge_counts_add_entries: host arrays row[], col[], value[] of n entries in any order, with repeats; 0 <= row < R, 0 <= col < C, 0 <= value <= 2^40, else
+ *     DGE_ERR_ARG naming the least offending position.  The independent way in, and the way back for what dge_counts_to_host gave.
+ *   - dge_counts_add_points: point i (x, y) is located by dge_regions_locate's rule — one region or none — and adds 1 to c[row of that region][col[i]].  Points
+ *     in no region are counted in *dropped.  Tweets.mapTweetsIntoTracts counts a point once for EVERY tract whose boundary contains it; this counts it once
+ *     (interior to several regions is no region, as in dge_regions_locate).  The hour column, time.substring(8, 10), is the host's to compute.
+ *   - dge_counts_merge: a NEW table over `groups` with c's C whose row g is the sum of the rows i of c with group_of[i] == g; group_of[i] is a row of the new
+ *     table or -1, which drops row i; anything else is DGE_ERR_ARG.  A sum above 2^62: DGE_ERR_RANGE.  The two region handles lie on one device.
+ *   - dge_counts_vectors: columns [col_lo, col_lo + n_cols) as float32 rows.  s_i is the exact sum of row i's selected columns (above 2^63 - 1:
+ *     DGE_ERR_RANGE).  normalise != 0: (float)((double)c / (double)s_i), each conversion and the division rounded to nearest even; a row with s_i == 0 is all
+ *     +0.0f.  normalise == 0: (float)c.  DGE_COUNTS_PRESENT_ALL marks every row present — POI and LEHD-od keep their zero rows (:411-432, :453-469);
+ *     DGE_COUNTS_PRESENT_NONZERO marks the rows with s_i != 0 — LEHD-ac and the CA merge drop the others (:498-505).  The crime file's float total column
+ *     is not read anywhere: normalise divides by the row's own sum.
+ *   - THE TEXT READER (dge_counts_add_table_texts / _files).  A text is BYTES, in pieces; no line crosses a piece.
+ *       LINES end at "\n", "\r\n" or a lone "\r" (the trip reader's rule and its feeder, csrc/seq_pieces.h).  The first skip_lines lines of every piece are
+ *         headers: counted in info.skipped and not looked at.  Lines of zero bytes are counted in info.empty and skipped.  A piece's last line may lack its
+ *         terminator.  A line of more than 65 536 bytes is the offence "long line"; nothing else of it is looked at.
+ *       FIELDS are cut at every sep byte (',', ' ' or a tab); there is no quoting.  Field numbers count from 0.  Only the key field and the value fields are
+ *         looked at; every other field's bytes pass unread but for the search for sep.
+ *       The KEY is bytes [key_lo, key_hi) of field key_field, clipped to the field's end; key_hi == 0 means to the field's end.  A leading '-' is the offence
+ *         "key sign" when neg_col_offset is -1; else the key is the digits behind it and the line's values land at column neg_col_offset instead of
+ *         col_offset ("id,in_0..in_23" / "-id,out_0..out_23" of the time-series text).  What remains is 1 .. 18 decimal digits.
+ *       VALUES are fields col_lo .. col_lo + n_cols - 1; value j adds itself to column col_offset + j (or neg_col_offset + j) of the row whose region id is the
+ *         key.  A value is 1 .. 19 decimal digits, at most 2^40; leading zeros are allowed.  No sign, no blank, no fraction.
+ *       FOREIGN KEYS.  A key that is no region's id skips the line and is counted in info.foreign — the reference's `if tid in keys`.  Such a line is still
+ *         checked for offences, so the verdict does not depend on the region set.
+ *       OFFENCES.  Each has a PLACE, a byte offset in its piece.  The call reports the one at the least (piece, offset), and of two at one place the one listed
+ *         first here.  The message names kind, piece (and path), offset, LINE — 1 + the lines of the piece in front — and FIELD — the sep bytes between the
+ *         line's start and the place:  "<entry>: <kind> at piece <k>[ (<path>)], offset <o>, line <l>, field <f>".
+ *           short line         fewer fields than the key and the values need.  Place: the line's end (its terminator's first byte, or the piece's size).
+ *           short key          the key field is shorter than key_lo + 1 bytes.  Place: the field's first byte.
+ *           bad key            no digit, a byte that is no digit, or a 19th digit.  Place: that byte, or where the first digit is missing.
+ *           key sign           place: the '-'.
+ *           empty value        place: the field's place (the sep or terminator that follows at once).
+ *           bad value byte     place: the field's first byte that is no digit, when it comes before a 20th digit.
+ *           long value         the 20th digit of a field.  Place: that digit.  Such a field is never "above 2^40".
+ *           value above 2^40   1 .. 19 digits greater than 2^40.  Place: the field's first byte.  DGE_ERR_RANGE; every other offence is DGE_ERR_IO.
+ *           long line          place: the line's first byte.
+ *         The offence reported does not depend on slab_bytes.
+ *       OTHER STATUSES.  Null or negative arguments, a bad sep, key_hi neither 0 nor above key_lo, key_lo or key_hi above 65 536, n_cols outside 1 .. 1024, a key field among the value fields, columns outside the table, neg_col_offset < -1,
+ *         non-zero reserved fields, n_pieces < 1 and a slab_bytes that is neither 0 nor at least 131 072 (the trip reader's range; above 1 GiB is 1 GiB):
+ *         DGE_ERR_ARG; plain values are checked before handles, and all of it before a device is looked for or a file is opened.  A missing file: DGE_ERR_IO
+ *         with its path.  Device memory: DGE_ERR_CAP.
+ * dge_table_read_info, filled on success only: lines counts every line, skipped the headers, empty the empty ones, rows the lines that reached the table,
+ * foreign those with a foreign key; values = rows * n_cols, total their sum; read_ms is the host's reading into pinned memory, kernel_ms the slabs' kernels. */
+typedef struct dge_counts dge_counts;     /* int64 [R x C], resident in HBM; holds a reference to its regions */
+enum { DGE_COUNTS_PRESENT_ALL = 0, DGE_COUNTS_PRESENT_NONZERO = 1 };
+struct dge_counts_info {
+    int64_t regions;              /* R                                                                      */
+    int64_t cols;                 /* C                                                                      */
+    int64_t nonzero;              /* cells != 0                                                             */
+    int64_t total;                /* the sum of all cells; INT64_MAX when it does not fit                   */
+};                                /* 32 bytes */
+typedef struct dge_table_read_options {
+    int32_t sep;                  /* offset 0: ',', ' ' or '\t'                                             */
+    int32_t skip_lines;           /* 4: header lines of every piece                                         */
+    int32_t key_field;            /* 8                                                                      */
+    int32_t key_lo;               /* 12                                                                     */
+    int32_t key_hi;               /* 16: 0 = to the field's end                                             */
+    int32_t col_lo;               /* 20: the first value field                                              */
+    int32_t n_cols;               /* 24                                                                     */
+    int32_t col_offset;           /* 28: value j lands in column col_offset + j                             */
+    int32_t neg_col_offset;       /* 32: -1 = a '-' in front of the key is an offence                       */
+    int32_t reserved;             /* 36: 0                                                                  */
+    int64_t slab_bytes;           /* 40: 0 = the default, 16 MiB                                            */
+    int64_t reserved2;            /* 48: 0                                                                  */
+} dge_table_read_options;         /* 56 bytes */
+typedef struct dge_table_read_info {
+    int64_t bytes;                /* offset 0                                                               */
+    int64_t lines;                /* 8                                                                      */
+    int64_t skipped;              /* 16                                                                     */
+    int64_t empty;                /* 24                                                                     */
+    int64_t rows;                 /* 32                                                                     */
+    int64_t foreign;              /* 40                                                                     */
+    int64_t values;               /* 48                                                                     */
+    int64_t total;                /* 56                                                                     */
+    int32_t pieces;               /* 64                                                                     */
+    int32_t slabs;                /* 68                                                                     */
+    double  read_ms;              /* 72                                                                     */
+    double  kernel_ms;            /* 80                                                                     */
+} dge_table_read_info;            /* 88 bytes */
+/* what the per-tract rows of the reference's label builders are kept in: replaces the dict of numpy rows of getLEHDfeatures_helper (:519-523) */
+int  dge_counts_create(const dge_regions* regions, int32_t n_cols, dge_counts** out);
+void dge_counts_destroy(dge_counts* c);
+int  dge_counts_info(const dge_counts* c, struct dge_counts_info* out);
+int  dge_counts_to_host(const dge_counts* c, int64_t* out /* R x C */);
+/* replaces pickle.load of a ready table (generatePOIClusteringlabel, :411-432): the host hands its cells over */
+int  dge_counts_add_entries(dge_counts* c, const int32_t* row, const int32_t* col, const int64_t* value, int64_t n);
+/* replace the line loops of getLEHDfeatures_helper (:512-536), generateCrimeClusteringlabel (:435-449), generateTweetsClusteringlabel (:398-407) and the
+   read of taxi-flow-time-series.txt (P/caseStudy.py:44-48) */
+int  dge_counts_add_table_texts(dge_counts* c, const char* const* texts, const int64_t* n_bytes, int32_t n_pieces, const dge_table_read_options* opt,
+                                dge_table_read_info* info /* may be NULL */);
+int  dge_counts_add_table_files(dge_counts* c, const char* const* paths, int32_t n_pieces, const dge_table_read_options* opt, dge_table_read_info* info /* may be NULL */);
+/* replaces Tweets.mapTweetsIntoTracts (J/Tweets.java:43-88); xy: host float64 [n x 2], col: host int32 [n] */
+int  dge_counts_add_points(dge_counts* c, const double* xy, const int32_t* col, int64_t n, int64_t* dropped /* may be NULL */);
+/* replaces get_CAfeatures_from_tractFeatures (P/embeddingCaseStudy_CA.py:56-74); group_of: host int32 [R] */
+int  dge_counts_merge(const dge_counts* c, const dge_regions* groups, const int32_t* group_of, dge_counts** out);
+/* replaces row / row.sum() (:505, :531) in front of KMeans */
+int  dge_counts_vectors(const dge_counts* c, int32_t col_lo, int32_t n_cols, int32_t normalise, int32_t present_mode, struct dge_vectors** out);
 
 /* ------------------------------------------------------------------------------------------------
  * Device self-test of the commit-lock protocol of update_policy 5 (new; no reference counterpart): n_workers groups
