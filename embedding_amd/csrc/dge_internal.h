@@ -153,8 +153,34 @@ struct dge_walks {
     int32_t L = 0;
     dge_tmp<int32_t> d = nullptr;
     uint64_t gen = 0;          // changes whenever the library writes the corpus (a trainer may keep what it derived from an unchanged one)
+    // The corpus's last ASYNCHRONOUS use: dge_model_train and dge_model_walk_and_train return with their launches queued on the model's stream and record `used`
+    // behind them (dge_walks_mark).  Every other entry that touches d goes behind it: dge_walks_order where it enqueues work, dge_walks_settle before a blocking
+    // copy.  A chain of marks on different streams holds, because a stream first orders itself behind the mark it replaces.  mutable: readers mark a const corpus.
+    mutable hipEvent_t used = nullptr;
+    mutable hipStream_t used_on = nullptr;
+    mutable bool used_pending = false;      // recorded, and no host wait of the library is known to have passed it
+    ~dge_walks() { if (used) (void)hipEventDestroy(used); }
 };
 uint64_t dge_next_generation();
+// `s` waits for the corpus's last asynchronous use; nothing to do when that use is on `s` itself.  No host wait.
+static inline int dge_walks_order(const dge_walks* w, hipStream_t s) {
+    if (w->used_pending && w->used_on != s) DGE_HIP(hipStreamWaitEvent(s, w->used, 0));
+    return DGE_OK;
+}
+// work that uses the corpus has just been queued on `s`
+static inline int dge_walks_mark(const dge_walks* w, hipStream_t s) {
+    if (!w->used) DGE_HIP(hipEventCreateWithFlags(&w->used, hipEventDisableTiming));
+    DGE_HIP(hipEventRecord(w->used, s));
+    w->used_on = s; w->used_pending = true;
+    return DGE_OK;
+}
+// the host waits for the corpus's last asynchronous use (one counted wait, and only while one is pending)
+static inline int dge_walks_settle(const dge_walks* w) {
+    if (w->used_pending) { DGE_HIP(hipEventSynchronize(w->used)); w->used_pending = false; }
+    return DGE_OK;
+}
+// a host wait that covers the last use has just been made (the device, or a stream that dge_walks_order put behind it)
+static inline void dge_walks_settled(const dge_walks* w) { w->used_pending = false; }
 
 // interned strings, id = position: a host object, no device involved.  seq_ingest.hip fills it, seq_write.hip reads ptr / len
 struct dge_names {

@@ -301,6 +301,7 @@ extern "C" int dge_model_eval_links(dge_model* m, const dge_walks* w, int64_t ro
     const int64_t n_steps = n_rows * (int64_t)std::max(w->L - 1, 0);
     if (n_steps == 0) return DGE_OK;
     DGE_HIP(hipSetDevice(m->device));
+    if ((rc = dge_walks_order(w, m->stream))) return rc;      // behind another model's launch that still writes the corpus
     int blocks; int64_t per_block;
     ev_geometry(m, n_steps, 64, &blocks, &per_block);
     dge_tmp<EvalPartial> d_part;
@@ -331,6 +332,7 @@ extern "C" int dge_model_eval_sgns(dge_model* m, const dge_walks* w, int64_t row
     const size_t lds = (size_t)groups * (size_t)w->L * sizeof(int32_t);
     if (lds > 49152) DGE_FAIL(DGE_ERR_ARG, "dge_model_eval_sgns: walks of %d tokens exceed the 12288 a workgroup can pack", w->L);
     DGE_HIP(hipSetDevice(m->device));
+    if ((rc = dge_walks_order(w, m->stream))) return rc;      // behind another model's launch that still writes the corpus
     int blocks; int64_t per_block;
     ev_geometry(m, n_rows, groups, &blocks, &per_block);
     dge_tmp<EvalPartial> d_part;

@@ -957,9 +957,11 @@ extern "C" int dge_sample_walks_into(const dge_graph* g, dge_walks* w, int64_t r
     if (g->device != w->device) DGE_FAIL(DGE_ERR_ARG, "dge_sample_walks_into: graph and corpus live on different devices");
     DGE_HIP(hipSetDevice(g->device));
     w->gen = dge_next_generation();
-    int rc = dge_launch_walks_strided(g, g->stream, w->d + row0 * w->L, n_walks, w->L, seed, first_index, nullptr);
+    int rc = dge_walks_order(w, g->stream);        // a model's queued launch may still read these rows: the graph's stream goes behind it, the host does not wait for it twice
+    if (!rc) rc = dge_launch_walks_strided(g, g->stream, w->d + row0 * w->L, n_walks, w->L, seed, first_index, nullptr);
     if (rc) return rc;
     DGE_HIP(hipStreamSynchronize(g->stream));
+    dge_walks_settled(w);
     return DGE_OK;
 }
 
@@ -982,6 +984,7 @@ extern "C" int dge_walks_to_host(const dge_walks* w, int32_t* out, int64_t cap_e
     if (!w || (!out && w->n > 0)) DGE_FAIL(DGE_ERR_ARG, "dge_walks_to_host: bad argument");
     if (cap_elems < w->n * w->L) DGE_FAIL(DGE_ERR_CAP, "dge_walks_to_host: buffer holds %lld of %lld tokens", (long long)cap_elems, (long long)(w->n * w->L));
     DGE_HIP(hipSetDevice(w->device));
+    if (int rc = dge_walks_settle(w)) return rc;   // the blocking copy below is ordered behind no model's stream by itself
     if (w->n) DGE_HIP(hipMemcpy(out, w->d, (size_t)(w->n * w->L) * sizeof(int32_t), hipMemcpyDeviceToHost));
     return DGE_OK;
 }
@@ -998,6 +1001,7 @@ extern "C" int dge_walks_add_position_prefix(dge_walks* w, int32_t region_count)
     if (!w || region_count <= 0) DGE_FAIL(DGE_ERR_ARG, "dge_walks_add_position_prefix: bad argument");
     if ((int64_t)region_count * w->L > 0x7fffffffLL) DGE_FAIL(DGE_ERR_RANGE, "position prefix overflows int32 ids");
     DGE_HIP(hipSetDevice(w->device));
+    if (int rc = dge_walks_settle(w)) return rc;   // stream 0 waits for no non-blocking stream: a model's queued launch on the corpus is waited for here
     w->gen = dge_next_generation();
     if (w->n) hipLaunchKernelGGL(k_position_prefix, dim3(dge_grid(w->n * w->L, 256)), dim3(256), 0, 0, w->d, w->n, w->L, region_count);
     DGE_HIP(hipDeviceSynchronize());

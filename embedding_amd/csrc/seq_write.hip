@@ -183,6 +183,7 @@ int sqw_run(const dge_walks* w, int64_t row0, int64_t n_rows, const dge_names* n
     SQW_TRY(dge_require_device(w->device));
     SqwRun R;
     SQW_TRY(R.open());
+    SQW_TRY(dge_walks_order(w, R.ks));                              // every kernel that reads the rows runs on ks: behind a model's launch that still writes them
     const int32_t L = w->L;
     const int32_t* walks = w->d + row0 * L;
     prefix = prefix ? 1 : 0;

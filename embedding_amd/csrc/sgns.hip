@@ -173,6 +173,10 @@ extern "C" int dge_count_tokens(const dge_walks* w, int64_t row0, int64_t n_rows
     DGE_HIP(hipSetDevice(w->device));
     int64_t n = n_rows * w->L;
     if (n == 0) return DGE_OK;
+    // d_counts is accumulated into: whatever the caller's streams still do to it comes first, and so does a model's launch that still writes the corpus
+    // (dge_model_walk_and_train) — the one wait for the device covers both; stream 0 is then ordered behind everything this call can depend on
+    DGE_HIP(hipDeviceSynchronize());
+    dge_walks_settled(w);
     unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_count_tokens, dim3(blocks), dim3(256), 0, 0, w->d + row0 * w->L, n, n_vertices, (unsigned long long*)d_counts);
     DGE_HIP(hipGetLastError());
@@ -558,7 +562,11 @@ extern "C" int dge_model_train(dge_model* m, const dge_walks* w, int64_t row0, i
     if (w->device != m->device) DGE_FAIL(DGE_ERR_ARG, "dge_model_train: corpus and model live on different devices");
     DGE_HIP(hipSetDevice(m->device));
     if (total_walks <= 0) total_walks = w->n;
-    return train_rows(m, w->d + row0 * w->L, n_rows, w->L, walk_index_base, epoch, words_before, words_scale, total_walks, w->gen);
+    // the launch is left queued: it goes behind a launch of another model that still writes the corpus, and the corpus remembers it (dge_internal.h)
+    int rc = dge_walks_order(w, m->stream);
+    if (!rc) rc = train_rows(m, w->d + row0 * w->L, n_rows, w->L, walk_index_base, epoch, words_before, words_scale, total_walks, w->gen);
+    if (!rc) rc = dge_walks_mark(w, m->stream);
+    return rc;
 }
 
 extern "C" int dge_model_walk_and_train(dge_model* m, const dge_graph* g, dge_walks* w, int64_t row0, int64_t n_rows, int64_t walk_seed,
@@ -568,13 +576,18 @@ extern "C" int dge_model_walk_and_train(dge_model* m, const dge_graph* g, dge_wa
     if (w->device != m->device || g->device != m->device) DGE_FAIL(DGE_ERR_ARG, "dge_model_walk_and_train: handles live on different devices");
     DGE_HIP(hipSetDevice(m->device));
     w->gen = dge_next_generation();
+    int rc = dge_walks_order(w, m->stream);      // the rows are written: behind every launch of another model that still reads them
+    if (rc) return rc;
     EventPair ev;
-    int rc = timing_begin(m, ev, 1);
+    rc = timing_begin(m, ev, 1);
     if (rc) return rc;
     rc = timing_end(m, ev, dge_launch_walks_strided(g, m->stream, w->d + row0 * w->L, n_rows, w->L, walk_seed, walk_index_base, nullptr));
+    if (!rc) rc = dge_walks_mark(w, m->stream);  // (the walk kernel is queued whatever becomes of the training launch)
     if (rc) return rc;
     if (total_walks <= 0) total_walks = w->n;
-    return train_rows(m, w->d + row0 * w->L, n_rows, w->L, walk_index_base, epoch, words_before, words_scale, total_walks, w->gen);
+    rc = train_rows(m, w->d + row0 * w->L, n_rows, w->L, walk_index_base, epoch, words_before, words_scale, total_walks, w->gen);
+    if (!rc) rc = dge_walks_mark(w, m->stream);
+    return rc;
 }
 
 extern "C" int dge_train_sgns_device(const dge_walks* w, const dge_train_config* cfg, dge_model** out) {

@@ -260,6 +260,7 @@ void locate_counters(const unsigned long long* c, int64_t points, double ms, dge
 int regions_locate(const dge_regions* rg, const double* xy, int64_t n, int32_t* region, dge_locate_info* info, bool on_device, const char* who) {
     if (!rg || n < 0 || (n > 0 && (!xy || !region))) DGE_FAIL(DGE_ERR_ARG, "%s: null or negative argument", who);
     SEQ_TRY(dge_require_device(rg->device));
+    if (on_device && n > 0) DGE_HIP(hipDeviceSynchronize());      // the caller's points may still be in flight on a stream of theirs; this call's stream is non-blocking
     SeqRun R;
     SEQ_TRY(seq_open(R, rg->device, who));
     dge_tmp<unsigned long long> counters;
@@ -291,6 +292,7 @@ int flows_add(dge_flows* f, const double* sxy, const double* exy, const int32_t*
     const dge_regions* rg = f->regions;
     SEQ_TRY(dge_require_device(rg->device));
     if (n == 0) return DGE_OK;
+    if (on_device) DGE_HIP(hipDeviceSynchronize());               // the caller's points and hours may still be in flight on a stream of theirs
     SeqRun R;
     SEQ_TRY(seq_open(R, rg->device, who));
     const int64_t cap = std::min(n, TRIP_CHUNK);

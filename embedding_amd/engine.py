@@ -343,7 +343,6 @@ class Regions:
             if xy.dtype != torch.float64 or not xy.is_cuda:
                 raise ValueError("a device tensor of float64 is expected")
             out = torch.empty(xy.numel() // 2, dtype=torch.int32, device=xy.device)
-            torch.cuda.synchronize(xy.device)
             check(lib.dge_regions_locate_device(self._h, _dev_ptr(xy), xy.numel() // 2, _dev_ptr(out), C.byref(inf)))
         return (out, _info_dict(inf)) if return_info else out
 
@@ -375,7 +374,6 @@ class Flows:
                 raise ValueError("device tensors of float64, float64 and int32 are expected")
             if not (s.numel() == e.numel() == 2 * h.numel()):
                 raise ValueError("start / end / hour lengths differ")
-            torch.cuda.synchronize(s.device)
             check(lib.dge_flows_add_trips_device(self._h, _dev_ptr(s), _dev_ptr(e), _dev_ptr(h), h.numel()))
             return
         s = np.ascontiguousarray(start_xy, np.float64).reshape(-1, 2); e = np.ascontiguousarray(end_xy, np.float64).reshape(-1, 2)

@@ -17,7 +17,19 @@
  *   - "host" pointers are ordinary process memory; "d_" pointers are device memory on the handle's
  *     device (e.g. a torch tensor's data_ptr()).  Handles work on their own non-blocking HIP stream: entry points that
  *     READ a caller's device buffer first wait for the device (hipDeviceSynchronize), entry points that WRITE one return
- *     after their stream has drained, so no stream handshake is needed on the caller's side.
+ *     after their stream has drained, so no stream handshake is needed on the caller's side.  (dge_count_tokens, which has no handle with a stream,
+ *     does both around a launch on stream 0.)
+ *   - Four entries RETURN WITH WORK STILL QUEUED, by design: dge_model_train and dge_model_walk_and_train (on the model's stream; the zero-wait episode of
+ *     the block schedule rests on it), dge_model_export/import_partition_async and dge_model_ring_pass (their own sections say what orders a caller's stream).
+ *     Later calls on the SAME model are ordered by its stream.  Other handles are ordered through the CORPUS: a dge_walks remembers its last queued use with an
+ *     event recorded on the stream that made it, and every other entry that touches the corpus goes behind that event — another model's train,
+ *     walk_and_train, eval_links and eval_sgns, dge_sample_walks_into and the .seq writer make their stream wait for it (no host wait is added);
+ *     dge_walks_to_host and dge_walks_add_position_prefix wait for it on the host; dge_count_tokens waits for the device.  So a corpus may be read, written
+ *     again or re-sampled right behind a queued launch without a handshake.  NOT covered: the raw pointer dge_walks_info hands out (the caller orders its own
+ *     reads), and a graph changed (add_edges, build_alias, ..) while a queued dge_model_walk_and_train still reads its tables: read the model's stats, or
+ *     synchronise dge_model_stream, first.  dge_walks_free and the other *_free behind a queued launch are safe: hipFree waits for the device.
+ *   - dge_graph_set_stream / dge_model_set_stream drain the handle's present stream, then move its work to the caller's; the handle never destroys a stream
+ *     it was given, and the rules above hold on it unchanged (a null stream is stream 0).
  *   - Handles are not thread-safe; the reference's walk API is single-threaded
  *     (J/CrossTimeGraph.java:134-140) and the trainer owns its workers (J/DeepWalk.java:75).
  */
