@@ -334,6 +334,7 @@ SIGNATURES = {
     "dge_model_reset_stats": (_int, [_vp]),
     "dge_model_schedule": (_int, [_vp, _P(_i32), _P(_i64), _P(_i32)]),
     "dge_model_kernel": (_int, [_vp, C.c_char_p, _i32]),
+    "dge_model_pair_loop": (_int, [_vp, _P(_i32), _P(_i32)]),
     "dge_model_lock_stats": (_int, [_vp, _P(_i64), _P(_i64), _P(_i64)]),
     "dge_model_score_pairs": (_int, [_vp, _vp, _vp, _i64, _vp]),
     "dge_model_eval_links": (_int, [_vp, _vp, _i64, _i64, _i32, C.c_uint64, _P(EvalResult)]),

@@ -700,6 +700,14 @@ extern "C" int dge_model_kernel(const dge_model* m, char* buf, int32_t cap) {
     return DGE_OK;
 }
 
+extern "C" int dge_model_pair_loop(const dge_model* m, int32_t* loop, int32_t* slots) {
+    if (!m) DGE_FAIL(DGE_ERR_ARG, "dge_model_pair_loop: null model");
+    if (!m->has_plan) DGE_FAIL(DGE_ERR_STATE, "dge_model_pair_loop: nothing has been trained yet");
+    if (loop) *loop = m->last_plan.window ? 1 : 0;
+    if (slots) *slots = m->last_plan.window ? m->last_plan.win_slots : 0;
+    return DGE_OK;
+}
+
 extern "C" int dge_model_reset_stats(dge_model* m) {
     if (!m) DGE_FAIL(DGE_ERR_ARG, "dge_model_reset_stats: null model");
     int rc = dge_drain_events(m);

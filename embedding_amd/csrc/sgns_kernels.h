@@ -1417,6 +1417,428 @@ k_sgns_train_locked(TrainParams p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------ the walk-window pair loop of the relaxed commit-lock trainer
+// (k_sgns_train_window: what TrainPlan::window launches under the name k_sgns_train_locked<relaxed>; it uses that kernel's primitives)
+//
+// k_sgns_train_locked locks, reads, writes and unlocks the pair's syn0 row for every pair: 14 of the pair's 85 requests at the L2's memory side, although a token is
+// context to ~16 centres of its walk.  Here the pair's syn0 row is READ without a lock (agent scope, as the centre's row always was), the pair's update is parked in
+// LDS per (walk, position), and a walk's rows are written once, under their locks, when the walk's last centre is done: 4 requests a pair instead of 14, plus
+// L x 14 per walk.  No syn0 lock in the pair, no second commit wait, no pair retry.
+//
+// Geometry: ONE workgroup of 768 threads a compute unit — 48 sixteen-lane workers, three waves a SIMD as before — so that the sigmoid table and the table's run form
+// are held once, and what is left of the 160 KB holds a WINDOW of walk slots.  A slot: the walk's syn0 deltas (position x row element, in the layout of the centre
+// delta: index 64q + 16 * component + lane holds element 64q + 4 * lane + component), its tokens, length, learning rate and RNG base, a hand-out counter and a
+// completion counter.  The work unit is ONE CENTRE of one walk: no worker is tied to a walk, none idles at a walk's end.
+//
+// A slot's life:   free (claim 0, next CLOSED)
+//               -> loading (claim 1 by compare-and-swap; the claimer takes the next walk, writes tokens, zeroes the deltas)
+//               -> open (next = 0 behind a release: workers take centre numbers with an atomic add on `next`; a number below the length is a centre)
+//               -> handed out (next >= length) -> complete (the worker whose increment of `done` reaches the length flushes the rows, in try-lock rounds)
+//               -> free (next = CLOSED, then claim = 0).
+// What keeps it from hanging: (1) no worker waits for a row lock while it holds one (rounds take what they win, commit, drop, ask again); (2) a worker that waits
+// for a slot or for work holds no row lock — and waits by going round the MAIN loop, never in a loop of its own: the four workers of a wave diverge, and a loop that
+// waited for something a worker of the same wave must do would never let that worker run; (3) no __syncthreads behind the prologue.  Workers leave when the walks
+// are exhausted and no slot has a centre left or is being loaded; every slot is flushed by whoever completes it, so the last one out has nothing to do.
+
+#define WIN_WORKERS 48
+#define WIN_THREADS (WIN_WORKERS * 16)
+#define WIN_MAX_SLOTS 16
+#define WIN_CLOSED (1 << 24)
+#define WIN_FLUSH_LANES 13
+static_assert(WIN_WORKERS == DGE_WIN_WORKERS && WIN_MAX_SLOTS == DGE_WIN_MAX_SLOTS, "sgns_plan.h sizes the window's LDS");
+
+extern __shared__ __attribute__((aligned(16))) float s_win[];
+
+#define WIN_LD(x) __hip_atomic_load(&(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+#define WIN_ST(x, v) __hip_atomic_store(&(x), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
+
+// the ballot of this worker's 16 lanes
+__device__ __forceinline__ unsigned win_ballot16(bool b) { return (unsigned)(__ballot(b) >> (threadIdx.x & 48)) & 0xFFFFu; }
+
+// Walk end: the slot's parked deltas go into their syn0 rows — try-lock rounds over the walk's positions, up to 13 at a time, rows loaded NEG_BATCH at a time,
+// one commit wait a round, the rows not won asked for again in the next round.  A token with two positions is flushed twice.  Nothing is held between rounds.
+template <int DCH>
+__device__ __forceinline__ void win_flush(const TableView& syn0, int* locks0, const float* sdelta, const int* stok, int len, int lane, int32_t filler_row) {
+    uint64_t pendm = len >= 2 ? (len >= 64 ? ~0ull : ((1ull << len) - 1ull)) : 0ull;      // (a walk of one token has no pair)
+    while (pendm) {
+        uint64_t m = pendm;
+        for (int j = 0; j < lane; j++) m &= m - 1ull;                 // lane j: the j-th position still pending
+        const int pos = (lane < WIN_FLUSH_LANES && m) ? (int)__builtin_ctzll(m) : -1;
+        const int32_t row = pos >= 0 ? stok[pos] : -1;
+        const bool won = pos >= 0 ? row_trylock(locks0, row) : false;
+        const unsigned gotl = win_ballot16(won);
+        for (int base = 0; base < WIN_FLUSH_LANES; base += NEG_BATCH) {
+            const unsigned got = (gotl >> base) & ((1u << NEG_BATCH) - 1u);
+            if (!got) continue;
+            int32_t tg[NEG_BATCH];
+            int ps[NEG_BATCH];
+            Row<DCH> rr[NEG_BATCH];
+#pragma unroll
+            for (int q = 0; q < NEG_BATCH; q++) { tg[q] = __shfl(row, (base + q) & 15, 16); ps[q] = __shfl(pos, (base + q) & 15, 16); }
+#pragma unroll
+            for (int q = 0; q < NEG_BATCH; q++) rowA_load<DCH, 16, false>(rr[q], syn0, ((got >> q) & 1u) ? tg[q] : filler_row, lane);
+#pragma unroll
+            for (int q = 0; q < NEG_BATCH; q++)
+                if ((got >> q) & 1u) {
+                    const float* d = sdelta + ps[q] * (DCH * 64) + lane;
+#pragma unroll
+                    for (int k = 0; k < DCH; k++) {
+                        rr[q].v[k].x += d[k * 64]; rr[q].v[k].y += d[k * 64 + 16]; rr[q].v[k].z += d[k * 64 + 32]; rr[q].v[k].w += d[k * 64 + 48];
+                    }
+                    rowA_store<DCH, 16, false>(rr[q], syn0, tg[q], lane);
+                }
+        }
+        row_commit_wait(0.f);
+        if (won) row_unlock<false>(locks0, row);
+#pragma unroll
+        for (int j = 0; j < WIN_FLUSH_LANES; j++) {
+            const int pj = __shfl(pos, j, 16);
+            if ((gotl >> j) & 1u) pendm &= ~(1ull << pj);
+        }
+        if (pendm && !gotl) __builtin_amdgcn_s_sleep(2);
+    }
+}
+
+template <int DCH>
+__global__ void __launch_bounds__(WIN_THREADS, 1)
+k_sgns_train_window(TrainParams p, int n_slots) {
+    __shared__ float s_exp[EXP_TABLE_SIZE];
+    __shared__ double s_run_base[DGE_RUN_MAX];
+    __shared__ uint32_t s_run_row[DGE_RUN_MAX + 1];
+    __shared__ uint32_t s_exc_slot[DGE_RUN_EXC];
+    __shared__ int32_t s_exc_row[DGE_RUN_EXC];
+    // the slots' control words
+    __shared__ int s_next[WIN_MAX_SLOTS];       // hand-out counter: a value below the length is a centre; WIN_CLOSED and more while the slot is not open
+    __shared__ int s_len[WIN_MAX_SLOTS];
+    __shared__ int s_done[WIN_MAX_SLOTS];       // centres completed
+    __shared__ int s_claim[WIN_MAX_SLOTS];      // 0 = free
+    __shared__ int s_seq[WIN_MAX_SLOTS];        // the order the slots were opened in: the oldest walk is served first
+    __shared__ float s_alpha[WIN_MAX_SLOTS];
+    __shared__ long long s_gbase[WIN_MAX_SLOTS];
+    __shared__ int s_seq_ctr, s_static_k, s_exhausted;
+    __shared__ unsigned s_plock[WIN_MAX_SLOTS * 2];      // one bit a position: whoever holds it adds to the position's delta
+
+    const bool use_runs = p.n_runs > 0;
+    if (use_runs) {
+        for (int i = threadIdx.x; i < DGE_RUN_MAX; i += blockDim.x) s_run_base[i] = p.run_base[i];
+        for (int i = threadIdx.x; i < DGE_RUN_MAX + 1; i += blockDim.x) s_run_row[i] = p.run_row[i];
+        for (int i = threadIdx.x; i < DGE_RUN_EXC; i += blockDim.x) { s_exc_slot[i] = p.exc_slot[i]; s_exc_row[i] = p.exc_row[i]; }
+    }
+    for (int i = threadIdx.x; i < EXP_TABLE_SIZE; i += blockDim.x) s_exp[i] = p.exp_table[i];
+    if (threadIdx.x < WIN_MAX_SLOTS) {
+        s_next[threadIdx.x] = WIN_CLOSED; s_len[threadIdx.x] = 0; s_done[threadIdx.x] = 0; s_seq[threadIdx.x] = 0;
+        s_claim[threadIdx.x] = (int)threadIdx.x < n_slots ? 0 : 1;      // (slots the LDS does not hold are never free)
+    }
+    if (threadIdx.x < WIN_MAX_SLOTS * 2) s_plock[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) { s_seq_ctr = 0; s_static_k = 0; s_exhausted = 0; }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 15;
+    const int wk = threadIdx.x >> 4;
+    const int64_t worker = (int64_t)blockIdx.x * WIN_WORKERS + wk;
+    if (worker >= p.n_workers) return;
+
+    TableView syn0 = make_view(p.syn0, p.V, p.stride, p.big_seg_shift);
+    TableView syn1neg = make_view(p.syn1neg, p.V, p.stride, p.big_seg_shift);
+    syn0.valid = syn1neg.valid = (uint32_t)p.D;
+    int* const locks1 = p.locks;
+    int* const locks0 = p.locks + p.V + 1;
+
+    uint64_t mA = 1, cA = 0;
+    for (int j = 0; j <= lane; j++) { mA *= DGE_W2V_MULT; cA = cA * DGE_W2V_MULT + 11; }
+
+    const int L = p.L, W = p.W, K = p.K;
+    const int tok_pad = (L + 3) & ~3;
+    const int slot_floats = L * DCH * 64 + tok_pad;
+    float* const my_dh = s_win + (size_t)wk * 2 * DCH * 64;
+    float* const slots = s_win + (size_t)WIN_WORKERS * 2 * DCH * 64;
+    unsigned long long my_pairs = 0, my_words = 0;
+
+    int slot = 0, len = 0, i = 0, c = 1, c_hi = 0;
+    bool have = false;                // a centre is open
+    int32_t word = 0;
+    float alpha = 0.f;
+    uint64_t s = 0;
+    Row<DCH> h;
+    bool h_dirty = false;
+    int32_t pend_row = -1;
+    int cur_buf = 0;
+    float* sdelta = slots;
+    const int* stok = (const int*)slots;
+
+#define WIN_POSITIVE()                                                                                                 \
+    do {                                                                                                               \
+        {   /* the walk's parked updates of this context row: what the sequential loop would have written by now */   \
+            const float* sd_ = sdelta + c * (DCH * 64) + lane;                                                         \
+            _Pragma("unroll") for (int q_ = 0; q_ < DCH; q_++) {                                                       \
+                l1.v[q_].x += sd_[q_ * 64]; l1.v[q_].y += sd_[q_ * 64 + 16]; l1.v[q_].z += sd_[q_ * 64 + 32]; l1.v[q_].w += sd_[q_ * 64 + 48]; \
+            }                                                                                                          \
+        }                                                                                                              \
+        const float f_ = row_dot(l1, h);                                                                               \
+        const float g_ = sgns_g(f_, 1.0f, alpha, s_exp);                                                               \
+        row_axpy(neu, g_, h);                                                                                          \
+        row_axpy(h, g_, l1);                                                                                           \
+        float* d_ = my_dh + cur_buf * DCH * 64 + lane;                                                                 \
+        _Pragma("unroll") for (int q_ = 0; q_ < DCH; q_++) {                                                           \
+            d_[q_ * 64] = fmaf(g_, l1.v[q_].x, d_[q_ * 64]); d_[q_ * 64 + 16] = fmaf(g_, l1.v[q_].y, d_[q_ * 64 + 16]); \
+            d_[q_ * 64 + 32] = fmaf(g_, l1.v[q_].z, d_[q_ * 64 + 32]); d_[q_ * 64 + 48] = fmaf(g_, l1.v[q_].w, d_[q_ * 64 + 48]); \
+        }                                                                                                              \
+        h_dirty = true;                                                                                                \
+    } while (0)
+#define WIN_CLOSE_CENTRE()                                                                                             \
+    do {                                                                                                               \
+        if (h_dirty) {                                                                                                 \
+            h_dirty = false;                                                                                           \
+            if (pend_row >= 0) (void)flushA_blocking<DCH, false, false>(syn1neg, locks1, pend_row, my_dh + (cur_buf ^ 1) * DCH * 64 + lane, lane); \
+            pend_row = word; cur_buf ^= 1;                                                                             \
+        }                                                                                                              \
+    } while (0)
+
+    for (;;) {
+        bool new_centre = false;
+        if (c > c_hi) {
+            if (have) {
+                // the centre is done: its delta becomes the pending flush; the walk's completion counter moves behind this worker's LDS adds
+                WIN_CLOSE_CENTRE();
+                have = false;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                int d = 0;
+                if (lane == 0) d = atomicAdd(&s_done[slot], 1) + 1;
+                d = __shfl(d, 0, 16);
+                if (d == len) {      // the walk's last centre: this worker writes the walk's rows and frees the slot
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                    win_flush<DCH>(syn0, locks0, sdelta, stok, len, lane, p.filler_row);
+                    if (lane == 0) {
+                        WIN_ST(s_next[slot], WIN_CLOSED);
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                        WIN_ST(s_claim[slot], 0);
+                    }
+                }
+            }
+            // the oldest open slot with a centre left
+            int key = 0x7fffffff;
+            if (lane < n_slots) {
+                const int nx = WIN_LD(s_next[lane]), ln = WIN_LD(s_len[lane]);
+                if (nx < ln) key = (WIN_LD(s_seq[lane]) << 4) | lane;
+            }
+            key = min(key, __shfl_xor(key, 1, 16));
+            key = min(key, __shfl_xor(key, 2, 16));
+            key = min(key, __shfl_xor(key, 4, 16));
+            key = min(key, __shfl_xor(key, 8, 16));
+            if (key == 0x7fffffff) {
+                // none: leave, wait, or open a slot with the next walk
+                const bool mine = lane < n_slots;
+                const int cl = mine ? WIN_LD(s_claim[lane]) : 1;
+                const unsigned freem = win_ballot16(mine && cl == 0);
+                const unsigned loadm = win_ballot16(mine && cl != 0 && WIN_LD(s_next[lane]) >= WIN_CLOSED);
+                if (WIN_LD(s_exhausted)) {
+                    if (!loadm) break;
+                    __builtin_amdgcn_s_sleep(4);
+                    continue;
+                }
+                if (!freem) { __builtin_amdgcn_s_sleep(4); continue; }
+                const int f = __builtin_ctz(freem);
+                int ok = 0;
+                if (lane == 0) ok = atomicCAS(&s_claim[f], 0, 1) == 0 ? 1 : 0;
+                ok = __shfl(ok, 0, 16);
+                if (!ok) continue;
+                // this worker loads the slot: the next walk of the launch-wide counter (or of the workgroup's own stride where the launch has none)
+                unsigned long long t = 0;
+                if (lane == 0) t = p.next_walk ? atomicAdd(p.next_walk, 1ull) : (unsigned long long)blockIdx.x + (unsigned long long)atomicAdd(&s_static_k, 1) * gridDim.x;
+                const int64_t w = (int64_t)shfl16_u64(t, 0);
+                int wl = 0;
+                if (w < p.n_rows) wl = min((int)p.len[w], L);
+                if (wl <= 0) {      // past the last walk, or an empty walk: the slot is free again
+                    if (lane == 0) {
+                        if (w >= p.n_rows) WIN_ST(s_exhausted, 1);
+                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                        WIN_ST(s_claim[f], 0);
+                    }
+                    continue;
+                }
+                my_words += (unsigned long long)wl;
+                float* const sl_d = slots + (size_t)f * slot_floats;
+                int* const sl_t = (int*)(sl_d + L * DCH * 64);
+                const int32_t* sen = p.sen + w * L;
+                for (int j = lane; j < L; j += 16) sl_t[j] = j < wl ? sen[j] : -1;
+                for (int j = lane; j < wl * DCH * 16; j += 16) ((float4*)sl_d)[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (lane == 0) {
+                    const int64_t wbw = p.wb[w];
+                    const int64_t done = p.words_done_base + (p.words_scale == 1.0 ? wbw : (int64_t)((double)wbw * p.words_scale));
+                    float a = (float)((double)p.alpha0 * (1.0 - (double)done / (double)(p.all_words + 1)));
+                    if (a < p.min_alpha) a = p.min_alpha;
+                    s_alpha[f] = a;
+                    s_gbase[f] = (long long)((p.gidx_base + w) * (int64_t)L);
+                    s_len[f] = wl;
+                    s_done[f] = 0;
+                    s_seq[f] = atomicAdd(&s_seq_ctr, 1);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // (every lane: its token and delta stores)
+                if (lane == 0) WIN_ST(s_next[f], 0);                        // open
+                continue;
+            }
+            {
+                const int sl = key & 15;
+                int t = WIN_CLOSED;
+                if (lane == 0) t = atomicAdd(&s_next[sl], 1);
+                t = __shfl(t, 0, 16);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                const int ln = WIN_LD(s_len[sl]);
+                if (t >= ln) continue;      // (another worker took the last one)
+                slot = sl; len = ln; i = t;
+            }
+            have = true;
+            sdelta = slots + (size_t)slot * slot_floats;
+            stok = (const int*)(sdelta + L * DCH * 64);
+            alpha = s_alpha[slot];
+            word = stok[i];
+            s = dge_mix64(p.seed + (uint64_t)((int64_t)s_gbase[slot] + i));
+            s = s * DGE_W2V_MULT + 11;
+            const int radius = W - (int)dge_fast_mod(s, (uint64_t)W, p.W_magic);
+            c = max(0, i - radius);
+            c_hi = min(len - 1, i + radius);
+            if (c_hi == i) c_hi--;
+            if (c == i) c++;
+            new_centre = true;
+            if (c > c_hi) continue;      // (a centre without a context: completed on the next trip)
+        }
+        const int32_t last = stok[c];
+
+        Row<DCH> l1, neu;
+        if (new_centre) {
+            // the previous centre's delta is still parked; when it belongs to THIS row it goes out first
+            if (pend_row == word) {
+                (void)flushA_blocking<DCH, false, false>(syn1neg, locks1, pend_row, my_dh + (cur_buf ^ 1) * DCH * 64 + lane, lane);
+                pend_row = -1;
+            }
+            rowA_load<DCH, 16, false>(h, syn1neg, word, lane);       // unlocked read: stale by at most the OTHER workers' updates in flight
+            float* d = my_dh + cur_buf * DCH * 64 + lane;
+#pragma unroll
+            for (int q = 0; q < DCH; q++) { d[q * 64] = 0.f; d[q * 64 + 16] = 0.f; d[q * 64 + 32] = 0.f; d[q * 64 + 48] = 0.f; }
+        }
+        // the pair's syn0 row: unlocked, in flight while the first round's try-locks travel; stale by the other workgroups' walks in flight
+        rowA_load<DCH, 16, false>(l1, syn0, last, lane);
+        row_zero(neu);
+        bool have_l1 = false;      // the positive target is trained in the pair's first round
+        int kd = 0;
+        do {    // chunks of up to LK_CHUNK negatives (at least one pass: the positive, also when K == 0)
+            const int kc = min(LK_CHUNK, K - kd);
+            int32_t t = -1;
+            {
+                const uint64_t sl = s * mA + cA;
+                if (lane < kc) {
+                    const uint64_t slt = dge_fast_mod(sl >> 16, (uint64_t)p.T, p.T_magic);
+                    t = use_runs ? neg_row_by_runs((uint32_t)slt, s_run_base, s_run_row, s_exc_slot, s_exc_row, p.n_exc, p.T_inv, p.V) : -2;
+                    if (t == -2) t = neg_table_row(p.ctab, slt);
+                    if (t == 0 && p.V > 1) t = (int32_t)(sl % (uint64_t)(p.V - 1)) + 1;
+                    if (t == word) t = -1;
+                }
+                if (kc > 0) s = shfl16_u64(sl, kc - 1);
+            }
+            if (lane == 13) t = pend_row;
+            unsigned pend13 = win_ballot16(lane < kc && t >= 0) & 0x1FFFu;
+            bool flush_pending = pend_row >= 0;
+            while (pend13 || !have_l1) {
+                // (a negative that drew the row whose flush is still pending lets the flush go first: word2vec order)
+                const bool want = (lane < kc && ((pend13 >> lane) & 1u) && !(flush_pending && t == pend_row)) || (lane == 13 && flush_pending);
+                const bool won = want ? row_trylock(locks1, t) : false;
+                const unsigned gotl = win_ballot16(won);
+                const bool got_l1 = !have_l1;
+                const unsigned got13 = gotl & 0x1FFFu & pend13;
+                const bool gotf = flush_pending && ((gotl >> 13) & 1u);
+                Row<DCH> fr;
+                if (flush_pending) rowA_load<DCH, 16, false>(fr, syn1neg, gotf ? pend_row : p.filler_row, lane);
+                have_l1 = true;
+                bool do_pos = got_l1;
+                for (int base = 0; base < kc; base += NEG_BATCH) {
+                    const unsigned got = (got13 >> base) & ((1u << NEG_BATCH) - 1u);
+                    if (!got) continue;
+                    int32_t tg[NEG_BATCH];
+                    Row<DCH> rr[NEG_BATCH];
+#pragma unroll
+                    for (int q = 0; q < NEG_BATCH; q++) tg[q] = __shfl(t, (base + q) & 15, 16);
+#pragma unroll
+                    for (int q = 0; q < NEG_BATCH; q++) rowA_load<DCH, 16, false>(rr[q], syn1neg, ((got >> q) & 1u) ? tg[q] : p.filler_row, lane);
+                    if (do_pos) { do_pos = false; WIN_POSITIVE(); }     // behind the batch's loads: they are in flight meanwhile
+#pragma unroll
+                    for (int q = 0; q < NEG_BATCH; q++)
+                        if ((got >> q) & 1u) {
+                            const float f = row_dot(l1, rr[q]);
+                            const float g = sgns_g(f, 0.0f, alpha, s_exp);
+                            row_axpy(neu, g, rr[q]);
+                            row_axpy(rr[q], g, l1);
+                            rowA_store<DCH, 16, false>(rr[q], syn1neg, tg[q], lane);
+                        }
+                }
+                if (do_pos) WIN_POSITIVE();                 // (no row of the chunk was won in this round, or K == 0)
+                if (gotf) {
+                    const float* d = my_dh + (cur_buf ^ 1) * DCH * 64 + lane;
+#pragma unroll
+                    for (int q = 0; q < DCH; q++) {
+                        fr.v[q].x += d[q * 64]; fr.v[q].y += d[q * 64 + 16]; fr.v[q].z += d[q * 64 + 32]; fr.v[q].w += d[q * 64 + 48];
+                    }
+                    rowA_store<DCH, 16, false>(fr, syn1neg, pend_row, lane);
+                }
+                row_commit_wait(0.f);
+                if (won) row_unlock<false>(locks1, t);
+                pend13 &= ~got13;
+                if (gotf) { flush_pending = false; pend_row = -1; if (lane == 13) t = -1; }
+                if (pend13) __builtin_amdgcn_s_sleep(2);
+            }
+            kd += LK_CHUNK;
+        } while (kd < K);
+
+        // The pair's update of its context row: parked in the walk's slot (other centres of the walk add to the same position).  LDS float atomics cost a
+        // quarter of the launch (8 a lane and pair: measured), so the position is taken with ONE try on its lock bit and updated with plain reads and writes;
+        // a pair that finds the position busy neither waits for it nor adds beside its holder: its update goes to the row itself, under the row's lock.
+        {
+            float* sd = sdelta + c * (DCH * 64) + lane;
+            unsigned* const lw = &s_plock[slot * 2 + (c >> 5)];
+            const unsigned bit = 1u << (c & 31);
+            int got = 0;
+            if (lane == 0) got = (atomicOr(lw, bit) & bit) ? 0 : 1;
+            got = __shfl(got, 0, 16);
+            if (got) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+                for (int q = 0; q < DCH; q++) {
+                    sd[q * 64] += neu.v[q].x; sd[q * 64 + 16] += neu.v[q].y; sd[q * 64 + 32] += neu.v[q].z; sd[q * 64 + 48] += neu.v[q].w;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                if (lane == 0) atomicAnd(lw, ~bit);
+            } else {
+                for (;;) {      // (nothing is held here)
+                    const bool won = lane == 0 ? row_trylock(locks0, last) : false;
+                    if (__shfl((int)won, 0, 16) != 0) {
+                        Row<DCH> cur;
+                        rowA_load<DCH, 16, false>(cur, syn0, last, lane);
+#pragma unroll
+                        for (int q = 0; q < DCH; q++) {
+                            cur.v[q].x += neu.v[q].x; cur.v[q].y += neu.v[q].y; cur.v[q].z += neu.v[q].z; cur.v[q].w += neu.v[q].w;
+                        }
+                        rowA_store<DCH, 16, false>(cur, syn0, last, lane);
+                        row_commit_wait(0.f);
+                        if (won) row_unlock<false>(locks0, last);
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(2);
+                }
+            }
+        }
+        my_pairs++;
+        c++;
+        if (c == i) c++;
+    }
+    // (every centre was closed before its worker looked for more work; what is left is the last centre's parked delta)
+    if (pend_row >= 0) (void)flushA_blocking<DCH, false, false>(syn1neg, locks1, pend_row, my_dh + (cur_buf ^ 1) * DCH * 64 + lane, lane);
+#undef WIN_POSITIVE
+#undef WIN_CLOSE_CENTRE
+    if (lane == 0) {
+        if (my_pairs) atomicAdd(&p.counters[0], my_pairs);
+        if (my_words) atomicAdd(&p.counters[1], my_words);
+    }
+}
+
 // ------------------------------------------------------------------------------------------ hierarchical softmax, a wave per centre (round 4)
 // k_sgns_train<.., HS> trains pair after pair: every (centre, context) pair climbs the centre's whole Huffman path, ~20 inner nodes of 512 bytes each read
 // AND updated per pair, the updates as memory-side float atomics — 10 KB of atomic traffic a pair at 1.13 TB/s: the bound of that kernel (0.49 of the
@@ -2033,7 +2455,12 @@ static inline void launch_train_b(const TrainParams& p, const TrainPlan& pl, hip
                 else hipLaunchKernelGGL((k_sgns_train_locked<DCH, true, BIG, false, false>), g, b, 0, st, p);
             } else {
                 if (pl.wdog) hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, false, true>), g, b, 0, st, p);      // (forced: with the watchdog)
-                else hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, false>), g, b, 0, st, p);
+                else if (pl.window) {      // the walk-window pair loop: one workgroup of 48 workers a compute unit, its LDS beyond 64 KB asked for per kernel
+                    if constexpr (DCH <= 2 && !BIG) {
+                        (void)hipFuncSetAttribute((const void*)k_sgns_train_window<DCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.win_shmem);
+                        hipLaunchKernelGGL((k_sgns_train_window<DCH>), dim3(pl.win_blocks), dim3(WIN_THREADS), pl.win_shmem, st, p, (int)pl.win_slots);
+                    }
+                } else hipLaunchKernelGGL((k_sgns_train_locked<DCH, false, BIG, false, false>), g, b, 0, st, p);
             }
             break;
         default: break;

@@ -199,6 +199,23 @@ static inline bool small_rows(const dge_train_config& cfg, const ScheduleStats& 
     return policy == 2 && cfg.use_hs == 0 && part_n <= 1 && cfg.dim > 16 && cfg.dim <= 32 && s.stride == 64 && L <= 64 && !big && knob[DGE_TUNE_SMALL_ROWS] != 0;
 }
 
+// The walk-window pair loop's LDS (sgns_kernels.h: k_sgns_train_window): one workgroup of 48 workers a compute unit has the CU's 160 KB.  Fixed: the sigmoid table (4 000 B), the
+// table's run form (25 092 B) and the slots' control words — 32 KB set aside — and the workers' centre-delta double buffers (48 x 2 rows).  A slot: L rows of
+// deltas and the walk's tokens.  At most 16 slots (a worker scans them with one lane each).
+#define DGE_LDS_BYTES 163840
+#define DGE_WIN_FIXED_BYTES 32768
+#define DGE_WIN_WORKERS 48
+#define DGE_WIN_MAX_SLOTS 16
+#define DGE_WIN_MIN_SLOTS 4
+static inline int64_t window_slot_bytes(int32_t stride, int32_t L) { return (int64_t)L * stride * 4 + (int64_t)((L + 3) & ~3) * 4; }
+static inline int window_slots(int32_t stride, int32_t L) {
+    const int64_t left = (int64_t)DGE_LDS_BYTES - DGE_WIN_FIXED_BYTES - (int64_t)DGE_WIN_WORKERS * 2 * stride * 4;
+    return (int)std::max<int64_t>(0, std::min<int64_t>(DGE_WIN_MAX_SLOTS, left / window_slot_bytes(stride, L)));
+}
+static inline size_t window_dyn_bytes(int32_t stride, int32_t L, int slots) {
+    return (size_t)((int64_t)DGE_WIN_WORKERS * 2 * stride * 4 + (int64_t)slots * window_slot_bytes(stride, L));
+}
+
 // ------------------------------------------------------------------------------------------ the plan
 // The trainer's forms; the flags below pick the template arguments (sgns_kernels.h, launch_train_b).
 enum class TrainForm { Sorted, InOrder, RowRmw, Atomics, SmallRows, Locked, HsCentre };
@@ -225,6 +242,12 @@ struct TrainPlan {
     uint64_t wd_ticks = 0;
     bool runs_off = false;        // the negative-sampling table, not its run form
     bool walk_counter = false;    // walks handed out by a launch-wide counter (TrainParams::next_walk)
+    // k_sgns_train_locked<relaxed> in its walk-window pair loop (k_sgns_train_window, sgns_kernels.h): its own geometry — blocks / threads / shmem above stay those of
+    // the per-pair loop, which the same plan would otherwise run
+    bool window = false;
+    int32_t win_slots = 0;
+    unsigned win_blocks = 0;
+    size_t win_shmem = 0;
     char error[512] = "";         // why plan_train refused
 
     // what dge_model_schedule reports as the update policy
@@ -546,6 +569,21 @@ static inline int plan_train(const dge_train_config& cfg, const ScheduleStats& s
         P.wd_ticks = (!forced_locks || knob[DGE_TUNE_WATCHDOG_MS] == 0) ? 0ull : (uint64_t)(budget_s * 1e8);
     }
     P.wdog = P.form == TrainForm::Locked && !P.hotmix && P.wd_ticks != 0;
+    // The walk-window pair loop: exactly the instantiation auto picks on a flat vocabulary (relaxed, rows of up to 128 floats, one table descriptor, no head, no
+    // block, no watchdog) with more than one worker, where at least four walks' deltas fit the LDS.  Everything else keeps the per-pair loop.
+    // (rows of 64 floats: only where the commit locks were asked for by hand.  Auto runs them four waves a SIMD in the per-pair loop — 16 384 workers against the
+    //  window's 12 288 — and that comparison has not been measured; the gain is measured at 128 floats, profiles/walk_window_ab.txt)
+    const bool win_width = s.stride == 128 || (s.stride == 64 && cfg.update_policy == 5);
+    if (P.form == TrainForm::Locked && !P.strict && !P.hotmix && !part && !P.wdog && !big && win_width && workers > 1 && L >= 1 && L <= 64) {
+        const int slots = window_slots(s.stride, L);
+        if (slots >= DGE_WIN_MIN_SLOTS) {
+            P.window = true;
+            P.win_slots = slots;
+            // (one workgroup a compute unit is all that is resident: more would only queue behind the first and, without the walk counter, train their share late)
+            P.win_blocks = (unsigned)std::min<int64_t>((workers + DGE_WIN_WORKERS - 1) / DGE_WIN_WORKERS, std::max(s.n_cus, 1));
+            P.win_shmem = window_dyn_bytes(s.stride, L, slots);
+        }
+    }
     // rows of 17 .. 32 floats under the atomics policy: half a wave a worker (k_sgns_train_small; one worker only when DGE_TUNE_SMALL_ROWS asks for it)
     if (small && P.form == TrainForm::Atomics && (workers > 1 || knob[DGE_TUNE_SMALL_ROWS] > 0)) {
         P.form = TrainForm::SmallRows;

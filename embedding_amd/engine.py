@@ -1443,6 +1443,12 @@ class SgnsModel:
         check(lib.dge_model_kernel(self._h, buf, 256))
         return buf.value.decode()
 
+    def pair_loop(self):
+        """{"loop", "slots"}: which pair loop the latest launch ran — 0 the per-pair syn0 lock, 1 the walk window (include/dge.h: dge_model_pair_loop)."""
+        a, b = C.c_int32(0), C.c_int32(0)
+        check(lib.dge_model_pair_loop(self._h, C.byref(a), C.byref(b)))
+        return {"loop": a.value, "slots": b.value}
+
     # ---- multi-GPU block schedule (include/dge.h: dge_model_set_partition)
     def set_partition(self, n_parts, ctx_part=0, tgt_part=0):
         check(lib.dge_model_set_partition(self._h, int(n_parts), int(ctx_part), int(tgt_part)))

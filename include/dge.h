@@ -819,6 +819,10 @@ int  dge_model_schedule(const dge_model* m, int32_t* update_policy, int64_t* wor
 /* ... and the trainer kernel (name and form) that launch ran, as text: e.g. "k_sgns_train_locked<relaxed>", "k_sgns_train_hsw<negatives under commit locks, 7 waves> (...)",
  * "k_sorted_phase (owner-computes: ...)".  The policy number alone does not say it (hierarchical softmax has three kernels). */
 int  dge_model_kernel(const dge_model* m, char* buf, int32_t cap);
+/* ... and which pair loop of it: 0 = every pair locks, reads, writes and unlocks its context (syn0) row (every kernel but the next), 1 = the walk-window loop of
+ * "k_sgns_train_locked<relaxed>" (csrc/sgns_kernels.h: k_sgns_train_window: the row read unlocked, a walk's syn0 updates parked in LDS and written once at the walk's end); *slots = the
+ * walks a workgroup keeps open (0 for loop 0).  The kernel's name does not say it. */
+int  dge_model_pair_loop(const dge_model* m, int32_t* loop, int32_t* slots);
 /* One block of the multi-GPU schedule under the lock kernels (k_sgns_train_locked<.., PART>), since the last dge_model_reset_stats: pairs that were put back because
  * their context row's lock was taken, lock rounds that left some wanted row unwon, and lock rounds in all — what a block's speed runs against (a block's live rows are
  * V / N per table: locks collide N times as often as on one GPU).  The one-GPU kernels do not count (they have no register to spare). */
