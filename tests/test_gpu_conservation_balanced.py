@@ -158,10 +158,11 @@ def _model_counts(dge, key, corpus):
     return counts
 
 
-def _check(dge, oracle, key, D, K, W=5, policy=0, workers=(0, 48), use_hs=False, knobs=None, kernel=None, reported=None, loose=()):
+def _check(dge, oracle, key, D, K, W=5, policy=0, workers=(0, 48), use_hs=False, knobs=None, kernel=None, reported=None, loose=(), launch=None):
     """One row of the matrix: a model from the corpus' counts, per worker count the two balanced states imported, one launch each, the tables compared.
     `kernel`: what dge_model_kernel must name with several workers (one worker under policy 0 runs in order), `reported`: the policy dge_model_schedule must report,
-    `loose`: the tables that are not exact by design with several workers (the module's docstring) — exact with one."""
+    `loose`: the tables that are not exact by design with several workers (the module's docstring) — exact with one.  `launch(m, corpus)`: trains the corpus in
+    the model's place (one launch of the whole corpus, and whatever the case asks of the model while the knobs are still set)."""
     ids, NV, _ = _bal_corpus(key)
     exp = _expected(oracle, key, D, W, K, use_hs)
     corpus = dge.WalkCorpus.from_host(ids, 0)
@@ -179,7 +180,7 @@ def _check(dge, oracle, key, D, K, W=5, policy=0, workers=(0, 48), use_hs=False,
             m.reset_stats()
             with dge.tuning(**knobs):
                 _knobs_in_force(dge, knobs)
-                m.train(corpus)
+                m.train(corpus) if launch is None else launch(m, corpus)
                 stats, sch, name = m.stats(), m.schedule(), m.kernel()
             label = "%s D=%d K=%d W=%d mag=%d policy=%d workers=%d %s run %s [%s, %.0f ms]" % (key, D, K, W, exp["mag"], policy, w, knobs or "", side, name, stats["kernel_ms"])
             assert stats["pairs"] == om.pairs, label

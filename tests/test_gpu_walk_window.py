@@ -32,16 +32,23 @@ def _slots(D, walk_len=L):
     return min(16, (LDS_BYTES - FIXED_BYTES - WG_WORKERS * 2 * stride * 4) // (walk_len * stride * 4 + ((walk_len + 3) & ~3) * 4))
 
 
-def _walks(NV, n, seed):
+def _walks(NV, n, seed, walk_len=L):
+    """ragged walks of up to walk_len tokens with holes; every fourth walk repeats a token (positions 3 and 7) and, where walks are longer than 32 tokens, is of full
+    length and repeats that token once more at position 35: one row behind two words of position bits; a walk of length 0 and one of length 1 among them"""
     rng = np.random.default_rng(seed)
-    ids = rng.integers(0, NV, (n, L)).astype(np.int32)
+    ids = rng.integers(0, NV, (n, walk_len)).astype(np.int32)
     rep = np.arange(n) % 4 == 0
-    ids[rep, 7] = ids[rep, 3]                                     # the same token twice in a walk: two positions, one row
-    ids[np.arange(L)[None, :] >= rng.integers(2, L + 1, n)[:, None]] = -1
+    if walk_len > 7:
+        ids[rep, 7] = ids[rep, 3]                                 # the same token twice in a walk: two positions, one row
+    lens = rng.integers(min(2, walk_len), walk_len + 1, n)
+    if walk_len > 35:
+        ids[rep, 35] = ids[rep, 3]
+        lens[rep] = walk_len
+    ids[np.arange(walk_len)[None, :] >= lens[:, None]] = -1
     ids[rng.random(ids.shape) < 0.05] = -1                       # holes
     if n >= 8:
         ids[5] = -1                                               # length 0
-        ids[6] = -1; ids[6, 11] = rng.integers(0, NV)             # length 1
+        ids[6] = -1; ids[6, min(11, walk_len - 1)] = rng.integers(0, NV)          # length 1
     return ids
 
 
@@ -57,20 +64,21 @@ def _release_module_state():
     _CASES.clear()
 
 
-def _case(oracle, NV, n, D, K, table):
-    """-> namespace(ids, cnt, V, exp {(side, sign): (state, oracle tables)}): one corpus and the sequential oracle's four saturated runs from it, computed once a module.
+def _case(oracle, NV, n, D, K, table, walk_len=L, window=W, epochs=1):
+    """-> namespace(ids, cnt, V, exp {(side, sign): (state, oracle tables)}): one corpus (walks of up to walk_len tokens) and the sequential oracle's four saturated runs
+    from it (window radius `window`, `epochs` passes in one call), computed once a module.
     Every vertex is in the vocabulary (counts = occurrences + 2) so that the vocabulary has NV rows whatever the corpus touches.  The premise is asserted on the
     reference alone: the standing table unchanged, the accumulating one whole multiples of alpha below 2^24."""
-    k = (NV, n, D, K)
+    k = (NV, n, D, K, table, walk_len, window, epochs)
     if k not in _CASES:
         if not _POOL:
             _POOL.append(cf.ThreadPoolExecutor(max_workers=4))
-        ids = _walks(NV, n, NV + n)
+        ids = _walks(NV, n, NV + n, walk_len)
         cnt = np.bincount(ids[ids >= 0], minlength=NV).astype(np.int64) + 2
         fut = {}
         for side, sign in RUNS:
             st = saturated_state(NV, D, side, sign, seed=SEED, mag=MAG)
-            fut[side, sign] = (st, _POOL[0].submit(oracle.train_sgns, ids, NV, D, W, negative=K, min_count=1, epochs=1, seed=SEED, table_size=table, alpha=SAT_ALPHA,
+            fut[side, sign] = (st, _POOL[0].submit(oracle.train_sgns, ids, NV, D, window, negative=K, min_count=1, epochs=epochs, seed=SEED, table_size=table, alpha=SAT_ALPHA,
                                                    min_alpha=SAT_ALPHA, arith=1, counts=cnt, syn0_init=st["syn0"], syn1neg_init=st["syn1neg"]))
         exp = {}
         for (side, sign), (st, f) in fut.items():
@@ -80,29 +88,30 @@ def _case(oracle, NV, n, D, K, table):
             units = getattr(om, moving)[:, 1:].astype(np.float64) / SAT_ALPHA
             assert (units == np.rint(units)).all() and np.abs(units).max() < 2 ** 24
             exp[side, sign] = (st, types.SimpleNamespace(syn0=om.syn0, syn1neg=om.syn1neg, pairs=om.pairs, vocab_ids=om.vocab_ids, V=om.V))
-        _CASES[k] = types.SimpleNamespace(ids=ids, cnt=cnt, V=NV, exp=exp, table=table, words=int((ids >= 0).sum()))
+        _CASES[k] = types.SimpleNamespace(ids=ids, cnt=cnt, V=NV, exp=exp, table=table, words=epochs * int((ids >= 0).sum()), walk_len=walk_len, window=window, epochs=epochs)
     return _CASES[k]
 
 
-def _model(dge, c, NV, D, K, workers):
+def _model(dge, c, NV, D, K, workers, window=W, epochs=1):
     import torch
-    cfg = dge.make_config(D, W, NV, negative=K, min_count=1, epochs=1, workers=workers, alpha=SAT_ALPHA, min_alpha=SAT_ALPHA, seed=SEED, table_size=c.table, update_policy=5)
+    cfg = dge.make_config(D, window, NV, negative=K, min_count=1, epochs=epochs, workers=workers, alpha=SAT_ALPHA, min_alpha=SAT_ALPHA, seed=SEED, table_size=c.table, update_policy=5)
     return dge.SgnsModel.create(cfg, torch.from_numpy(c.cnt).to("cuda:0"), 0)
 
 
-def _launch(dge, m, corpus, c, D, run, knobs, loop, label):
-    """one launch from the run's saturated state -> the tables; pairs, words, the kernel's name, the reported policy and the pair loop asserted"""
+def _launch(dge, m, corpus, c, D, run, knobs, loop, label, launch=None):
+    """one launch (`launch(m, corpus)`: the case's own way to train the corpus, an epoch a launch for instance) from the run's saturated state -> the tables; pairs,
+    words, the kernel's name, the reported policy and the pair loop — with the slots the corpus' walk length leaves room for — asserted"""
     st, om = c.exp[run]
     assert np.array_equal(m.vectors()[1], om.vocab_ids)
     _import_state(dge, m, st, -(-D // 64) * 64)
     m.reset_stats()
     with dge.tuning(**knobs):
         _knobs_in_force(dge, knobs)
-        m.train(corpus)
+        m.train(corpus) if launch is None else launch(m, corpus)
         stats, sch, name, pl = m.stats(), m.schedule(), m.kernel(), m.pair_loop()
     label = "%s -> %s, %d workers, pair loop %s" % (label, name, sch["workers"], pl)
     assert name == NAME and sch["update_policy"] == 5, label
-    assert pl == ({"loop": 1, "slots": _slots(D)} if loop else {"loop": 0, "slots": 0}), label
+    assert pl == ({"loop": 1, "slots": _slots(D, corpus.shape[1])} if loop else {"loop": 0, "slots": 0}), label
     assert stats["pairs"] == om.pairs and stats["words"] == c.words, (label, stats, om.pairs, c.words)
     return _read_tables(m, D, False), sch, label
 
