@@ -12,18 +12,11 @@ import numpy as np
 import pytest
 
 import helpers
+from eval_ref import host_map, look, mix64      # the draw rules' plain-numpy pieces live in tests/eval_ref.py
 
 pytestmark = pytest.mark.gpu
 
 U64 = np.uint64
-
-
-def mix64(x):
-    """splitmix64 (csrc/dge_algos.h: dge_mix64) on a uint64 array; array arithmetic wraps."""
-    x = np.atleast_1d(np.asarray(x, dtype=U64)) + U64(0x9E3779B97F4A7C15)
-    x = (x ^ (x >> U64(30))) * U64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> U64(27))) * U64(0x94D049BB133111EB)
-    return x ^ (x >> U64(31))
 
 
 def softplus(x):
@@ -33,16 +26,6 @@ def softplus(x):
 def gamma(D):
     u = 2.0 ** -24
     return D * u / (1.0 - D * u)
-
-
-def host_map(vid, NV):
-    remap = -np.ones(NV, np.int64); remap[vid.astype(np.int64)] = np.arange(len(vid))
-    return remap
-
-
-def look(remap, v):
-    v = np.asarray(v, np.int64)
-    return np.where((v >= 0) & (v < len(remap)), remap[np.clip(v, 0, len(remap) - 1)], -1)
 
 
 def dev_scores(m, ctx, tgt):
